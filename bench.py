@@ -3,9 +3,13 @@
 decode, driven by the GenerationSession block loop — BASELINE.json `configs[2]`.
 
   python bench.py --gpus N --steps K --warmup W        (N>1: launched by torch.distributed.run)
+  python bench.py ... --full                           (+ CPU baseline, context-parallel diagnostic block)
+  python bench.py ... --dump-outputs DIR               (+ the last timed block's outputs as DIR/<name>.npy)
 
 One "step" = one generated block = KV-recompute forward + 4 denoise forwards + VAE decode of 3 latent
 frames = 12 output frames.  Prints ONE JSON line on rank 0 (see README / DESIGN.md §Measurement).
+A plain run only sets up, warms up, times the K blocks and prints the line; the measurements that cost
+runs of their own (the CPU baseline, the eager per-rank diagnostic block of --gpus N) run under --full.
 """
 import argparse
 import json
@@ -34,6 +38,28 @@ MFMA_PEAK_TFLOPS = 2500.0  # dense bf16, MI355X (MI355X_MICROARCH.md)
 HBM_PEAK_TBPS = 8.0        # HBM3E, MI355X (MI355X_MICROARCH.md)
 MFMA_SUSTAINED_FP8_TFLOPS = 4350.0  # v_mfma_f32_32x32x64_f8f6f4 loop, random e4m3 operands (scripts/micro/fp8_mfma.hip)
 MFMA_SUSTAINED_TFLOPS = 1770.0  # measured: MFMA-only loop, random operands, clock settles at 1.78 GHz (profiles/r01_mfma_peak.txt)
+DUMP_BUDGET_BYTES = 64 << 20       # --dump-outputs: all .npy files together
+
+
+def dump_outputs(outdir, arrays):
+    """Write {name: tensor} as outdir/<name>.npy in float32, in order.  An array that would take the total past
+    DUMP_BUDGET_BYTES is written as <name>_sample.npy instead: its elements at a fixed, seeded, sorted set of flat indices
+    (the same for every run of the same command).  The contract configuration fits whole (latents 1.2 MB + pixels 57.5 MB)."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    left = DUMP_BUDGET_BYTES
+    written = {}
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().contiguous().numpy()
+        room = max(0, (left - 4096) // a.itemsize)          # (4 KiB per file for the .npy header)
+        if a.size > room:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=room, replace=False))
+            a, name = a.reshape(-1)[idx], name + "_sample"
+        path = os.path.join(outdir, name + ".npy")
+        np.save(path, a)
+        left -= os.path.getsize(path)
+        written[name] = list(a.shape)
+    return written
 
 
 def gemm_algorithmic_bytes(mc, M=4680):
@@ -166,7 +192,14 @@ def main():
     ap.add_argument("--kv-cache-num-frames", type=int, default=3)
     ap.add_argument("--denoising-steps", type=int, default=4)
     ap.add_argument("--no-vae", action="store_true", help="diagnostic only: skips the VAE (result is flagged invalid)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements that cost runs of their own: the CPU baseline (N = 1 line, ~2 min; "
+                         "--no-cpu-baseline drops it) and, for --gpus N / --cp-host-probe, one eager block behind the timed "
+                         "region with every kernel class and every wait for a collective bracketed (config.cp_diagnostics)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed blocks, write what the last one returned to its caller as DIR/<name>.npy (float32, "
+                         "<= 64 MiB in all): latents.npy (the denoised latents) and pixels.npy (the decoded frames)")
     ap.add_argument("--profile-classes", default="gemm,attn,conv,layernorm,rope",
                     help="kernel classes bracketed with hipEvents inside the timed region: 'gemm,attn,conv,layernorm,rope' (the roofline "
                          "kernel, the attention kernels, the VAE convolutions and the HBM-bound row kernels, default), 'all' "
@@ -231,17 +264,21 @@ def main():
         os.environ.setdefault("MASTER_PORT", "29531")
     shared_gpu = os.environ.get("RTV_BENCH_SHARED_GPU") == "1"
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
-        # `python bench.py --gpus N` without a launcher: re-execute under torch.distributed.run, one rank per GPU of this node
+        # `python bench.py --gpus N` without a launcher: run torch.distributed.run as a child process, one rank per GPU of this
+        # node, and exit with its status (not exec: this process has initialised the GPU, and replacing the program of such a
+        # process is not safe)
         if torch.cuda.device_count() < args.gpus and not shared_gpu:
             raise SystemExit(f"bench.py: --gpus {args.gpus} requested but only {torch.cuda.device_count()} GPU(s) visible")
         import socket
+        import subprocess
         sock = socket.socket()
         sock.bind(("127.0.0.1", 0))
         port = sock.getsockname()[1]
         sock.close()
         os.dup2(json_fd, 1)      # the launcher and its ranks inherit the real stdout
-        os.execv(sys.executable, [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
-                                  "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:])
+        res = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
+                              "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:])
+        sys.exit(res.returncode)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -365,7 +402,7 @@ def main():
     prompt[:, :64] = torch.randn(1, 64, 4096, generator=g, device=dev).to(torch.bfloat16)
     models = Models(transformer=wr, pipeline=pipe, text_encoder=StaticTextEncoder(prompt), vae_decoder=vae,
                     vae_encoder=vae_enc)
-    diag_blocks = 1 if use_cp else 0      # one eager, fully bracketed block behind the timed region (untimed; --cp-host-probe too)
+    diag_blocks = 1 if use_cp and args.full else 0   # --full: one eager, fully bracketed block behind the timed region (untimed; --cp-host-probe too)
     # (the session's noise tensor is drawn in one call whose values depend on its SIZE - the generator's grid follows numel - so every
     # run reserves the diagnostic block, context parallel or not: an N-rank run and the single-GPU run of the same command see the same
     # noise and their last timed block can be compared bit for bit, tests/test_context_parallel_gpu.py)
@@ -444,6 +481,11 @@ def main():
     latents_checksum = {"sha256_bf16": hashlib.sha256(sess.last_pred.detach().cpu().contiguous().view(torch.int16).numpy().tobytes()).hexdigest()[:16],
                         "abs_sum": float(lat.double().abs().sum()), "mean": float(lat.double().mean()),
                         "shape": list(lat.shape)}
+    if args.dump_outputs and rank == 0:   # (before the diagnostic block: it generates one more block)
+        # what the caller of generate_block received from the last timed block: the decoded frames (the denoised latents with
+        # --no-vae), and the denoised latents themselves
+        dumped = dump_outputs(args.dump_outputs, {"latents": sess.last_pred} if args.no_vae else {"latents": sess.last_pred, "pixels": out})
+        print(f"[bench] outputs of the last timed block -> {args.dump_outputs}: {dumped}", file=sys.stderr)
 
     step_ms = [e0.elapsed_time(e1) for rc, e0, e1 in wr.events if not rc]
     recompute_ms = [e0.elapsed_time(e1) for rc, e0, e1 in wr.events if rc]
@@ -640,7 +682,7 @@ def main():
                 for name, v in prof.items() if name in ("attn", "conv", "layernorm", "rope") and v["ms"] > 0},
         },
     }
-    if not args.no_cpu_baseline and world == 1:      # the CPU baseline belongs to the N = 1 line only (rank 0's host cores, ~2 min)
+    if args.full and not args.no_cpu_baseline and world == 1:   # the CPU baseline belongs to the N = 1 line only (rank 0's host cores, ~2 min)
         result["cpu_baseline"] = cpu_baseline(mc, with_vae=not args.no_vae)
     sys.stdout.flush()
     os.write(json_fd, (json.dumps(result) + "\n").encode())

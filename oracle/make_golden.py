@@ -630,6 +630,47 @@ def golden_loader_manifest(ref):
         json.dump(out, f, indent=1, sort_keys=True)
 
 
+def golden_cache_window(ref):
+    """tests/golden/cache_window_reference.json: the reference's CausalWanModel (1 layer, tiny dims) driven through random call
+    sequences with local attention windows and sinks (frames 1 or 3 per call, repeated calls on the same block); after every
+    call its cache indices and the rows of its K cache left non-zero, as [start, end) of the written rows and whether they are
+    contiguous.  tests/test_capi_and_host.py replays the same sequences through CausalWanModel._cache_window.  Data only."""
+    import json
+    import random
+    rng = random.Random(11)
+    fs = 1560
+    g = torch.Generator().manual_seed(2)
+    ctx = torch.randn(64, TEXT_DIM, generator=g).to(torch.bfloat16)
+    trials = []
+    for trial, (las, sink) in enumerate([(4, 0), (6, 1), (6, 2), (9, 1)]):
+        cfg = dict(TINY, num_layers=1, local_attn_size=las, sink_size=sink)
+        w = wo.make_weights(cfg, seed=trial, text_dim=TEXT_DIM)
+        wr = ref_shim.build_reference_wrapper(ref, ref_shim.build_reference_model(ref, cfg, w, TEXT_DIM))
+        kv_size = las * fs
+        rkv = [{"k": torch.zeros(1, kv_size, 2, 128, dtype=torch.bfloat16), "v": torch.zeros(1, kv_size, 2, 128, dtype=torch.bfloat16),
+                "global_end_index": torch.tensor([0]), "local_end_index": torch.tensor([0])}]
+        rca = [{"k": torch.zeros(1, 512, 2, 128, dtype=torch.bfloat16), "v": torch.zeros(1, 512, 2, 128, dtype=torch.bfloat16),
+                "is_init": False}]
+        calls, cur = [], 0
+        for call in range(7):
+            frames = rng.choice([1, 3])
+            if call and rng.random() < 0.35:
+                cur, frames = prev
+            lat = torch.randn(1, frames, 16, 60, 104, generator=g).to(torch.bfloat16)
+            with torch.inference_mode():
+                wr(lat, {"prompt_embeds": [ctx]}, torch.ones([1, frames], dtype=torch.int64) * 500, rkv, rca, current_start=cur)
+            written = (rkv[0]["k"][0].float().abs().sum((-1, -2)) > 0).nonzero().flatten().tolist()
+            lo, hi = (written[0], written[-1] + 1) if written else (0, 0)
+            calls.append({"current_start": cur, "frames": frames, "global_end_index": int(rkv[0]["global_end_index"]),
+                          "local_end_index": int(rkv[0]["local_end_index"]), "written_rows": [lo, hi],
+                          "written_contiguous": len(written) == hi - lo})
+            prev = (cur, frames)
+            cur += frames * fs
+        trials.append({"local_attn_size": las, "sink_size": sink, "kv_size": kv_size, "calls": calls})
+    with open(os.path.join(OUT, "cache_window_reference.json"), "w") as f:
+        json.dump({"frame_seq_length": fs, "trials": trials}, f, indent=1)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     torch.manual_seed(0)
@@ -637,6 +678,8 @@ if __name__ == "__main__":
     which = sys.argv[1:] or ["ops", "dit", "rolling", "vae", "vae_single", "vae_enc", "vae_wrapper", "t5", "session", "webcam", "start_frame", "v2v", "pipeline"]
     if "loader_manifest" in which:   # not in the default list (names / shapes only; does not change unless upstream's modules do)
         golden_loader_manifest(ref)
+    if "cache_window" in which:      # not in the default list (indices only; does not change unless upstream's modules do)
+        golden_cache_window(ref)
     if "ops" in which:
         golden_ops(ref)
     if "dit" in which:

@@ -77,7 +77,9 @@ EXTRA_SIGNATURES = {}
 
 def build(verbose=False):
     """Compile librtv_hip.so for gfx950 with hipcc (cross-compiles without a GPU)."""
-    cmd = ["make", "-C", CSRC, "-j", str(os.cpu_count() or 4)]
+    # MAX_JOBS if the environment sets it, else the CPUs this process may use, at most 16 (os.cpu_count() counts the whole host)
+    jobs = os.environ.get("MAX_JOBS") or str(min(16, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else os.cpu_count() or 4))
+    cmd = ["make", "-C", CSRC, "-j", jobs]
     res = subprocess.run(cmd, capture_output=True, text=True)
     if verbose or res.returncode != 0:
         print(res.stdout[-4000:])

@@ -107,7 +107,7 @@ def test_two_process_context_parallel_session_equals_single_process(exchange, ba
 @pytest.mark.parametrize("exchange", ["heads", "rows"])
 def test_eight_rank_bench_launcher_path_equals_single_process(exchange):
     """Eight-rank readiness without an eight-GPU node: `bench.py --gpus 8` through ITS OWN launcher path
-    (re-exec under torch.distributed.run, one process per rank, ContextParallel + row-sharded VAE decode + pixel all-gather +
+    (torch.distributed.run as a child process, one process per rank, ContextParallel + row-sharded VAE decode + pixel all-gather +
     frame delivery), all ranks sharing cuda:0 with gloo collectives (RTV_BENCH_SHARED_GPU=1), on the test-rig model (8 heads: one
     head per rank under the head exchange; 585 token rows per rank).  The last block's latents must be bit-identical with the
     single-process run of the same command.  attn_kv_splits 1 and GEMM tile config 4 (no split-K): the default dispatch splits K
@@ -155,7 +155,8 @@ def test_bench_context_parallel_line_carries_per_rank_diagnostics():
     env.pop("RANK", None)
 
     def run(args, **extra):
-        res = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + args + ["--steps", "1", "--warmup", "2", "--no-cpu-baseline"],
+        res = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + args + ["--steps", "1", "--warmup", "2", "--full",
+                                                                                     "--no-cpu-baseline"],
                              capture_output=True, text=True, env=dict(env, **extra), timeout=500, cwd=root)
         assert res.returncode == 0, res.stderr[-3000:]
         return json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
@@ -177,3 +178,35 @@ def test_bench_context_parallel_line_carries_per_rank_diagnostics():
     assert rec["kernel_ms_per_block"]["gemm"] > 0 and set(rec["exposed_collective_ms_per_block"]) >= {"exchange_kv", "exchange_o"}
     assert rec["exposed_collective_ms_per_block"]["exchange_kv"]["waits"] == 40 * 5
     assert rec["exposed_collective_ms_per_block"]["exchange_o"]["waits"] == 40 * 5 - 1
+
+
+@pytest.mark.timeout(600)
+def test_bench_plain_line_times_steps_and_dumps_the_last_block(tmp_path):
+    """A plain `bench.py` line (no --full) times exactly --steps blocks and carries neither the CPU baseline nor the diagnostic block;
+    `--dump-outputs DIR` writes what the last timed block returned (float32, <= 64 MiB in all): the denoised latents - the ones the
+    line's checksum describes - and the 12 decoded frames."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None)
+    env.pop("RANK", None)
+    out = tmp_path / "outputs"
+    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--model", "tiny", "--steps", "2", "--warmup", "1",
+                          "--dump-outputs", str(out)], capture_output=True, text=True, env=env, timeout=500, cwd=root)
+    assert res.returncode == 0, res.stderr[-3000:]
+    line = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["steps"] == 2 and line["ms_per_step"] > 0
+    assert abs(line["value"] * line["ms_per_step"] / 1e3 - 12.0) < 1e-6          # 12 frames per timed block
+    assert "cpu_baseline" not in line and line["config"]["cp_diagnostics"] is None
+    files = sorted(p.name for p in out.iterdir())
+    assert files == ["latents.npy", "pixels.npy"], files
+    assert sum(p.stat().st_size for p in out.iterdir()) <= 64 << 20
+    lat, px = np.load(out / "latents.npy"), np.load(out / "pixels.npy")
+    assert lat.dtype == np.float32 and px.dtype == np.float32
+    ck = line["config"]["last_block_latents_checksum"]
+    assert list(lat.shape) == ck["shape"] == [1, 3, 16, 60, 104]
+    assert abs(float(np.abs(lat.astype(np.float64)).sum()) - ck["abs_sum"]) <= 1e-9 * ck["abs_sum"]
+    assert px.shape[1] == 12 and np.isfinite(px).all()
