@@ -469,6 +469,41 @@ int rtv_vae_enc_cache_slot(int H, int W, int slot, size_t* offset, int* C, int* 
 int rtv_vae_encode(const rtv_vae_enc_weights* w, const void* frames, int Ttot, int t0, int tn, int H, int W, int first,
                    void* arena, size_t arena_bytes, void* mu, int Tout_tot, int tout, rtv_stream_t stream);
 
+/* ---- TAEHV tiny-VAE streaming decoder (opt-in fast decode, `use_taehv`; csrc/taehv.hip) ----------------------------
+ * The `decoder` of demo_utils/taehv.py:159-234 (checkpoint taew2_1.pth): Clamp, conv 16 -> 256, three stages of three
+ * MemBlocks (256, 128, 64 channels) with nearest-2x upsampling + TGrow between them, conv 64 -> 64, ReLU, conv 64 -> 3.
+ * Weights fp16 [Cout][taps][Cin] as for the Wan decoder. */
+typedef struct rtv_taehv_weights {
+  rtv_vae_conv conv_in;      /* decoder.1: [256][9][32] (Cin padded 16 -> 32), bias [256] */
+  rtv_vae_conv mem[9][3];    /* MemBlocks decoder.{3,4,5,9,10,11,15,16,17}, conv.{0,2,4} with biases.  conv.0 is [C][18][C]:
+                                taps 0-8 read x_{t-1} (its input channels C..2C-1), taps 9-17 read x_t (channels 0..C-1);
+                                conv.2 / conv.4 are [C][9][C] */
+  const void* up[3];         /* TGrow decoder.{7,13,19} folded into the conv behind it, decoder.{8,14,20}:
+                                [stride * Cout][9][Cin], filter s * Cout + o = output channel o of frame stride * t + s
+                                (up[0]: [128][9][256]; up[1]: [2 * 64][9][128]; up[2]: [2 * 64][9][64]); no bias */
+  rtv_vae_conv head;         /* decoder.22: [8][9][64] (Cout padded 3 -> 8), bias [8] */
+} rtv_taehv_weights;
+
+/* Caller-owned arena: the nine MemBlock state slices (each block's input at the previous frame of its own rate) at the
+ * front, at offsets that depend on (h, w) only, then scratch for calls of up to t_max latent frames.  0 = unsupported size. */
+size_t rtv_taehv_arena_bytes(int h, int w, int t_max);
+/* State slice `slot` (0..8 = MemBlock decoder.{3,4,5,9,10,11,15,16,17}): fp16 channels-last [H][W][C] at arena + offset. */
+int rtv_taehv_state_slot(int h, int w, int slot, size_t* offset, int* C, int* H, int* W);
+/* z: fp16 [T][16][h][w] latents; pixels: float32 [T'][3][8h][8w], clamp(2 * decoder - 1, -1, 1).  first = 1 zeroes the
+ * state and drops TAEHV's 3 warm-up frames (T' = 4T - 3); otherwise T' = 4T.  Bit-identical however a stream is split
+ * into calls. */
+int rtv_taehv_decode(const rtv_taehv_weights* w, const void* z, int T, int h, int wd, int first, void* arena,
+                     size_t arena_bytes, void* pixels, rtv_stream_t stream);
+/* One TAEHV convolution (3x3, zero padding 1) on channels-last fp16, the layer kernel of rtv_taehv_decode (tests):
+ * output frame t reads input slices t .. t + kt - 1 (kt = 2: the MemBlock [x_{t-1} | x_t] window, w [Cout][18][Cin]);
+ * ups = 1 reads through a nearest-2x upsampling (in: [.][H/2][W/2][Cin]); out = conv + bias, then ReLU if relu, or
+ * ReLU(conv + bias + residual[M][Cout]) if residual; n_split = Cout / 2 scatters filter group s to frame 2t + s (out
+ * [2T][H][W][n_split]); head = 1 (Cout 8): out float32 [T][3][H][W] = clamp(2 * (conv + bias) - 1, -1, 1).
+ * Cin % 32 == 0; Cout 64 or a multiple of 128 (head: 8); 16-byte aligned pointers; zeros >= 16 bytes of zeros. */
+int rtv_taehv_conv(const void* in, const void* w, const void* bias, const void* residual, void* out, int T, int H, int W,
+                   int Cin, int Cout, int kt, int ups, int n_split, int relu, int head, const void* zeros,
+                   rtv_stream_t stream);
+
 /* ---- hardware-layout probes (test support; see csrc/probe.hip) --------------------------------- */
 int rtv_probe_mfma(const void* A /*[32][16] bf16*/, const void* B /*[16][32] bf16*/, void* D /*[32][32] f32*/,
                    rtv_stream_t stream);

@@ -1,0 +1,514 @@
+// TAEHV tiny-VAE streaming decoder (the `decoder` nn.Sequential of demo_utils/taehv.py:159-234, checkpoint taew2_1.pth for
+// Wan 2.1): the opt-in fast decode behind `use_taehv`.  fp16 channels-last activations, fp32 accumulation on MFMA.
+//
+// Every layer is a 3x3 'same' convolution run as an implicit GEMM (the LDS-DMA gather idiom of vae_conv.hip's
+// conv_igemm_kernel, on its own kernel here so that the Wan decoder's code objects stay as they are):
+//   out[pixel][co] = epilogue( sum_{dt, dy, dx, ci} in[slice t + dt][y + dy - 1][x + dx - 1][ci] * W[co][(dt * 3 + dy) * 3 + dx][ci] )
+//   * MemBlock conv1 over cat[x_t, x_{t-1}] is a 2-slice convolution (kt = 2) over a [x_{t-1} | x_t] window of a concat buffer
+//     [state | T new slices]: output frame t reads slices t and t + 1, the weight's time tap 0 holds the x_{t-1} half of
+//     conv.0 (input channels C..2C-1), tap 1 the x_t half.  The channel concat is never materialised; slice 0 is the block's
+//     carried state (its input at the previous frame, zeros on a stream's first call);
+//   * nearest-2x upsampling is read through the gather (source = coordinate >> 1);
+//   * TGrow (a bias-free 1x1 conv C -> stride * C, channel group s -> frame stride * t + s) is FOLDED into the 3x3 conv behind
+//     it: nearest upsampling commutes with a 1x1 conv and the conv's zero padding is TGrow(0) = 0, so the composed filters
+//     Wf[s * Cout + o][tap][c] = sum_c' Wconv[o][c'][tap] * Wtgrow[s * C + c'][c] (composed in fp32 on the host, then fp16)
+//     give the same function; filter group s is scattered to frame stride * t + s in the epilogue (n_split).  Not bit-identical
+//     with the unfolded two-layer form (one fp16 rounding of the composed weight instead of one of the TGrow output);
+//   * epilogues: + bias, ReLU, the MemBlock tail ReLU(conv + bias + x_t) (x_t = the block's input slices), and the head
+//     out = clamp(2 * (conv + bias) - 1, -1, 1) written as float32 [T][3][H][W] (3 filters padded to 8);
+//   * Clamp (tanh(x / 3) * 3) is the prologue of the first conv: taehv_prep_kernel applies it while it transposes the latents
+//     to channels-last and pads 16 -> 32 channels.
+// The K order of an output pixel is (dt, dy, dx, channel slab), the same for every tile position and every T, and no
+// launch splits K: a stream decoded as 3 + 3, 1 x 6 or 2 + 4 latent frames per call gives bit-identical pixels.  The tile
+// configuration is chosen from the layer (Cout, head) only.
+#include "gemm_core.h"
+#include "rtv_internal.h"
+
+namespace rtv {
+namespace tae {
+
+struct ConvParams {
+  const uint16_t* in;        // [T + kt - 1][inH][inW][Cin]
+  const uint16_t* w;         // [Cout][kt * 9][Cin]
+  const uint16_t* bias;      // [Cout] or null
+  const uint16_t* residual;  // [M][Cout] or null: out = ReLU(conv + bias + residual)
+  void* out;                 // f16 [M][Cout] (n_split: f16 [2T][H][W][n_split]); head: float32 [T][3][H][W]
+  const uint16_t* zeros;     // >= 16 bytes of zeros
+  int T, H, W;               // output grid
+  int inH, inW;              // input grid (H >> ups)
+  int Cin, Cout, kt, ups, n_split, relu;
+  int M, tiles_m, tiles_n;
+};
+
+template <int TN>
+__device__ __forceinline__ int img_off(int row, int chunk, int half) {   // conv_img_off of vae_conv.hip (TN = 2)
+  static_assert(TN == 2, "epilogue image laid out for two 32-filter blocks per wave");
+  return row * 128 + ((chunk ^ (row & 7)) << 4) + ((half ^ ((row >> 3) & 1)) << 3);
+}
+
+template <int BM, int BN, int BK, int WM, int WN, bool HEAD>
+__global__ __launch_bounds__(WM* WN * 64) void taehv_conv_kernel(ConvParams p) {
+  typedef TileCfg<BM, BN, BK, WM, WN> Cfg;
+  constexpr int STAGES = 3;
+  constexpr int PIECES = Cfg::A_INST + Cfg::B_INST;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+
+  const int id = xcd_remap(blockIdx.x, p.tiles_m * p.tiles_n);
+  const int tile_m = id / p.tiles_n, tile_n = id % p.tiles_n;
+  const int m0 = tile_m * BM, n0 = tile_n * BN;
+
+  const int cpos = lane % Cfg::CH;
+  const int rsub = lane / Cfg::CH;
+  const int HW = p.H * p.W;
+  // per-lane gather state (see conv_igemm_kernel): base offset of the lane's pixel in the input, in-image bits of its 3 x 3
+  // neighbourhood (bits 0-2 rows, 3-5 columns) and, with upsampling, the parities of its row / column (bits 6, 7)
+  int base_off[Cfg::A_INST], flags[Cfg::A_INST];
+#pragma unroll
+  for (int i = 0; i < Cfg::A_INST; ++i) {
+    const int row = (wave * Cfg::A_INST + i) * Cfg::RPI + rsub;
+    const int m = min(m0 + row, p.M - 1);
+    const int pt = m / HW;
+    const int rem = m - pt * HW;
+    const int py = rem / p.W, px = rem - py * p.W;
+    int f = 0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      if (py + k - 1 >= 0 && py + k - 1 < p.H) f |= 1 << k;
+      if (px + k - 1 >= 0 && px + k - 1 < p.W) f |= 8 << k;
+    }
+    if (p.ups) f |= ((py & 1) << 6) | ((px & 1) << 7);
+    flags[i] = f;
+    base_off[i] = ((pt * p.inH + (py >> p.ups)) * p.inW + (px >> p.ups)) * p.Cin + Cfg::swz(row, cpos) * 8;
+  }
+  uint32_t b_off[Cfg::B_INST];
+  const int Ktot = p.kt * 9 * p.Cin;
+#pragma unroll
+  for (int i = 0; i < Cfg::B_INST; ++i) {
+    const int row = (wave * Cfg::B_INST + i) * Cfg::RPI + rsub;
+    const int gn = min(n0 + row, p.Cout - 1);
+    b_off[i] = (uint32_t)gn * (uint32_t)Ktot + Cfg::swz(row, cpos) * 8;
+  }
+  const int nk = p.kt * 9 * (p.Cin / BK);
+  const int slice = p.inH * p.inW * p.Cin;
+
+  int is_dt = 0, is_dy = 0, is_dx = 0, is_c = 0, is_ks = 0;
+  const uint16_t* a_src[Cfg::A_INST];
+  int a_live[Cfg::A_INST];
+  auto tap_setup = [&]() __attribute__((always_inline)) {
+    const int ry = is_dy - 1, rx = is_dx - 1;
+    const int row_e = p.ups ? (ry >> 1) : ry, row_o = p.ups ? ((ry + 1) >> 1) : ry;
+    const int col_e = p.ups ? (rx >> 1) : rx, col_o = p.ups ? ((rx + 1) >> 1) : rx;
+    const int t_off = is_dt * slice;
+    const int d_re = t_off + row_e * p.inW * p.Cin, d_ro = t_off + row_o * p.inW * p.Cin;
+    const int d_ce = col_e * p.Cin, d_co = col_o * p.Cin;
+#pragma unroll
+    for (int i = 0; i < Cfg::A_INST; ++i) {
+      const int f = flags[i];
+      const bool ok = ((f >> is_dy) & (f >> (3 + is_dx)) & 1) != 0;
+      const int off = base_off[i] + ((f & 64) ? d_ro : d_re) + ((f & 128) ? d_co : d_ce);
+      a_src[i] = ok ? p.in + (ptrdiff_t)off : p.zeros;
+      a_live[i] = ok ? 1 : 0;
+    }
+  };
+  auto issue = [&]() __attribute__((always_inline)) {
+    char* sA = smem + (is_ks % STAGES) * Cfg::STAGE_BYTES;
+    char* sB = sA + Cfg::A_BYTES;
+    if (is_c == 0) tap_setup();
+#pragma unroll
+    for (int i = 0; i < Cfg::A_INST; ++i) dma16(a_src[i] + a_live[i] * is_c, sA + (wave * Cfg::A_INST + i) * 1024);
+    const uint16_t* Wk = p.w + (size_t)is_ks * BK;
+#pragma unroll
+    for (int i = 0; i < Cfg::B_INST; ++i) dma16(Wk + b_off[i], sB + (wave * Cfg::B_INST + i) * 1024);
+    ++is_ks;
+    is_c += BK;
+    if (is_c == p.Cin) {
+      is_c = 0;
+      if (++is_dx == 3) {
+        is_dx = 0;
+        if (++is_dy == 3) {
+          is_dy = 0;
+          ++is_dt;
+        }
+      }
+    }
+  };
+
+  f32x16 acc[Cfg::TM][Cfg::TN];
+#pragma unroll
+  for (int mi = 0; mi < Cfg::TM; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < Cfg::TN; ++ni)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
+
+  const int wm = wave / WN, wn = wave % WN;
+  const int a_row0 = wm * (BM / WM), b_row0 = wn * (BN / WN);
+
+#define TV_FENCE() __builtin_amdgcn_sched_barrier(0)
+  issue();
+  if (nk > 1) issue();
+  for (int ks = 0; ks < nk; ++ks) {
+    if (ks + 1 < nk) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PIECES) : "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    TV_FENCE();
+    __builtin_amdgcn_s_barrier();
+    TV_FENCE();
+    if (ks + 2 < nk) issue();
+    TV_FENCE();
+    const char* sA = smem + (ks % STAGES) * Cfg::STAGE_BYTES;
+    mma_stage<true, Cfg, BK>(sA, sA + Cfg::A_BYTES, a_row0, b_row0, lane, acc);
+    TV_FENCE();
+  }
+  __builtin_amdgcn_s_barrier();
+  TV_FENCE();
+#undef TV_FENCE
+
+  const int l31 = lane & 31, g = lane >> 5;
+  if constexpr (HEAD) {
+    // filters 0..2 of the (one) 32-filter block sit in quad rq = 0 of the lanes with g = 0: float32 planar stores, 32
+    // consecutive pixels per channel and instruction
+    if (g != 0 || n0 + b_row0 != 0) return;
+    float* out = (float*)p.out;
+    const float b0 = p.bias ? f16_to_f32(p.bias[0]) : 0.f, b1 = p.bias ? f16_to_f32(p.bias[1]) : 0.f,
+                b2 = p.bias ? f16_to_f32(p.bias[2]) : 0.f;
+#pragma unroll
+    for (int mi = 0; mi < Cfg::TM; ++mi) {
+      const int m = m0 + a_row0 + mi * 32 + l31;
+      if (m >= p.M) continue;
+      const int t = m / HW, pix = m - t * HW;
+      float* o = out + (size_t)t * 3 * HW + pix;
+      o[0] = fminf(fmaxf(2.f * (acc[mi][0][0] + b0) - 1.f, -1.f), 1.f);
+      o[HW] = fminf(fmaxf(2.f * (acc[mi][0][1] + b1) - 1.f, -1.f), 1.f);
+      o[2 * (size_t)HW] = fminf(fmaxf(2.f * (acc[mi][0][2] + b2) - 1.f, -1.f), 1.f);
+    }
+    return;
+  } else {
+    // bias, then through a wave-private LDS image so that every lane moves 16 contiguous bytes of a pixel's channels;
+    // residual + ReLU / ReLU on the way out
+    constexpr int TM = Cfg::TM, TN = Cfg::TN, CPR = TN * 4;
+    char* img = smem + wave * (TM * 32 * TN * 64);
+    constexpr int PASSES = TM * 32 * CPR / 64;
+    u32x4 res_pre[PASSES];
+    if (p.residual) {
+#pragma unroll
+      for (int ps = 0; ps < PASSES; ++ps) {
+        const int q = ps * 64 + lane;
+        const int row = q / CPR, c = q - row * CPR;
+        const int m = min(m0 + a_row0 + row, p.M - 1), n = min(n0 + b_row0 + c * 8, p.Cout - 8);   // clamped rows are never stored
+        res_pre[ps] = *(const u32x4*)(p.residual + (size_t)m * p.Cout + n);
+      }
+    }
+#pragma unroll
+    for (int mi = 0; mi < TM; ++mi) {
+      const int row = mi * 32 + l31;
+#pragma unroll
+      for (int ni = 0; ni < TN; ++ni)
+#pragma unroll
+        for (int rq = 0; rq < 4; ++rq) {
+          const int n = min(n0 + b_row0 + ni * 32 + rq * 8 + g * 4, p.Cout - 4);
+          float v[4] = {acc[mi][ni][rq * 4 + 0], acc[mi][ni][rq * 4 + 1], acc[mi][ni][rq * 4 + 2], acc[mi][ni][rq * 4 + 3]};
+          if (p.bias) {
+            const u32x2 bb = *(const u32x2*)(p.bias + n);
+            v[0] += f16_to_f32(bb[0] & 0xffff);
+            v[1] += f16_to_f32(bb[0] >> 16);
+            v[2] += f16_to_f32(bb[1] & 0xffff);
+            v[3] += f16_to_f32(bb[1] >> 16);
+          }
+          u32x2 o;
+          o[0] = pack_f16x2(v[0], v[1]);
+          o[1] = pack_f16x2(v[2], v[3]);
+          *(u32x2*)(img + img_off<TN>(row, ni * 4 + rq, g)) = o;
+        }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    uint16_t* out = (uint16_t*)p.out;
+#pragma unroll
+    for (int ps = 0; ps < PASSES; ++ps) {
+      const int q = ps * 64 + lane;
+      const int row = q / CPR, c = q - row * CPR;
+      const int m = m0 + a_row0 + row;
+      const int n = n0 + b_row0 + c * 8;
+      u32x4 t = *(const u32x4*)(img + img_off<TN>(row, c, 0) - (((row >> 3) & 1) << 3));   // chunk start; halves swapped on odd octets
+      if ((row >> 3) & 1) t = u32x4{t[2], t[3], t[0], t[1]};
+      if (m >= p.M || n >= p.Cout) continue;
+      if (p.residual || p.relu) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          float a0, a1;
+          unpack_f16x2(t[i], a0, a1);
+          if (p.residual) {
+            float r0, r1;
+            unpack_f16x2(res_pre[ps][i], r0, r1);
+            a0 += r0;
+            a1 += r1;
+          }
+          t[i] = pack_f16x2(fmaxf(a0, 0.f), fmaxf(a1, 0.f));
+        }
+      }
+      size_t drow = (size_t)m;
+      int ch = n, ld = p.Cout;
+      if (p.n_split > 0) {
+        const int tt = m / HW, pix = m - tt * HW;
+        const int grp = n / p.n_split;
+        drow = (size_t)(2 * tt + grp) * HW + pix;
+        ch = n - grp * p.n_split;
+        ld = p.n_split;
+      }
+      *(u32x4*)(out + drow * ld + ch) = t;
+    }
+  }
+}
+
+template <int BM, int BN, int BK, int WM, int WN, bool HEAD>
+static int launch_cfg(ConvParams p, hipStream_t stream) {
+  typedef TileCfg<BM, BN, BK, WM, WN> Cfg;
+  static_assert(HEAD || Cfg::NW * Cfg::TM * 32 * Cfg::TN * 64 <= 3 * Cfg::STAGE_BYTES, "epilogue image must fit the stage buffers");
+  static_assert(HEAD || Cfg::TN == 2, "epilogue image layout");
+  static_assert(!HEAD || (BN == 32 && WN == 1), "head: one 32-filter block");
+  p.tiles_m = (p.M + BM - 1) / BM;
+  p.tiles_n = (p.Cout + BN - 1) / BN;
+  const int lds = 3 * Cfg::STAGE_BYTES;
+  auto kern = taehv_conv_kernel<BM, BN, BK, WM, WN, HEAD>;
+  static LdsAttr lds_attr;
+  if (int st = ensure_dynamic_lds((const void*)kern, lds, &lds_attr, "taehv_conv")) return st;
+  ProfScope prof(PROF_CONV, stream, 2.0 * p.M * (double)p.Cout * p.kt * 9 * p.Cin);
+  hipLaunchKernelGGL(kern, dim3(p.tiles_m * p.tiles_n), dim3(Cfg::NT), lds, stream, p);
+  return check_launch("taehv_conv");
+}
+
+// One layer.  The kernel configuration is a function of the layer only (head or Cout), never of T / H / W.
+static int launch_conv(ConvParams p, int head, hipStream_t stream) {
+  if (!p.in || !p.w || !p.out || !p.zeros) return set_error(-1, "taehv_conv: null pointer");
+  if (p.T <= 0) return 0;
+  if (p.H <= 0 || p.W <= 0) return set_error(-1, "taehv_conv: bad size");
+  if (p.kt != 1 && p.kt != 2) return set_error(-1, "taehv_conv: kt must be 1 or 2");
+  if (p.ups != 0 && p.ups != 1) return set_error(-1, "taehv_conv: ups must be 0 or 1");
+  if (p.ups && ((p.H | p.W) & 1)) return set_error(-1, "taehv_conv: upsampled output dims must be even");
+  if (p.Cin <= 0 || p.Cin % 32) return set_error(-1, "taehv_conv: Cin must be a multiple of 32 (pad channels)");
+  if (head ? p.Cout != 8 : (p.Cout != 64 && p.Cout % 128 != 0))
+    return set_error(-1, "taehv_conv: Cout must be 8 (head), 64 or a multiple of 128");
+  if (head && (p.residual || p.n_split || p.relu)) return set_error(-1, "taehv_conv: the head has a bias-only epilogue");
+  if (p.n_split && (p.n_split % 8 || p.Cout != 2 * p.n_split)) return set_error(-1, "taehv_conv: n_split must be Cout / 2");
+  if ((((uintptr_t)p.in | (uintptr_t)p.w | (uintptr_t)p.out | (uintptr_t)p.residual | (uintptr_t)p.zeros) & 15) ||
+      ((uintptr_t)p.bias & 7))
+    return set_error(-1, "taehv_conv: pointers must be 16-byte aligned (bias 8)");
+  p.inH = p.H >> p.ups;
+  p.inW = p.W >> p.ups;
+  // the gather indexes the input with 32-bit element offsets
+  if ((size_t)(p.T + p.kt - 1) * p.inH * p.inW * p.Cin >= 0x7fffffffull || (size_t)p.T * p.H * p.W >= 0x7fffffffull)
+    return set_error(-1, "taehv_conv: input too large for 32-bit offsets");
+  p.M = p.T * p.H * p.W;
+  if (head) return launch_cfg<128, 32, 32, 2, 1, true>(p, stream);
+  if (p.Cout == 64) return launch_cfg<256, 64, 32, 4, 1, false>(p, stream);
+  return launch_cfg<128, 128, 32, 2, 2, false>(p, stream);
+}
+
+// z fp16 [T][16][h][w] -> Clamp (tanh(x / 3) * 3) -> channels-last [T][h][w][32] (16 real + 16 zero channels)
+__global__ void taehv_prep_kernel(const f16_t* __restrict__ z, int T, int hw, f16_t* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (int64_t)T * hw) return;
+  const int64_t t = i / hw, p = i - t * hw;
+  u32x4 o[4];
+#pragma unroll
+  for (int c = 0; c < 16; c += 2) {
+    const float a = f16_to_f32(z[(t * 16 + c) * hw + p]), b = f16_to_f32(z[(t * 16 + c + 1) * hw + p]);
+    o[c >> 3][(c & 7) >> 1] = pack_f16x2(tanhf(a / 3.f) * 3.f, tanhf(b / 3.f) * 3.f);
+  }
+  o[2] = u32x4{0u, 0u, 0u, 0u};
+  o[3] = u32x4{0u, 0u, 0u, 0u};
+  u32x4* dst = (u32x4*)(out + i * 32);
+  dst[0] = o[0];
+  dst[1] = o[1];
+  dst[2] = o[2];
+  dst[3] = o[3];
+}
+
+// ---------------------------------------------------------------- arena
+// [9 MemBlock state slices | scratch for calls of up to t_max latent frames].  The state slices come first, at offsets that
+// depend on (h, w) only, so a stream can move to a larger arena by copying that prefix.
+constexpr int kStageC[3] = {256, 128, 64};
+struct Layout {
+  size_t state[9], state_bytes;
+  size_t x0, cat[3][2], tmp[3][2], fin, zeros, total;
+};
+
+static size_t al(size_t b) { return (b + 255) & ~(size_t)255; }
+
+static bool make_layout(int h, int w, int t_max, Layout* L) {
+  if (h <= 0 || w <= 0 || h > 1024 || w > 1024 || t_max < 0 || t_max > 4096) return false;
+  size_t off = 0;
+  for (int k = 0; k < 9; ++k) {
+    const int s = k / 3;
+    L->state[k] = off;
+    off += al((size_t)(h << s) * (w << s) * kStageC[s] * 2);
+  }
+  L->state_bytes = off;
+  const size_t T = (size_t)t_max;
+  L->x0 = off;
+  off += al(T * h * w * 32 * 2);
+  for (int s = 0; s < 3; ++s) {
+    const size_t sl = (size_t)(h << s) * (w << s) * kStageC[s] * 2;
+    const size_t F = s < 2 ? T : 2 * T;
+    for (int j = 0; j < 2; ++j) {
+      L->cat[s][j] = off;
+      off += al((F + 1) * sl);
+    }
+    for (int j = 0; j < 2; ++j) {
+      L->tmp[s][j] = off;
+      off += al(F * sl);
+    }
+  }
+  L->fin = off;
+  off += al((size_t)2 * (8 * h) * (8 * w) * 64 * 2);
+  L->zeros = off;
+  off += 256;
+  L->total = off;
+  return true;
+}
+
+}  // namespace tae
+}  // namespace rtv
+
+using namespace rtv;
+
+#define TAE_TRY(expr)         \
+  do {                        \
+    int st_ = (expr);         \
+    if (st_) return st_;      \
+  } while (0)
+
+extern "C" size_t rtv_taehv_arena_bytes(int h, int w, int t_max) {
+  tae::Layout L;
+  if (t_max <= 0 || !tae::make_layout(h, w, t_max, &L)) return 0;
+  return L.total;
+}
+
+extern "C" int rtv_taehv_state_slot(int h, int w, int slot, size_t* offset, int* C, int* H, int* W) {
+  tae::Layout L;
+  if (!tae::make_layout(h, w, 0, &L)) return set_error(-1, "taehv: bad latent size");
+  if (slot < 0 || slot >= 9) return set_error(-1, "taehv: state slot must be 0..8");
+  const int s = slot / 3;
+  if (offset) *offset = L.state[slot];
+  if (C) *C = tae::kStageC[s];
+  if (H) *H = h << s;
+  if (W) *W = w << s;
+  return 0;
+}
+
+extern "C" int rtv_taehv_conv(const void* in, const void* w, const void* bias, const void* residual, void* out, int T, int H,
+                              int W, int Cin, int Cout, int kt, int ups, int n_split, int relu, int head, const void* zeros,
+                              rtv_stream_t stream) {
+  tae::ConvParams p{};
+  p.in = (const uint16_t*)in;
+  p.w = (const uint16_t*)w;
+  p.bias = (const uint16_t*)bias;
+  p.residual = (const uint16_t*)residual;
+  p.out = out;
+  p.zeros = (const uint16_t*)zeros;
+  p.T = T;
+  p.H = H;
+  p.W = W;
+  p.Cin = Cin;
+  p.Cout = Cout;
+  p.kt = kt;
+  p.ups = ups;
+  p.n_split = n_split;
+  p.relu = relu ? 1 : 0;
+  return tae::launch_conv(p, head ? 1 : 0, (hipStream_t)stream);
+}
+
+extern "C" int rtv_taehv_decode(const rtv_taehv_weights* wt, const void* z, int T, int h, int w, int first, void* arena,
+                                size_t arena_bytes, void* pixels, rtv_stream_t stream_) {
+  if (!wt || !z || !arena || !pixels) return set_error(-1, "taehv_decode: null argument");
+  if (T <= 0) return set_error(-1, "taehv_decode: T must be positive");
+  if (((uintptr_t)arena) & 255) return set_error(-1, "taehv_decode: arena must be 256-byte aligned");
+  tae::Layout L;
+  if (!tae::make_layout(h, w, T, &L)) return set_error(-1, "taehv_decode: unsupported latent size or T");
+  if (arena_bytes < L.total) return set_error(-1, "taehv_decode: arena too small for T (see rtv_taehv_arena_bytes)");
+  // the largest gather input (the 64-channel MemBlock concat buffers, 2T + 1 slices) must stay within 32-bit offsets
+  if ((size_t)(2 * T + 1) * (4 * h) * (4 * w) * 64 >= 0x7fffffffull) return set_error(-1, "taehv_decode: T too large");
+  hipStream_t stream = (hipStream_t)stream_;
+  char* A = (char*)arena;
+  auto at = [&](size_t off) { return (uint16_t*)(A + off); };
+  const uint16_t* zeros = at(L.zeros);
+  if (hipMemsetAsync(A + L.zeros, 0, 256, stream) != hipSuccess) return set_error(-1, "taehv_decode: memset failed");
+  if (first && hipMemsetAsync(A, 0, L.state_bytes, stream) != hipSuccess) return set_error(-1, "taehv_decode: memset failed");
+
+  auto conv = [&](const void* in, const void* wts, const void* bias, const void* res, void* out, int Tn, int H, int W, int Cin,
+                  int Cout, int kt, int ups, int n_split, int relu, int head) {
+    tae::ConvParams p{};
+    p.in = (const uint16_t*)in;
+    p.w = (const uint16_t*)wts;
+    p.bias = (const uint16_t*)bias;
+    p.residual = (const uint16_t*)res;
+    p.out = out;
+    p.zeros = zeros;
+    p.T = Tn;
+    p.H = H;
+    p.W = W;
+    p.Cin = Cin;
+    p.Cout = Cout;
+    p.kt = kt;
+    p.ups = ups;
+    p.n_split = n_split;
+    p.relu = relu;
+    return tae::launch_conv(p, head, stream);
+  };
+
+  // decoder.0 (Clamp) + layout, decoder.1 / 2: conv 16 -> 256 + bias, ReLU -> slices 1..T of the first MemBlock's concat buffer
+  {
+    const int n = T * h * w;
+    hipLaunchKernelGGL(tae::taehv_prep_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, (const f16_t*)z, T, h * w,
+                       (f16_t*)at(L.x0));
+    TAE_TRY(check_launch("taehv_prep"));
+    const size_t sl = (size_t)h * w * 256;
+    TAE_TRY(conv(at(L.x0), wt->conv_in.w, wt->conv_in.b, nullptr, at(L.cat[0][0]) + sl, T, h, w, 32, 256, 1, 0, 0, 1, 0));
+  }
+  uint16_t* cur = nullptr;
+  int F = T;
+  for (int s = 0; s < 3; ++s) {
+    const int C = tae::kStageC[s], H = h << s, W = w << s;
+    const size_t sl = (size_t)H * W * C;
+    F = s < 2 ? T : 2 * T;
+    cur = at(L.cat[s][0]);
+    for (int b = 0; b < 3; ++b) {
+      const int k = s * 3 + b;
+      const rtv_vae_conv* mb = wt->mem[k];
+      uint16_t* nxt = at(L.cat[s][(b + 1) & 1]);
+      uint16_t* state = at(L.state[k]);
+      // [x_{t-1} | x_t] window: slice 0 = the input of the previous frame (carried across calls)
+      if (hipMemcpyAsync(cur, state, sl * 2, hipMemcpyDeviceToDevice, stream) != hipSuccess)
+        return set_error(-1, "taehv_decode: copy failed");
+      TAE_TRY(conv(cur, mb[0].w, mb[0].b, nullptr, at(L.tmp[s][0]), F, H, W, C, C, 2, 0, 0, 1, 0));
+      if (hipMemcpyAsync(state, cur + (size_t)F * sl, sl * 2, hipMemcpyDeviceToDevice, stream) != hipSuccess)
+        return set_error(-1, "taehv_decode: copy failed");
+      TAE_TRY(conv(at(L.tmp[s][0]), mb[1].w, mb[1].b, nullptr, at(L.tmp[s][1]), F, H, W, C, C, 1, 0, 0, 1, 0));
+      TAE_TRY(conv(at(L.tmp[s][1]), mb[2].w, mb[2].b, cur + sl, nxt + sl, F, H, W, C, C, 1, 0, 0, 1, 0));
+      cur = nxt;
+    }
+    if (s < 2) {   // decoder.{6,7,8} / {12,13,14}: up 2x, TGrow folded into the conv -> slices 1.. of the next stage's buffer
+      const size_t sl2 = (size_t)(2 * H) * (2 * W) * tae::kStageC[s + 1];
+      TAE_TRY(conv(cur + sl, wt->up[s], nullptr, nullptr, at(L.cat[s + 1][0]) + sl2, F, 2 * H, 2 * W, C, 128, 1, 1,
+                   s == 0 ? 0 : 64, 0, 0));
+    }
+  }
+  // decoder.{18..22}: up 2x + TGrow(64, 2) folded into conv 64 -> 64, ReLU, conv 64 -> 3, one 64-channel frame j (= output frames
+  // 2j, 2j + 1) at a time; on a stream's first call the output frames 0..2 are TAEHV's warm-up frames and are not produced
+  {
+    const int H = 8 * h, W = 8 * w;
+    const size_t sl = (size_t)(4 * h) * (4 * w) * 64, fsl = (size_t)H * W * 64;
+    const int skip = first ? 3 : 0;
+    for (int j = 0; j < F; ++j) {
+      const int lo = 2 * j > skip ? 2 * j : skip;
+      if (lo >= 2 * j + 2) continue;
+      TAE_TRY(conv(cur + (size_t)(1 + j) * sl, wt->up[2], nullptr, nullptr, at(L.fin), 1, H, W, 64, 128, 1, 1, 64, 1, 0));
+      TAE_TRY(conv(at(L.fin) + (size_t)(lo - 2 * j) * fsl, wt->head.w, wt->head.b, nullptr,
+                   (float*)pixels + (size_t)(lo - skip) * 3 * H * W, 2 * j + 2 - lo, H, W, 64, 8, 1, 0, 0, 0, 1));
+    }
+  }
+  return 0;
+}

@@ -40,9 +40,9 @@ class GenerateParams:
     timestep_shift: float = 5.0
 
 
-def Models(transformer, pipeline, text_encoder=None, vae_decoder=None, vae_encoder=None):
+def Models(transformer, pipeline, text_encoder=None, vae_decoder=None, vae_encoder=None, taehv_decoder=None):
     return types.SimpleNamespace(transformer=transformer, pipeline=pipeline, text_encoder=text_encoder,
-                                 vae_decoder=vae_decoder, vae_encoder=vae_encoder)
+                                 vae_decoder=vae_decoder, vae_encoder=vae_encoder, taehv_decoder=taehv_decoder)
 
 
 class StaticTextEncoder:
@@ -65,8 +65,14 @@ def resample_array(array, target_length):
 
 
 class GenerationSession:
-    def __init__(self, params: GenerateParams, models, frame_callback: Optional[Callable] = None, device="cuda"):
+    def __init__(self, params: GenerateParams, models, frame_callback: Optional[Callable] = None, device="cuda",
+                 use_taehv=False):
+        """use_taehv (the reference's config.use_taehv, release_server.py:350): decode blocks with models.taehv_decoder
+        (realtime_video_amd.taehv.TAEHVDecoder) instead of models.vae_decoder."""
         self.params, self.models = params, models
+        self.use_taehv = bool(use_taehv)
+        if self.use_taehv and getattr(models, "taehv_decoder", None) is None:
+            raise ValueError("use_taehv=True needs Models(..., taehv_decoder=TAEHVDecoder(...))")
         self.frame_callback = frame_callback or (lambda *a, **k: None)
         self.gpu = torch.device(device)
         self.block_idx = 0
@@ -286,8 +292,13 @@ class GenerationSession:
         self.all_latents[:, self.current_start_frame:self.current_start_frame + nfpb] = denoised_pred
         self.last_pred = denoised_pred
         pixels = None
-        if models.vae_decoder is not None:
-            pixels, self.decode_vae_cache = models.vae_decoder(denoised_pred.half(), *self.decode_vae_cache)
+        decoder = models.vae_decoder
+        if self.use_taehv:
+            decoder = getattr(models, "taehv_decoder", None)
+            if decoder is None:
+                raise ValueError("use_taehv=True needs models.taehv_decoder")
+        if decoder is not None:
+            pixels, self.decode_vae_cache = decoder(denoised_pred.half(), *self.decode_vae_cache)
             self.frame_context_cache.extend(pixels.split(1, dim=1))
             if idx == 0:
                 pixels = pixels[:, 3:]  # the first block yields 9 frames, 3 are dropped (:722-723)

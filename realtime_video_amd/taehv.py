@@ -1,0 +1,244 @@
+"""TAEHV tiny-VAE streaming decoder: the opt-in fast decode behind `use_taehv` (the reference's `config.use_taehv`,
+release_server.py:350), for the `decoder` of demo_utils/taehv.py:159-234 with the Wan 2.1 checkpoint taew2_1.pth.
+
+    pixels, state = TAEHVDecoder(device)(z[1, T, 16, h, w] fp16, *state)
+
+is the streaming contract of `VAEDecoderWrapper`: a list of `None` (the session's `[None] * 55`) starts a stream, passing
+the returned list back continues it.  pixels are float32 [1, T', 3, 8h, 8w] = clamp(2 * decoder - 1, -1, 1), T' = 4T - 3
+on a stream's first call (TAEHV's 3 warm-up frames, `frames_to_trim`, are not produced) and 4T afterwards - the frame
+count and alignment of the Wan decoder.  The returned state is the nine MemBlock state slices (each block's input at the
+previous frame of its rate) as [1, C, H, W] views into the stream's arena, updated in place by the next call.  Backed by
+`rtv_taehv_decode` (include/rtv_hip.h, csrc/taehv.hip); no CPU fallback.
+"""
+import ctypes
+import hashlib
+import math
+
+import torch
+
+from . import _lib
+from .vae_decoder import CacheArenas, _Conv, pack_conv_weight
+
+c_vp = ctypes.c_void_p
+
+MEMBLOCKS = (3, 4, 5, 9, 10, 11, 15, 16, 17)      # decoder indices of the nine MemBlocks
+MEM_CHANNELS = (256, 256, 256, 128, 128, 128, 64, 64, 64)
+TGROWS = ((7, 8, 256, 128, 1), (13, 14, 128, 64, 2), (19, 20, 64, 64, 2))   # (TGrow idx, conv idx, C in, C out, stride)
+WARMUP_FRAMES = 3                                  # TAEHV.frames_to_trim with the default decoder_time_upscale
+
+
+class _TaehvWeights(ctypes.Structure):
+    _fields_ = [("conv_in", _Conv), ("mem", (_Conv * 3) * 9), ("up", c_vp * 3), ("head", _Conv)]
+
+
+_lib.EXTRA_SIGNATURES.update({
+    "rtv_taehv_state_slot": [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_size_t)] + [ctypes.POINTER(ctypes.c_int)] * 3,
+    "rtv_taehv_decode": [ctypes.POINTER(_TaehvWeights), c_vp] + [ctypes.c_int] * 4 + [c_vp, ctypes.c_size_t, c_vp, c_vp],
+    "rtv_taehv_conv": [c_vp] * 5 + [ctypes.c_int] * 10 + [c_vp, c_vp],
+})
+
+
+def arena_bytes(h, w, t_max):
+    lib = _lib.load()
+    lib.rtv_taehv_arena_bytes.restype = ctypes.c_size_t
+    lib.rtv_taehv_arena_bytes.argtypes = [ctypes.c_int] * 3
+    return int(lib.rtv_taehv_arena_bytes(h, w, t_max))
+
+
+def fold_tgrow(tgrow_w, conv_w, stride):
+    """TGrow (1x1, C -> stride * C, no bias) followed by a bias-free 3x3 conv C -> Cout, as ONE 3x3 conv C -> stride * Cout whose
+    filter s * Cout + o is output channel o of frame stride * t + s (exact: the nearest upsampling in front commutes with the
+    1x1 conv, and TGrow maps the conv's zero padding to zeros).  Composed in float32."""
+    tg = tgrow_w.detach().float().reshape(tgrow_w.shape[0], tgrow_w.shape[1])   # [stride * C][C]
+    cw = conv_w.detach().float()                                               # [Cout][C][3][3]
+    C = tg.shape[1]
+    parts = [torch.einsum("okyx,kc->ocyx", cw, tg[s * C:(s + 1) * C]) for s in range(stride)]
+    return torch.cat(parts, 0)
+
+
+class TAEHVDecoder:
+    z_dim = 16
+
+    def __init__(self, device="cuda", decoder_time_upscale=(True, True), decoder_space_upscale=(True, True, True)):
+        if tuple(decoder_time_upscale) != (True, True) or tuple(decoder_space_upscale) != (True, True, True):
+            raise NotImplementedError("TAEHVDecoder: only the default decoder_time_upscale / decoder_space_upscale")
+        self.device = torch.device(device)
+        self._t = {}
+        self._w = None
+        self._arenas = CacheArenas()
+
+    def eval(self):
+        return self
+
+    def to(self, *a, **k):
+        return self
+
+    def half(self):
+        return self
+
+    # ------------------------------------------------------------------ weights
+    @staticmethod
+    def state_dict_spec():
+        """(name, shape) of every tensor of the reference module's `decoder` state_dict, in module order."""
+        spec = [("decoder.1.weight", (256, 16, 3, 3)), ("decoder.1.bias", (256,))]
+        for idx, C in zip(MEMBLOCKS, MEM_CHANNELS):
+            for j, cin in ((0, 2 * C), (2, C), (4, C)):
+                spec += [(f"decoder.{idx}.conv.{j}.weight", (C, cin, 3, 3)), (f"decoder.{idx}.conv.{j}.bias", (C,))]
+            if idx in (5, 11, 17):
+                tg, cv, cin, cout, stride = TGROWS[(idx - 5) // 6]
+                spec += [(f"decoder.{tg}.conv.weight", (cin * stride, cin, 1, 1)), (f"decoder.{cv}.weight", (cout, cin, 3, 3))]
+        spec += [("decoder.22.weight", (3, 64, 3, 3)), ("decoder.22.bias", (3,))]
+        return spec
+
+    @staticmethod
+    def patch_tgrow_layers(sd):
+        """taehv.py:195-208: a TGrow weight wider than the module's keeps its LAST stride * C output channels.  Returns a new dict."""
+        sd = dict(sd)
+        for tg, _cv, cin, _cout, stride in TGROWS:
+            key = f"decoder.{tg}.conv.weight"
+            if key in sd and sd[key].shape[0] > cin * stride:
+                sd[key] = sd[key][-cin * stride:]
+        return sd
+
+    def load_state_dict(self, sd, strict=True):
+        """Reference key names (`decoder.{i}...`); `encoder.*` keys (a real taew2_1.pth carries both) are ignored."""
+        spec = dict(self.state_dict_spec())
+        sd = self.patch_tgrow_layers({k: v for k, v in sd.items() if not k.startswith("encoder.")})
+        missing = [k for k in spec if k not in sd]
+        unexpected = [k for k in sd if k not in spec]
+        if strict and (missing or unexpected):
+            raise KeyError(f"TAEHVDecoder.load_state_dict: missing {missing}, unexpected {unexpected}")
+        if missing:
+            raise KeyError(f"TAEHVDecoder.load_state_dict: missing {missing}")
+        for k, shape in spec.items():
+            if tuple(sd[k].shape) != shape:
+                raise ValueError(f"TAEHVDecoder.load_state_dict: {k} has shape {tuple(sd[k].shape)}, expected {shape}")
+        dev, f16 = self.device, torch.float16
+        t = {}
+        W = _TaehvWeights()
+
+        def put(name, x):
+            t[name] = x.to(dev).contiguous()
+            return t[name].data_ptr()
+
+        def conv(dst, wname, w, b, cin_pad=None, cout_pad=None):
+            dst.w = put(wname + ".w", pack_conv_weight(w, cin_pad, cout_pad))
+            b = b.detach().to(f16).reshape(-1)
+            if cout_pad and cout_pad > b.numel():
+                b = torch.cat([b, b.new_zeros(cout_pad - b.numel())])
+            dst.b = put(wname + ".b", b)
+
+        conv(W.conv_in, "decoder.1", sd["decoder.1.weight"], sd["decoder.1.bias"], cin_pad=32)
+        for k, (idx, C) in enumerate(zip(MEMBLOCKS, MEM_CHANNELS)):
+            pre = f"decoder.{idx}.conv"
+            w0 = sd[pre + ".0.weight"]
+            # cat([x_t, x_{t-1}]) input channels -> time taps [x_{t-1} | x_t] of a 2-slice conv
+            conv(W.mem[k][0], pre + ".0", torch.stack([w0[:, C:], w0[:, :C]], dim=2), sd[pre + ".0.bias"])
+            conv(W.mem[k][1], pre + ".2", sd[pre + ".2.weight"], sd[pre + ".2.bias"])
+            conv(W.mem[k][2], pre + ".4", sd[pre + ".4.weight"], sd[pre + ".4.bias"])
+        for s, (tg, cv, _cin, _cout, stride) in enumerate(TGROWS):
+            W.up[s] = put(f"up{s}", pack_conv_weight(fold_tgrow(sd[f"decoder.{tg}.conv.weight"], sd[f"decoder.{cv}.weight"], stride)))
+        conv(W.head, "decoder.22", sd["decoder.22.weight"], sd["decoder.22.bias"], cout_pad=8)
+        self._t, self._w = t, W
+        return [], []
+
+    @classmethod
+    def random_state_dict(cls, seed=0):
+        """Deterministic synthetic decoder weights (CPU generator, float32) that keep the signal alive through the 23 layers:
+        He-scaled convs in front of a ReLU, variance-preserving transitions, each MemBlock's last conv scaled down (its
+        branch adds to the identity), small biases, and a head that maps to about 0.5 +- 0.1 (std) (inside TAEHV's [0, 1])."""
+        g = torch.Generator().manual_seed(seed)
+        sd = {}
+        for name, shape in cls.state_dict_spec():
+            if name.endswith(".bias"):
+                sd[name] = 0.5 + 0.02 * torch.randn(shape, generator=g) if name == "decoder.22.bias" else 0.02 * torch.randn(shape, generator=g)
+                continue
+            fan_in = math.prod(shape[1:])
+            gain = math.sqrt(2.0)
+            if name.endswith(".conv.4.weight"):
+                gain = 0.3
+            elif ".conv.weight" in name or name in ("decoder.8.weight", "decoder.14.weight"):
+                gain = 1.0             # TGrow and the conv behind it: no ReLU in between / after
+            elif name == "decoder.22.weight":
+                gain = 0.13
+            sd[name] = torch.randn(shape, generator=g) * (gain / math.sqrt(fan_in))
+        return sd
+
+    @staticmethod
+    def checksum(sd):
+        """sha256 over the float32 bytes of the decoder tensors in state_dict_spec order."""
+        h = hashlib.sha256()
+        for name, _ in TAEHVDecoder.state_dict_spec():
+            h.update(sd[name].detach().float().contiguous().cpu().numpy().tobytes())
+        return h.hexdigest()
+
+    def init_random_weights(self, seed=0):
+        self.load_state_dict(self.random_state_dict(seed))
+        return self
+
+    # ------------------------------------------------------------------ arena / state views
+    def _new_arena(self, h, w, t_max):
+        n = arena_bytes(h, w, t_max)
+        if n == 0:
+            raise ValueError(f"TAEHV decoder: unsupported latent size {h}x{w} / T {t_max}")
+        arena = torch.empty(n + 256, dtype=torch.uint8, device=self.device)   # the state is zeroed by a stream's first call
+        return arena, (-arena.data_ptr()) % 256
+
+    @staticmethod
+    def _slots(h, w):
+        out = []
+        off, C, H, Wd = ctypes.c_size_t(0), ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+        for i in range(9):
+            _lib.call("rtv_taehv_state_slot", h, w, i, ctypes.byref(off), ctypes.byref(C), ctypes.byref(H), ctypes.byref(Wd))
+            out.append((off.value, C.value, H.value, Wd.value))
+        return out
+
+    def _state_views(self, arena, base, h, w):
+        views = []
+        for off, C, H, Wd in self._slots(h, w):
+            start = base + off
+            v = arena[start:start + C * H * Wd * 2].view(torch.float16).view(H, Wd, C)
+            views.append(v.permute(2, 0, 1).unsqueeze(0))     # [1, C, H, W] (channels-last in memory)
+        self._arenas.register(views, arena, base, (h, w))
+        return views
+
+    # ------------------------------------------------------------------ forward
+    def forward(self, z, *state):
+        if self._w is None:
+            raise RuntimeError("TAEHV decoder: weights not loaded")
+        if not z.is_cuda:
+            raise RuntimeError("realtime_video_amd.TAEHVDecoder needs GPU tensors (no CPU fallback)")
+        B, T, C, h, w = z.shape
+        if B != 1 or C != 16:
+            raise NotImplementedError("TAEHV decoder: batch 1, 16 latent channels")
+        zz = z[0].to(torch.float16).contiguous()
+        first = len(state) == 0 or state[0] is None
+        need = arena_bytes(h, w, T)
+        if need == 0:
+            raise ValueError(f"TAEHV decoder: unsupported latent size {h}x{w} / T {T}")
+        t_max = max(T, 3)
+        if first:
+            ent = self._arenas.recycle((h, w))   # the arena of a dropped stream of this size, if any
+            if ent is None or ent[0].numel() - ent[1] < need:
+                ent = self._new_arena(h, w, t_max)
+            arena, base = ent
+            views = self._state_views(arena, base, h, w)
+        else:
+            views = list(state[:9])
+            arena, base = self._arenas.lookup(views, (h, w), lambda: self._new_arena(h, w, t_max)[0],
+                                              lambda a, b: self._state_views(a, b, h, w))
+            if arena.numel() - base < need:
+                # a longer call than this stream's arena was sized for: move the state to a larger one
+                self._arenas.forget(views)
+                arena, base = self._new_arena(h, w, t_max)
+                old, views = views, self._state_views(arena, base, h, w)
+                for dst, src in zip(views, old):
+                    dst.copy_(src)
+        n_out = 4 * T - WARMUP_FRAMES if first else 4 * T
+        pixels = torch.empty((n_out, 3, 8 * h, 8 * w), dtype=torch.float32, device=z.device)
+        _lib.call("rtv_taehv_decode", ctypes.byref(self._w), c_vp(zz.data_ptr()), T, h, w, int(first),
+                  c_vp(arena.data_ptr() + base), ctypes.c_size_t(arena.numel() - base), c_vp(pixels.data_ptr()),
+                  c_vp(torch.cuda.current_stream().cuda_stream))
+        return pixels.unsqueeze(0), views
+
+    __call__ = forward

@@ -389,6 +389,10 @@ class CacheArenas:
                 return ent[0], ent[1]
         return None
 
+    def forget(self, cache):
+        """Unregister the arena of `cache` (its owner has moved the stream to another arena)."""
+        self._by_ptr.pop(cache[0].data_ptr(), None)
+
     def lookup(self, cache, size, new_arena, make_views):
         """`cache` (a list, updated in place when it has to be rebuilt) -> (arena, base)."""
         key = cache[0].data_ptr()
