@@ -504,6 +504,35 @@ int rtv_taehv_conv(const void* in, const void* w, const void* bias, const void* 
                    int Cin, int Cout, int kt, int ups, int n_split, int relu, int head, const void* zeros,
                    rtv_stream_t stream);
 
+/* ---- TAEHV tiny-VAE streaming encoder (pixel -> latent side of `use_taehv`; csrc/taehv.hip) -------------------------
+ * The `encoder` of demo_utils/taehv.py:172-178 (checkpoint taew2_1.pth): conv 3 -> 64 + ReLU, then three stages of
+ * [TPool + stride-2 conv, three MemBlocks] at H/2, H/4, H/8 (frame rate T/2, T/4, T/4), conv 64 -> 16.  Each TPool (a
+ * bias-free 1x1 conv over `stride` frames' channels) is folded into the bias-free stride-2 conv behind it. */
+typedef struct rtv_taehv_enc_weights {
+  rtv_vae_conv conv_in;      /* encoder.0: fp16 [64][32], tap c * 9 + dy * 3 + dx (27 padded to 32), bias [64] */
+  const void* down[3];       /* encoder.{2,7,12} folded into encoder.{3,8,13}: [64][18][64] (time tap 0 = frame 2j, 1 = frame
+                                2j + 1), [64][18][64], [64][9][64]; no bias */
+  rtv_vae_conv mem[9][3];    /* MemBlocks encoder.{4,5,6,9,10,11,14,15,16}, laid out as rtv_taehv_weights.mem at C = 64 */
+  rtv_vae_conv head;         /* encoder.17: [16][9][64], bias [16] */
+} rtv_taehv_enc_weights;
+
+/* Caller-owned arena: the nine MemBlock state slices at the front, at offsets that depend on (H, W) only, then scratch
+ * for calls of up to t_max frames.  0 = unsupported size (H, W multiples of 8; t_max a multiple of 4). */
+size_t rtv_taehv_enc_arena_bytes(int H, int W, int t_max);
+/* State slice `slot` (0..8 = MemBlock encoder.{4,5,6,9,10,11,14,15,16}): fp16 channels-last [h][w][64] at arena + offset. */
+int rtv_taehv_enc_state_slot(int H, int W, int slot, size_t* offset, int* C, int* h, int* w);
+/* frames: fp16 planar [3][T_total][H][W] in [-1, 1]; this call encodes frames t0 .. t0 + tn (tn a multiple of 4) into
+ * latent frames j .. j + tn / 4 of latents fp16 [16][T_out][H/8][W/8].  first = 1 zeroes the state.  Bit-identical however
+ * a stream is split into calls. */
+int rtv_taehv_encode(const rtv_taehv_enc_weights* w, const void* frames, int T_total, int t0, int tn, int H, int W, int first,
+                     void* arena, size_t arena_bytes, void* latents, int T_out, int j, rtv_stream_t stream);
+/* One encoder layer (tests).  form 0: the first conv, in = planar frames [3][n_total][H][W], frames n0 .. n0 + T ->
+ * out [T][H][W][64] = ReLU(conv(0.5 * x + 0.5, zero padded) + bias).  form 1: stride-2 3x3 conv 64 -> 64 without bias, (H, W)
+ * the OUTPUT grid, in [T * kt][2H][2W][64]; kt = 2 reads the frame pair (2t, 2t + 1) with w [64][18][64].  form 2: the latent
+ * head 64 -> 16 + bias, in [T][H][W][64] -> out fp16 planar [16][n_total][H][W], frames n0 .. n0 + T. */
+int rtv_taehv_enc_conv(const void* in, const void* w, const void* bias, void* out, int form, int T, int H, int W, int kt,
+                       int n_total, int n0, const void* zeros, rtv_stream_t stream);
+
 /* ---- hardware-layout probes (test support; see csrc/probe.hip) --------------------------------- */
 int rtv_probe_mfma(const void* A /*[32][16] bf16*/, const void* B /*[16][32] bf16*/, void* D /*[32][32] f32*/,
                    rtv_stream_t stream);

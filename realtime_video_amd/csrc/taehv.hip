@@ -1,5 +1,6 @@
 // TAEHV tiny-VAE streaming decoder (the `decoder` nn.Sequential of demo_utils/taehv.py:159-234, checkpoint taew2_1.pth for
 // Wan 2.1): the opt-in fast decode behind `use_taehv`.  fp16 channels-last activations, fp32 accumulation on MFMA.
+// The streaming encoder (the `encoder` of the same module) follows the decoder, from "encoder" below on.
 //
 // Every layer is a 3x3 'same' convolution run as an implicit GEMM (the LDS-DMA gather idiom of vae_conv.hip's
 // conv_igemm_kernel, on its own kernel here so that the Wan decoder's code objects stay as they are):
@@ -38,6 +39,9 @@ struct ConvParams {
   int inH, inW;              // input grid (H >> ups)
   int Cin, Cout, kt, ups, n_split, relu;
   int M, tiles_m, tiles_n;
+  // encoder forms: DOWN kernels read input (2y + dy - 1, 2x + dx - 1) of slice t * tstride + dt; the latent head (HEAD == 2)
+  // writes f16 planar [16][out_T][H][W] from frame out_j on
+  int tstride, out_T, out_j;
 };
 
 template <int TN>
@@ -46,7 +50,7 @@ __device__ __forceinline__ int img_off(int row, int chunk, int half) {   // conv
   return row * 128 + ((chunk ^ (row & 7)) << 4) + ((half ^ ((row >> 3) & 1)) << 3);
 }
 
-template <int BM, int BN, int BK, int WM, int WN, bool HEAD>
+template <int BM, int BN, int BK, int WM, int WN, int HEAD, bool DOWN>
 __global__ __launch_bounds__(WM* WN * 64) void taehv_conv_kernel(ConvParams p) {
   typedef TileCfg<BM, BN, BK, WM, WN> Cfg;
   constexpr int STAGES = 3;
@@ -74,14 +78,25 @@ __global__ __launch_bounds__(WM* WN * 64) void taehv_conv_kernel(ConvParams p) {
     const int rem = m - pt * HW;
     const int py = rem / p.W, px = rem - py * p.W;
     int f = 0;
+    if constexpr (DOWN) {
+      // stride 2: the 3 x 3 neighbourhood is centred on input (2 py, 2 px); in-image bits are taken on the input grid
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      if (py + k - 1 >= 0 && py + k - 1 < p.H) f |= 1 << k;
-      if (px + k - 1 >= 0 && px + k - 1 < p.W) f |= 8 << k;
+      for (int k = 0; k < 3; ++k) {
+        if (2 * py + k - 1 >= 0 && 2 * py + k - 1 < p.inH) f |= 1 << k;
+        if (2 * px + k - 1 >= 0 && 2 * px + k - 1 < p.inW) f |= 8 << k;
+      }
+      flags[i] = f;
+      base_off[i] = ((pt * p.tstride * p.inH + 2 * py) * p.inW + 2 * px) * p.Cin + Cfg::swz(row, cpos) * 8;
+    } else {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        if (py + k - 1 >= 0 && py + k - 1 < p.H) f |= 1 << k;
+        if (px + k - 1 >= 0 && px + k - 1 < p.W) f |= 8 << k;
+      }
+      if (p.ups) f |= ((py & 1) << 6) | ((px & 1) << 7);
+      flags[i] = f;
+      base_off[i] = ((pt * p.inH + (py >> p.ups)) * p.inW + (px >> p.ups)) * p.Cin + Cfg::swz(row, cpos) * 8;
     }
-    if (p.ups) f |= ((py & 1) << 6) | ((px & 1) << 7);
-    flags[i] = f;
-    base_off[i] = ((pt * p.inH + (py >> p.ups)) * p.inW + (px >> p.ups)) * p.Cin + Cfg::swz(row, cpos) * 8;
   }
   uint32_t b_off[Cfg::B_INST];
   const int Ktot = p.kt * 9 * p.Cin;
@@ -167,7 +182,27 @@ __global__ __launch_bounds__(WM* WN * 64) void taehv_conv_kernel(ConvParams p) {
 #undef TV_FENCE
 
   const int l31 = lane & 31, g = lane >> 5;
-  if constexpr (HEAD) {
+  if constexpr (HEAD == 2) {
+    // latent head: filters 0..15 sit in quads rq = 0, 1 of both half-waves (filter rq * 8 + g * 4 + i); f16 planar stores, 32
+    // consecutive pixels per channel and instruction
+    if (n0 + b_row0 != 0) return;
+    uint16_t* out = (uint16_t*)p.out;
+#pragma unroll
+    for (int mi = 0; mi < Cfg::TM; ++mi) {
+      const int m = m0 + a_row0 + mi * 32 + l31;
+      if (m >= p.M) continue;
+      const int t = m / HW, pix = m - t * HW;
+#pragma unroll
+      for (int rq = 0; rq < 2; ++rq)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int n = rq * 8 + g * 4 + i;
+          const float v = acc[mi][0][rq * 4 + i] + (p.bias ? f16_to_f32(p.bias[n]) : 0.f);
+          out[((size_t)n * p.out_T + p.out_j + t) * HW + pix] = f32_to_f16(v);
+        }
+    }
+    return;
+  } else if constexpr (HEAD == 1) {
     // filters 0..2 of the (one) 32-filter block sit in quad rq = 0 of the lanes with g = 0: float32 planar stores, 32
     // consecutive pixels per channel and instruction
     if (g != 0 || n0 + b_row0 != 0) return;
@@ -263,7 +298,7 @@ __global__ __launch_bounds__(WM* WN * 64) void taehv_conv_kernel(ConvParams p) {
   }
 }
 
-template <int BM, int BN, int BK, int WM, int WN, bool HEAD>
+template <int BM, int BN, int BK, int WM, int WN, int HEAD, bool DOWN = false>
 static int launch_cfg(ConvParams p, hipStream_t stream) {
   typedef TileCfg<BM, BN, BK, WM, WN> Cfg;
   static_assert(HEAD || Cfg::NW * Cfg::TM * 32 * Cfg::TN * 64 <= 3 * Cfg::STAGE_BYTES, "epilogue image must fit the stage buffers");
@@ -272,7 +307,7 @@ static int launch_cfg(ConvParams p, hipStream_t stream) {
   p.tiles_m = (p.M + BM - 1) / BM;
   p.tiles_n = (p.Cout + BN - 1) / BN;
   const int lds = 3 * Cfg::STAGE_BYTES;
-  auto kern = taehv_conv_kernel<BM, BN, BK, WM, WN, HEAD>;
+  auto kern = taehv_conv_kernel<BM, BN, BK, WM, WN, HEAD, DOWN>;
   static LdsAttr lds_attr;
   if (int st = ensure_dynamic_lds((const void*)kern, lds, &lds_attr, "taehv_conv")) return st;
   ProfScope prof(PROF_CONV, stream, 2.0 * p.M * (double)p.Cout * p.kt * 9 * p.Cin);
@@ -298,13 +333,14 @@ static int launch_conv(ConvParams p, int head, hipStream_t stream) {
     return set_error(-1, "taehv_conv: pointers must be 16-byte aligned (bias 8)");
   p.inH = p.H >> p.ups;
   p.inW = p.W >> p.ups;
+  p.tstride = 1;
   // the gather indexes the input with 32-bit element offsets
   if ((size_t)(p.T + p.kt - 1) * p.inH * p.inW * p.Cin >= 0x7fffffffull || (size_t)p.T * p.H * p.W >= 0x7fffffffull)
     return set_error(-1, "taehv_conv: input too large for 32-bit offsets");
   p.M = p.T * p.H * p.W;
-  if (head) return launch_cfg<128, 32, 32, 2, 1, true>(p, stream);
-  if (p.Cout == 64) return launch_cfg<256, 64, 32, 4, 1, false>(p, stream);
-  return launch_cfg<128, 128, 32, 2, 2, false>(p, stream);
+  if (head) return launch_cfg<128, 32, 32, 2, 1, 1>(p, stream);
+  if (p.Cout == 64) return launch_cfg<256, 64, 32, 4, 1, 0>(p, stream);
+  return launch_cfg<128, 128, 32, 2, 2, 0>(p, stream);
 }
 
 // z fp16 [T][16][h][w] -> Clamp (tanh(x / 3) * 3) -> channels-last [T][h][w][32] (16 real + 16 zero channels)
@@ -364,6 +400,181 @@ static bool make_layout(int h, int w, int t_max, Layout* L) {
   }
   L->fin = off;
   off += al((size_t)2 * (8 * h) * (8 * w) * 64 * 2);
+  L->zeros = off;
+  off += 256;
+  L->total = off;
+  return true;
+}
+
+
+// ================================================================ encoder (the `encoder` of demo_utils/taehv.py:172-178)
+// conv 3 -> 64 + ReLU at full resolution; TPool(64, 2) folded into the stride-2 conv behind it (both linear and bias-free,
+// TPool(0) = 0 keeps the conv's zero padding: one stride-2 conv with two time taps over the frame pair 2j, 2j + 1); three
+// MemBlocks at H/2 and half the frame rate; the same again to H/4 and a quarter of the frame rate; TPool(64, 1) folded into
+// a plain stride-2 conv to H/8; three MemBlocks; conv 64 -> 16 + bias written as planar f16 latents.  The MemBlock convs are
+// the decoder's Cout = 64 forms above.  A call holds a multiple of 4 frames, so no TPool pair straddles two calls and the
+// carried state is the nine MemBlock inputs of the previous frame only.
+
+// One stride-2 layer or the latent head.  The kernel configuration is a function of the layer only.
+static int launch_enc_conv(ConvParams p, int head, hipStream_t stream) {
+  if (!p.in || !p.w || !p.out || !p.zeros) return set_error(-1, "taehv_enc_conv: null pointer");
+  if (p.T <= 0) return 0;
+  if (p.H <= 0 || p.W <= 0) return set_error(-1, "taehv_enc_conv: bad size");
+  if (p.kt != 1 && p.kt != 2) return set_error(-1, "taehv_enc_conv: kt must be 1 or 2");
+  if (p.Cin != 64) return set_error(-1, "taehv_enc_conv: Cin must be 64");
+  if (p.Cout != (head ? 16 : 64)) return set_error(-1, "taehv_enc_conv: Cout must be 64 (stride 2) or 16 (head)");
+  if (head && (p.kt != 1 || p.out_j < 0 || p.out_T <= 0 || p.out_j + p.T > p.out_T))
+    return set_error(-1, "taehv_enc_conv: head frames outside the output tensor");
+  if ((((uintptr_t)p.in | (uintptr_t)p.w | (uintptr_t)p.zeros) & 15) || ((uintptr_t)p.out & (head ? 1 : 15)) ||
+      ((uintptr_t)p.bias & 7))
+    return set_error(-1, "taehv_enc_conv: pointers must be 16-byte aligned (bias 8)");
+  p.ups = 0;
+  p.n_split = 0;
+  p.relu = 0;
+  p.residual = nullptr;
+  p.inH = head ? p.H : 2 * p.H;
+  p.inW = head ? p.W : 2 * p.W;
+  p.tstride = head ? 1 : p.kt;   // the folded TPool(64, 2) reads the frame pair (2t, 2t + 1): windows do not overlap
+  // the gather indexes the input with 32-bit element offsets
+  if ((size_t)p.T * p.kt * p.inH * p.inW * p.Cin >= 0x7fffffffull || (size_t)p.T * p.H * p.W >= 0x7fffffffull)
+    return set_error(-1, "taehv_enc_conv: input too large for 32-bit offsets");
+  p.M = p.T * p.H * p.W;
+  if (head) return launch_cfg<128, 32, 32, 2, 1, 2>(p, stream);
+  return launch_cfg<256, 64, 32, 4, 1, 0, true>(p, stream);
+}
+
+struct FirstParams {
+  const uint16_t* frames;   // f16 planar [3][T_total][H][W] in [-1, 1]
+  const uint16_t* w;        // [64][32]: tap c * 9 + dy * 3 + dx, taps 27..31 zero
+  const uint16_t* bias;     // [64]
+  uint16_t* out;            // f16 channels-last [T][H][W][64]
+  int T_total, t0, T, H, W, M;
+};
+
+// Encoder layer 0: conv 3 -> 64 + bias, ReLU on TAEHV's [0, 1] pixels (0.5 * x + 0.5 of the wrapper's [-1, 1] frames, applied
+// to in-image taps only so that the zero padding stays zero in [0, 1] space).  One wave = 32 pixels x 64 filters: each lane
+// gathers 16 of its pixel's 27 (padded to 32) taps straight from the planar frames (2-byte loads, consecutive lanes =
+// consecutive pixels), four 32x32x16 f16 MFMAs against the register-resident [64][32] weight, then bias + ReLU and a
+// half-wave exchange (v_permlane32_swap) so that every lane stores 16 contiguous bytes: 4 global_store_dwordx4 per lane,
+// the 128 contiguous bytes of a pixel written by its two lanes.
+// Bound by its output: 128 B written per pixel (51 MB per 480 x 832 frame) against 6 B read and 4 MFMAs per 32 pixels.
+__global__ __launch_bounds__(256) void taehv_enc_first_kernel(FirstParams p) {
+  const int lane = threadIdx.x & 63, l31 = lane & 31, g = lane >> 5;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int m = (blockIdx.x * 4 + wave) * 32 + l31;
+  const int mc = min(m, p.M - 1);   // clamped pixels compute in bounds and are not stored
+  const int HW = p.H * p.W;
+  const int t = mc / HW, rem = mc - t * HW;
+  const int y = rem / p.W, x = rem - y * p.W;
+  int f = 0;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    if (y + k - 1 >= 0 && y + k - 1 < p.H) f |= 1 << k;
+    if (x + k - 1 >= 0 && x + k - 1 < p.W) f |= 8 << k;
+  }
+  const uint16_t* src = p.frames + (size_t)(p.t0 + t) * HW + rem;
+  const int plane = p.T_total * HW;
+  // MFMA K slot ks * 16 + g * 8 + i = tap index; the two half-waves hold different taps of the same pixel
+  u32x4 bfrag[2];
+#pragma unroll
+  for (int ks = 0; ks < 2; ++ks) {
+    float v[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int k0 = ks * 16 + i, k1 = k0 + 8;
+      const int off0 = k0 < 27 ? (k0 / 9) * plane + ((k0 % 9) / 3 - 1) * p.W + (k0 % 3 - 1) : 0;
+      const int off1 = k1 < 27 ? (k1 / 9) * plane + ((k1 % 9) / 3 - 1) * p.W + (k1 % 3 - 1) : 0;
+      const int mask0 = k0 < 27 ? (1 << ((k0 % 9) / 3)) | (8 << (k0 % 3)) : 64;   // bit 6 is never set: a padding tap
+      const int mask1 = k1 < 27 ? (1 << ((k1 % 9) / 3)) | (8 << (k1 % 3)) : 64;
+      const int mask = g ? mask1 : mask0;
+      const bool ok = (f & mask) == mask;
+      const int off = ok ? (g ? off1 : off0) : 0;
+      const float px = f16_to_f32(src[off]);
+      v[i] = ok ? 0.5f * px + 0.5f : 0.f;
+    }
+    bfrag[ks] = u32x4{pack_f16x2(v[0], v[1]), pack_f16x2(v[2], v[3]), pack_f16x2(v[4], v[5]), pack_f16x2(v[6], v[7])};
+  }
+  f32x16 acc[2];
+#pragma unroll
+  for (int nb = 0; nb < 2; ++nb) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[nb][r] = 0.f;
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      const u32x4 wf = *(const u32x4*)(p.w + (nb * 32 + l31) * 32 + ks * 16 + g * 8);
+      acc[nb] = Mfma32<true>::run(wf, bfrag[ks], acc[nb]);
+    }
+  }
+  // acc[nb][rq * 4 + i] = filter nb * 32 + rq * 8 + g * 4 + i of pixel l31
+  uint16_t* dst = p.out + (size_t)mc * 64 + g * 8;
+#pragma unroll
+  for (int nb = 0; nb < 2; ++nb)
+#pragma unroll
+    for (int rq = 0; rq < 4; rq += 2) {
+      u32x2 o[2];
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        const u32x2 bb = *(const u32x2*)(p.bias + nb * 32 + (rq + q) * 8 + g * 4);
+        float b0, b1, b2, b3;
+        unpack_f16x2(bb[0], b0, b1);
+        unpack_f16x2(bb[1], b2, b3);
+        const int r = (rq + q) * 4;
+        o[q][0] = pack_f16x2(fmaxf(acc[nb][r + 0] + b0, 0.f), fmaxf(acc[nb][r + 1] + b1, 0.f));
+        o[q][1] = pack_f16x2(fmaxf(acc[nb][r + 2] + b2, 0.f), fmaxf(acc[nb][r + 3] + b3, 0.f));
+      }
+      // lanes 32-63 of quad rq <-> lanes 0-31 of quad rq + 1: the low half-wave ends up with filters 8 rq' .. 8 rq' + 7 of its
+      // pixel (rq' = rq), the high one with the next eight
+      const auto s0 = __builtin_amdgcn_permlane32_swap(o[0][0], o[1][0], false, false);
+      const auto s1 = __builtin_amdgcn_permlane32_swap(o[0][1], o[1][1], false, false);
+      if (m < p.M) *(u32x4*)(dst + nb * 32 + (rq >> 1) * 16) = u32x4{s0[0], s1[0], s0[1], s1[1]};
+    }
+}
+
+static int launch_enc_first(FirstParams p, hipStream_t stream) {
+  if (!p.frames || !p.w || !p.bias || !p.out) return set_error(-1, "taehv_enc_first: null pointer");
+  if (p.T <= 0) return 0;
+  if (p.H <= 0 || p.W <= 0 || p.t0 < 0 || p.t0 + p.T > p.T_total) return set_error(-1, "taehv_enc_first: bad size / frame range");
+  if ((((uintptr_t)p.w | (uintptr_t)p.out) & 15) || ((uintptr_t)p.bias & 7) || ((uintptr_t)p.frames & 1))
+    return set_error(-1, "taehv_enc_first: weights / output must be 16-byte aligned (bias 8)");
+  if ((size_t)3 * p.T_total * p.H * p.W >= 0x7fffffffull || (size_t)p.T * p.H * p.W >= 0x7fffffffull / 64)
+    return set_error(-1, "taehv_enc_first: input too large for 32-bit offsets");
+  p.M = p.T * p.H * p.W;
+  ProfScope prof(PROF_CONV, stream, 2.0 * p.M * 64.0 * 27);
+  hipLaunchKernelGGL(taehv_enc_first_kernel, dim3((p.M + 127) / 128), dim3(256), 0, stream, p);
+  return check_launch("taehv_enc_first");
+}
+
+// [9 MemBlock state slices | two full-resolution 64-channel frames | per-stage concat / scratch buffers for calls of up to
+// t_max frames].  Layer 0 and the first folded down-conv run one frame pair at a time, so the full-resolution activations
+// never take more than two frames.
+struct EncLayout {
+  size_t state[9], state_bytes;
+  size_t full, cat[3][2], tmp[3][2], zeros, total;
+};
+
+static bool make_enc_layout(int H, int W, int t_max, EncLayout* L) {
+  if (H <= 0 || W <= 0 || H > 8192 || W > 8192 || (H & 7) || (W & 7) || t_max < 0 || t_max > 4096 || (t_max & 3)) return false;
+  size_t off = 0;
+  for (int k = 0; k < 9; ++k) {
+    const int s = k / 3;
+    L->state[k] = off;
+    off += al((size_t)(H >> (s + 1)) * (W >> (s + 1)) * 64 * 2);
+  }
+  L->state_bytes = off;
+  L->full = off;
+  off += al((size_t)2 * H * W * 64 * 2);
+  for (int s = 0; s < 3; ++s) {
+    const size_t sl = (size_t)(H >> (s + 1)) * (W >> (s + 1)) * 64 * 2;
+    const size_t F = s == 0 ? t_max / 2 : t_max / 4;
+    for (int j = 0; j < 2; ++j) {
+      L->cat[s][j] = off;
+      off += al((F + 1) * sl);
+    }
+    for (int j = 0; j < 2; ++j) {
+      L->tmp[s][j] = off;
+      off += al(F * sl);
+    }
+  }
   L->zeros = off;
   off += 256;
   L->total = off;
@@ -509,6 +720,175 @@ extern "C" int rtv_taehv_decode(const rtv_taehv_weights* wt, const void* z, int 
       TAE_TRY(conv(at(L.fin) + (size_t)(lo - 2 * j) * fsl, wt->head.w, wt->head.b, nullptr,
                    (float*)pixels + (size_t)(lo - skip) * 3 * H * W, 2 * j + 2 - lo, H, W, 64, 8, 1, 0, 0, 0, 1));
     }
+  }
+  return 0;
+}
+
+// ---------------------------------------------------------------- encoder C ABI
+extern "C" size_t rtv_taehv_enc_arena_bytes(int H, int W, int t_max) {
+  tae::EncLayout L;
+  if (t_max <= 0 || !tae::make_enc_layout(H, W, t_max, &L)) return 0;
+  return L.total;
+}
+
+extern "C" int rtv_taehv_enc_state_slot(int H, int W, int slot, size_t* offset, int* C, int* h, int* w) {
+  tae::EncLayout L;
+  if (!tae::make_enc_layout(H, W, 0, &L)) return set_error(-1, "taehv_enc: frame size must be positive multiples of 8");
+  if (slot < 0 || slot >= 9) return set_error(-1, "taehv_enc: state slot must be 0..8");
+  const int s = slot / 3;
+  if (offset) *offset = L.state[slot];
+  if (C) *C = 64;
+  if (h) *h = H >> (s + 1);
+  if (w) *w = W >> (s + 1);
+  return 0;
+}
+
+extern "C" int rtv_taehv_enc_conv(const void* in, const void* w, const void* bias, void* out, int form, int T, int H, int W,
+                                  int kt, int n_total, int n0, const void* zeros, rtv_stream_t stream) {
+  if (form == 0) {
+    tae::FirstParams f{};
+    f.frames = (const uint16_t*)in;
+    f.w = (const uint16_t*)w;
+    f.bias = (const uint16_t*)bias;
+    f.out = (uint16_t*)out;
+    f.T_total = n_total;
+    f.t0 = n0;
+    f.T = T;
+    f.H = H;
+    f.W = W;
+    return tae::launch_enc_first(f, (hipStream_t)stream);
+  }
+  if (form != 1 && form != 2) return set_error(-1, "taehv_enc_conv: form must be 0 (first), 1 (stride 2) or 2 (head)");
+  tae::ConvParams p{};
+  p.in = (const uint16_t*)in;
+  p.w = (const uint16_t*)w;
+  p.bias = (const uint16_t*)bias;
+  p.out = out;
+  p.zeros = (const uint16_t*)zeros;
+  p.T = T;
+  p.H = H;
+  p.W = W;
+  p.Cin = 64;
+  p.Cout = form == 2 ? 16 : 64;
+  p.kt = kt;
+  p.out_T = n_total;
+  p.out_j = n0;
+  return tae::launch_enc_conv(p, form == 2, (hipStream_t)stream);
+}
+
+extern "C" int rtv_taehv_encode(const rtv_taehv_enc_weights* wt, const void* frames, int T_total, int t0, int tn, int H, int W,
+                                int first, void* arena, size_t arena_bytes, void* latents, int T_out, int j,
+                                rtv_stream_t stream_) {
+  if (!wt || !frames || !arena || !latents) return set_error(-1, "taehv_encode: null argument");
+  if (tn <= 0 || (tn & 3)) return set_error(-1, "taehv_encode: tn must be a positive multiple of 4");
+  if (t0 < 0 || t0 + tn > T_total) return set_error(-1, "taehv_encode: frames t0 .. t0 + tn outside the clip");
+  if (j < 0 || j + tn / 4 > T_out) return set_error(-1, "taehv_encode: latent frames outside the output tensor");
+  if (((uintptr_t)arena) & 255) return set_error(-1, "taehv_encode: arena must be 256-byte aligned");
+  tae::EncLayout L;
+  if (!tae::make_enc_layout(H, W, tn, &L)) return set_error(-1, "taehv_encode: H and W must be multiples of 8 (or tn too large)");
+  if (arena_bytes < L.total) return set_error(-1, "taehv_encode: arena too small for tn (see rtv_taehv_enc_arena_bytes)");
+  hipStream_t stream = (hipStream_t)stream_;
+  char* A = (char*)arena;
+  auto at = [&](size_t off) { return (uint16_t*)(A + off); };
+  const uint16_t* zeros = at(L.zeros);
+  if (hipMemsetAsync(A + L.zeros, 0, 256, stream) != hipSuccess) return set_error(-1, "taehv_encode: memset failed");
+  if (first && hipMemsetAsync(A, 0, L.state_bytes, stream) != hipSuccess) return set_error(-1, "taehv_encode: memset failed");
+
+  auto conv = [&](const void* in, const rtv_vae_conv& c, const void* res, void* out, int Tn, int Hh, int Ww, int kt) {
+    tae::ConvParams p{};
+    p.in = (const uint16_t*)in;
+    p.w = (const uint16_t*)c.w;
+    p.bias = (const uint16_t*)c.b;
+    p.residual = (const uint16_t*)res;
+    p.out = out;
+    p.zeros = zeros;
+    p.T = Tn;
+    p.H = Hh;
+    p.W = Ww;
+    p.Cin = 64;
+    p.Cout = 64;
+    p.kt = kt;
+    p.relu = 1;
+    return tae::launch_conv(p, 0, stream);
+  };
+  auto down = [&](const void* in, const void* wts, void* out, int Tn, int Hh, int Ww, int kt) {
+    tae::ConvParams p{};
+    p.in = (const uint16_t*)in;
+    p.w = (const uint16_t*)wts;
+    p.out = out;
+    p.zeros = zeros;
+    p.T = Tn;
+    p.H = Hh;
+    p.W = Ww;
+    p.Cin = 64;
+    p.Cout = 64;
+    p.kt = kt;
+    return tae::launch_enc_conv(p, 0, stream);
+  };
+
+  // encoder.{0..3}: conv 3 -> 64 + ReLU on a frame pair, then TPool(64, 2) + stride-2 conv as one layer -> slice 1 + q of the
+  // first MemBlock's concat buffer at H/2
+  {
+    const size_t sl = (size_t)(H / 2) * (W / 2) * 64;
+    for (int q = 0; q < tn / 2; ++q) {
+      tae::FirstParams f{};
+      f.frames = (const uint16_t*)frames;
+      f.w = (const uint16_t*)wt->conv_in.w;
+      f.bias = (const uint16_t*)wt->conv_in.b;
+      f.out = at(L.full);
+      f.T_total = T_total;
+      f.t0 = t0 + 2 * q;
+      f.T = 2;
+      f.H = H;
+      f.W = W;
+      TAE_TRY(tae::launch_enc_first(f, stream));
+      TAE_TRY(down(at(L.full), wt->down[0], at(L.cat[0][0]) + (size_t)(1 + q) * sl, 1, H / 2, W / 2, 2));
+    }
+  }
+  uint16_t* cur = nullptr;
+  for (int s = 0; s < 3; ++s) {
+    const int Hs = H >> (s + 1), Ws = W >> (s + 1);
+    const int F = s == 0 ? tn / 2 : tn / 4;
+    const size_t sl = (size_t)Hs * Ws * 64;
+    cur = at(L.cat[s][0]);
+    for (int b = 0; b < 3; ++b) {
+      const int k = s * 3 + b;
+      const rtv_vae_conv* mb = wt->mem[k];
+      uint16_t* nxt = at(L.cat[s][(b + 1) & 1]);
+      uint16_t* state = at(L.state[k]);
+      // [x_{t-1} | x_t] window: slice 0 = the block's input at the previous frame (carried across calls)
+      if (hipMemcpyAsync(cur, state, sl * 2, hipMemcpyDeviceToDevice, stream) != hipSuccess)
+        return set_error(-1, "taehv_encode: copy failed");
+      TAE_TRY(conv(cur, mb[0], nullptr, at(L.tmp[s][0]), F, Hs, Ws, 2));
+      if (hipMemcpyAsync(state, cur + (size_t)F * sl, sl * 2, hipMemcpyDeviceToDevice, stream) != hipSuccess)
+        return set_error(-1, "taehv_encode: copy failed");
+      TAE_TRY(conv(at(L.tmp[s][0]), mb[1], nullptr, at(L.tmp[s][1]), F, Hs, Ws, 1));
+      TAE_TRY(conv(at(L.tmp[s][1]), mb[2], cur + sl, nxt + sl, F, Hs, Ws, 1));
+      cur = nxt;
+    }
+    if (s < 2) {   // encoder.{7,8}: TPool(64, 2) + stride-2 conv; encoder.{12,13}: TPool(64, 1) + stride-2 conv
+      const size_t sl2 = (size_t)(Hs / 2) * (Ws / 2) * 64;
+      TAE_TRY(down(cur + sl, wt->down[s + 1], at(L.cat[s + 1][0]) + sl2, tn / 4, Hs / 2, Ws / 2, s == 0 ? 2 : 1));
+    }
+  }
+  // encoder.17: conv 64 -> 16 + bias -> latent frames j .. j + tn / 4 of the planar output
+  {
+    const size_t sl = (size_t)(H / 8) * (W / 8) * 64;
+    tae::ConvParams p{};
+    p.in = cur + sl;
+    p.w = (const uint16_t*)wt->head.w;
+    p.bias = (const uint16_t*)wt->head.b;
+    p.out = latents;
+    p.zeros = zeros;
+    p.T = tn / 4;
+    p.H = H / 8;
+    p.W = W / 8;
+    p.Cin = 64;
+    p.Cout = 16;
+    p.kt = 1;
+    p.out_T = T_out;
+    p.out_j = j;
+    TAE_TRY(tae::launch_enc_conv(p, 1, stream));
   }
   return 0;
 }

@@ -40,9 +40,10 @@ class GenerateParams:
     timestep_shift: float = 5.0
 
 
-def Models(transformer, pipeline, text_encoder=None, vae_decoder=None, vae_encoder=None, taehv_decoder=None):
+def Models(transformer, pipeline, text_encoder=None, vae_decoder=None, vae_encoder=None, taehv_decoder=None, taehv_encoder=None):
     return types.SimpleNamespace(transformer=transformer, pipeline=pipeline, text_encoder=text_encoder,
-                                 vae_decoder=vae_decoder, vae_encoder=vae_encoder, taehv_decoder=taehv_decoder)
+                                 vae_decoder=vae_decoder, vae_encoder=vae_encoder, taehv_decoder=taehv_decoder,
+                                 taehv_encoder=taehv_encoder)
 
 
 class StaticTextEncoder:
@@ -68,7 +69,8 @@ class GenerationSession:
     def __init__(self, params: GenerateParams, models, frame_callback: Optional[Callable] = None, device="cuda",
                  use_taehv=False):
         """use_taehv (the reference's config.use_taehv, release_server.py:350): decode blocks with models.taehv_decoder
-        (realtime_video_amd.taehv.TAEHVDecoder) instead of models.vae_decoder."""
+        (realtime_video_amd.taehv.TAEHVDecoder) instead of models.vae_decoder and, when models.taehv_encoder
+        (realtime_video_amd.taehv.TAEHVEncoder) is present, encode every pixel input with it instead of models.vae_encoder."""
         self.params, self.models = params, models
         self.use_taehv = bool(use_taehv)
         if self.use_taehv and getattr(models, "taehv_decoder", None) is None:
@@ -103,14 +105,20 @@ class GenerationSession:
         if params.start_frame is not None:            # release_server.py:429-431
             self.setup_start_frame(params.start_frame, models)
 
+    def _encoder(self, models):
+        """The pixel -> latent codec of this session: models.taehv_encoder under use_taehv when there is one, else
+        models.vae_encoder (None when the session has neither)."""
+        taehv = getattr(models, "taehv_encoder", None) if self.use_taehv else None
+        return taehv if taehv is not None else models.vae_encoder
+
     # release_server.py:417-428 (+ :529-540 encode_v2v)
     def setup_input_video(self, frames, models):
         """Offline video-to-video: the video's latents, noised to the first step's level with the session generator, replace
         the noise; the block count follows the video (latent frames / 3 - 1, capped by params.num_blocks)."""
-        if models.vae_encoder is None:
+        if self._encoder(models) is None:
             raise RuntimeError("input_frames needs a VAE encoder")
         s0 = self.denoising_step_list[0] / 1000
-        latents, _ = encode_video_latent(models.vae_encoder, [None] * 55, frames=frames.to(self.gpu), height=self.params.height,
+        latents, _ = encode_video_latent(self._encoder(models), [None] * 55, frames=frames.to(self.gpu), height=self.params.height,
                                          width=self.params.width, stream=False, max_frames=None, resample_to=None)
         latents = latents[None].to(self.gpu, dtype=self.noise.dtype).movedim(1, 2)
         self.noise = (latents * (1.0 - s0) + self._randn(latents.shape) * s0).contiguous()
@@ -121,7 +129,7 @@ class GenerationSession:
         """Image-to-video start: the image, repeated over the whole pixel context window (1 + (c-1)*4 frames), is encoded
         and becomes `resume_latents` - block 0 then recomputes the KV cache from it and generation continues behind it.
         `image`: PIL image, or the [3, H, W] tensor in [0, 1] torchvision's to_tensor would make of it."""
-        if models.vae_encoder is None:
+        if self._encoder(models) is None:
             raise RuntimeError("start_frame needs a VAE encoder")
         if not torch.is_tensor(image):
             import numpy as np
@@ -130,7 +138,7 @@ class GenerationSession:
         frame_cache_len = 1 + (self.params.kv_cache_num_frames - 1) * 4
         tensor = image.to(dtype=torch.float16).to(self.gpu).sub_(0.5).mul_(2.0)
         tensors = torch.stack([tensor] * frame_cache_len)
-        latents = encode_video_latent(models.vae_encoder, [None] * 55, resample_to=16, max_frames=81, video_path_or_url=None,
+        latents = encode_video_latent(self._encoder(models), [None] * 55, resample_to=16, max_frames=81, video_path_or_url=None,
                                       frames=tensors, height=self.height, width=self.width, stream=False)[0]
         self.resume_latents = latents.transpose(0, 1)[None]
 
@@ -186,7 +194,7 @@ class GenerationSession:
         frame_list = list(self.frame_queue)
         self.frame_queue.clear()
         frames = torch.stack(resample_array(frame_list, n)).to(self.gpu)
-        latents, self.encode_vae_cache = encode_video_latent(models.vae_encoder, self.encode_vae_cache, frames=frames,
+        latents, self.encode_vae_cache = encode_video_latent(self._encoder(models), self.encode_vae_cache, frames=frames,
                                                              height=self.params.height, width=self.params.width,
                                                              stream=idx > 0)
         return latents
@@ -204,11 +212,11 @@ class GenerationSession:
                 return ctx[:, :1]
             return torch.cat((ctx[:, :1], ctx[:, 1:][:, -c + 1:]), dim=1)
         tail = ctx[:, 1:][:, -c + 1:]
-        if models.vae_encoder is None:
+        if self._encoder(models) is None:
             raise RuntimeError("first-frame re-encode needs a VAE encoder (release_server.py:572-575); "
                                "set keep_first_frame=True to run without one")
         # re-encode the oldest pixel frame of the context window as a fresh first frame (release_server.py:574)
-        first = encode_video_latent(models.vae_encoder, [None] * 55, resample_to=16, max_frames=81, video_path_or_url=None,
+        first = encode_video_latent(self._encoder(models), [None] * 55, resample_to=16, max_frames=81, video_path_or_url=None,
                                     frames=self.frame_context_cache[0][0].half(), height=self.height, width=self.width,
                                     stream=False)[0].transpose(0, 1)[None]          # [1, 1, 16, h, w]
         return torch.cat((first, tail), dim=1).to(self.all_latents)

@@ -1,5 +1,5 @@
-"""TAEHV tiny-VAE streaming decoder: the opt-in fast decode behind `use_taehv` (the reference's `config.use_taehv`,
-release_server.py:350), for the `decoder` of demo_utils/taehv.py:159-234 with the Wan 2.1 checkpoint taew2_1.pth.
+"""TAEHV tiny-VAE streaming decoder and encoder: the opt-in fast codec behind `use_taehv` (the reference's `config.use_taehv`,
+release_server.py:350), for the `decoder` / `encoder` of demo_utils/taehv.py:159-234 with the Wan 2.1 checkpoint taew2_1.pth.
 
     pixels, state = TAEHVDecoder(device)(z[1, T, 16, h, w] fp16, *state)
 
@@ -9,6 +9,10 @@ on a stream's first call (TAEHV's 3 warm-up frames, `frames_to_trim`, are not pr
 count and alignment of the Wan decoder.  The returned state is the nine MemBlock state slices (each block's input at the
 previous frame of its rate) as [1, C, H, W] views into the stream's arena, updated in place by the next call.  Backed by
 `rtv_taehv_decode` (include/rtv_hip.h, csrc/taehv.hip); no CPU fallback.
+
+    latents[1, 16, T', h, w], cache = TAEHVEncoder(device)(frames[1, 3, T, H, W] in [-1, 1], feat_cache, stream=False)
+
+is the call contract of `VAEEncoderWrapper`, so `encode_video_latent(vae=TAEHVEncoder, ...)` works unchanged; see the class.
 """
 import ctypes
 import hashlib
@@ -31,10 +35,22 @@ class _TaehvWeights(ctypes.Structure):
     _fields_ = [("conv_in", _Conv), ("mem", (_Conv * 3) * 9), ("up", c_vp * 3), ("head", _Conv)]
 
 
+ENC_MEMBLOCKS = (4, 5, 6, 9, 10, 11, 14, 15, 16)  # encoder indices of the nine MemBlocks (64 channels each)
+TPOOLS = ((2, 3, 2), (7, 8, 2), (12, 13, 1))      # (TPool idx, stride-2 conv idx, time stride)
+
+
+class _TaehvEncWeights(ctypes.Structure):
+    _fields_ = [("conv_in", _Conv), ("down", c_vp * 3), ("mem", (_Conv * 3) * 9), ("head", _Conv)]
+
+
 _lib.EXTRA_SIGNATURES.update({
     "rtv_taehv_state_slot": [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_size_t)] + [ctypes.POINTER(ctypes.c_int)] * 3,
     "rtv_taehv_decode": [ctypes.POINTER(_TaehvWeights), c_vp] + [ctypes.c_int] * 4 + [c_vp, ctypes.c_size_t, c_vp, c_vp],
     "rtv_taehv_conv": [c_vp] * 5 + [ctypes.c_int] * 10 + [c_vp, c_vp],
+    "rtv_taehv_enc_state_slot": [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_size_t)] + [ctypes.POINTER(ctypes.c_int)] * 3,
+    "rtv_taehv_encode": [ctypes.POINTER(_TaehvEncWeights), c_vp] + [ctypes.c_int] * 6 + [c_vp, ctypes.c_size_t, c_vp,
+                                                                                      ctypes.c_int, ctypes.c_int, c_vp],
+    "rtv_taehv_enc_conv": [c_vp] * 4 + [ctypes.c_int] * 7 + [c_vp, c_vp],
 })
 
 
@@ -54,6 +70,25 @@ def fold_tgrow(tgrow_w, conv_w, stride):
     C = tg.shape[1]
     parts = [torch.einsum("okyx,kc->ocyx", cw, tg[s * C:(s + 1) * C]) for s in range(stride)]
     return torch.cat(parts, 0)
+
+
+def enc_arena_bytes(H, W, t_max):
+    lib = _lib.load()
+    lib.rtv_taehv_enc_arena_bytes.restype = ctypes.c_size_t
+    lib.rtv_taehv_enc_arena_bytes.argtypes = [ctypes.c_int] * 3
+    return int(lib.rtv_taehv_enc_arena_bytes(H, W, t_max))
+
+
+def fold_tpool(tpool_w, conv_w, stride):
+    """TPool (1x1, stride * C -> C over the channels of `stride` consecutive frames, no bias) followed by a bias-free 3x3 conv
+    C -> Cout, as ONE conv whose time tap s reads frame stride * t + s: [Cout, C, stride, 3, 3] (stride 1: [Cout, C, 3, 3]).
+    Exact: both are linear, nothing sits between them and TPool maps the conv's zero padding to zeros.  The mirror of
+    fold_tgrow.  Composed in float32."""
+    tp = tpool_w.detach().float().reshape(tpool_w.shape[0], tpool_w.shape[1])   # [C][stride * C]
+    cw = conv_w.detach().float()                                               # [Cout][C][3][3]
+    C = tp.shape[0]
+    parts = [torch.einsum("okyx,kc->ocyx", cw, tp[:, s * C:(s + 1) * C]) for s in range(stride)]
+    return parts[0] if stride == 1 else torch.stack(parts, 2)
 
 
 class TAEHVDecoder:
@@ -240,5 +275,188 @@ class TAEHVDecoder:
                   c_vp(arena.data_ptr() + base), ctypes.c_size_t(arena.numel() - base), c_vp(pixels.data_ptr()),
                   c_vp(torch.cuda.current_stream().cuda_stream))
         return pixels.unsqueeze(0), views
+
+    __call__ = forward
+
+
+class TAEHVEncoder:
+    """The `encoder` of demo_utils/taehv.py:172-178 behind the call contract of `VAEEncoderWrapper`: preview grade, not the
+    Wan encoder.  No latent mean / std scaling (taew2_1 works in the DiT's latent space, as TAEHVDecoder assumes).
+
+    Time contract (this project's convention - the reference never calls its encoder; the inverse of the decoder's dropped
+    warm-up frames): a fresh cache (None / [None] * 55) takes T = 1 + 4k frames, presents frame 0 four times (the static clip
+    whose decode is frame 0 once the decoder has dropped its 3 warm-up frames), then k groups of 4 -> 1 + k latents, the
+    Wan encoder's count; a carried cache with stream=True takes T = 4k -> k latents.  Anything else raises ValueError.
+
+    The returned cache is the nine MemBlock state slices ([1, 64, h, w] views into the stream's arena, updated in place by the
+    next call).  Backed by `rtv_taehv_encode`; no CPU fallback."""
+    z_dim = 16
+    GROUP = 12     # frames per rtv_taehv_encode call (sizes the arena: longer clips run in groups, bit-identical)
+
+    def __init__(self, device="cuda"):
+        self.device = torch.device(device)
+        self._t = {}
+        self._w = None
+        self._arenas = CacheArenas()
+
+    def eval(self):
+        return self
+
+    def to(self, *a, **k):
+        return self
+
+    def half(self):
+        return self
+
+    # ------------------------------------------------------------------ weights
+    @staticmethod
+    def state_dict_spec():
+        """(name, shape) of every tensor of the reference module's `encoder` state_dict, in module order."""
+        spec = [("encoder.0.weight", (64, 3, 3, 3)), ("encoder.0.bias", (64,))]
+        for k, idx in enumerate(ENC_MEMBLOCKS):
+            if k % 3 == 0:
+                tp, cv, stride = TPOOLS[k // 3]
+                spec += [(f"encoder.{tp}.conv.weight", (64, 64 * stride, 1, 1)), (f"encoder.{cv}.weight", (64, 64, 3, 3))]
+            for j, cin in ((0, 128), (2, 64), (4, 64)):
+                spec += [(f"encoder.{idx}.conv.{j}.weight", (64, cin, 3, 3)), (f"encoder.{idx}.conv.{j}.bias", (64,))]
+        spec += [("encoder.17.weight", (16, 64, 3, 3)), ("encoder.17.bias", (16,))]
+        return spec
+
+    def load_state_dict(self, sd, strict=True):
+        """Reference key names (`encoder.{i}...`); `decoder.*` keys (a real taew2_1.pth carries both) are ignored."""
+        spec = dict(self.state_dict_spec())
+        sd = {k: v for k, v in sd.items() if not k.startswith("decoder.")}
+        missing = [k for k in spec if k not in sd]
+        unexpected = [k for k in sd if k not in spec]
+        if strict and (missing or unexpected):
+            raise KeyError(f"TAEHVEncoder.load_state_dict: missing {missing}, unexpected {unexpected}")
+        if missing:
+            raise KeyError(f"TAEHVEncoder.load_state_dict: missing {missing}")
+        for k, shape in spec.items():
+            if tuple(sd[k].shape) != shape:
+                raise ValueError(f"TAEHVEncoder.load_state_dict: {k} has shape {tuple(sd[k].shape)}, expected {shape}")
+        dev, f16 = self.device, torch.float16
+        t = {}
+        W = _TaehvEncWeights()
+
+        def put(name, x):
+            t[name] = x.to(dev).contiguous()
+            return t[name].data_ptr()
+
+        def conv(dst, wname, w, b):
+            dst.w = put(wname + ".w", pack_conv_weight(w))
+            dst.b = put(wname + ".b", b.detach().to(f16).reshape(-1))
+
+        # first conv: K order c * 9 + dy * 3 + dx (the weight's own flattening), 27 taps padded to the MFMA's 32
+        w0 = sd["encoder.0.weight"].detach().to(f16).reshape(64, 27)
+        W.conv_in.w = put("encoder.0.w", torch.cat([w0, w0.new_zeros(64, 5)], 1))
+        W.conv_in.b = put("encoder.0.b", sd["encoder.0.bias"].detach().to(f16).reshape(-1))
+        for s, (tp, cv, stride) in enumerate(TPOOLS):
+            W.down[s] = put(f"down{s}", pack_conv_weight(fold_tpool(sd[f"encoder.{tp}.conv.weight"], sd[f"encoder.{cv}.weight"], stride)))
+        for k, idx in enumerate(ENC_MEMBLOCKS):
+            pre = f"encoder.{idx}.conv"
+            w0 = sd[pre + ".0.weight"]
+            # cat([x_t, x_{t-1}]) input channels -> time taps [x_{t-1} | x_t] of a 2-slice conv
+            conv(W.mem[k][0], pre + ".0", torch.stack([w0[:, 64:], w0[:, :64]], dim=2), sd[pre + ".0.bias"])
+            conv(W.mem[k][1], pre + ".2", sd[pre + ".2.weight"], sd[pre + ".2.bias"])
+            conv(W.mem[k][2], pre + ".4", sd[pre + ".4.weight"], sd[pre + ".4.bias"])
+        conv(W.head, "encoder.17", sd["encoder.17.weight"], sd["encoder.17.bias"])
+        self._t, self._w = t, W
+        return [], []
+
+    @classmethod
+    def random_state_dict(cls, seed=0):
+        """Deterministic synthetic encoder weights (CPU generator, float32), the recipe of TAEHVDecoder.random_state_dict:
+        He-scaled convs in front of a ReLU, variance-preserving TPool / stride-2 convs, each MemBlock's last conv scaled
+        down, small biases, a unit-gain head."""
+        g = torch.Generator().manual_seed(seed)
+        sd = {}
+        for name, shape in cls.state_dict_spec():
+            if name.endswith(".bias"):
+                sd[name] = 0.02 * torch.randn(shape, generator=g)
+                continue
+            fan_in = math.prod(shape[1:])
+            gain = math.sqrt(2.0)
+            if name.endswith(".conv.4.weight"):
+                gain = 0.3
+            elif ".conv.weight" in name or name in ("encoder.3.weight", "encoder.8.weight", "encoder.13.weight", "encoder.17.weight"):
+                gain = 1.0             # TPool, the conv behind it and the head: no ReLU in between / after
+            sd[name] = torch.randn(shape, generator=g) * (gain / math.sqrt(fan_in))
+        return sd
+
+    @staticmethod
+    def checksum(sd):
+        """sha256 over the float32 bytes of the encoder tensors in state_dict_spec order."""
+        h = hashlib.sha256()
+        for name, _ in TAEHVEncoder.state_dict_spec():
+            h.update(sd[name].detach().float().contiguous().cpu().numpy().tobytes())
+        return h.hexdigest()
+
+    def init_random_weights(self, seed=0):
+        self.load_state_dict(self.random_state_dict(seed))
+        return self
+
+    # ------------------------------------------------------------------ arena / state views
+    def _new_arena(self, H, W):
+        n = enc_arena_bytes(H, W, self.GROUP)
+        if n == 0:
+            raise ValueError(f"TAEHV encoder: frame size {H}x{W} not supported (H and W must be multiples of 8)")
+        return torch.empty(n + 256, dtype=torch.uint8, device=self.device)   # the state is zeroed by a stream's first call
+
+    def _state_views(self, arena, base, H, W):
+        views = []
+        off, C, h, w = ctypes.c_size_t(0), ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+        for i in range(9):
+            _lib.call("rtv_taehv_enc_state_slot", H, W, i, ctypes.byref(off), ctypes.byref(C), ctypes.byref(h), ctypes.byref(w))
+            start = base + off.value
+            v = arena[start:start + C.value * h.value * w.value * 2].view(torch.float16).view(h.value, w.value, C.value)
+            views.append(v.permute(2, 0, 1).unsqueeze(0))     # [1, C, h, w] (channels-last in memory)
+        self._arenas.register(views, arena, base, (H, W))
+        return views
+
+    # ------------------------------------------------------------------ forward
+    def forward(self, z, feat_cache=None, stream=False):
+        if self._w is None:
+            raise RuntimeError("TAEHV encoder: weights not loaded")
+        if not z.is_cuda:
+            raise RuntimeError("realtime_video_amd.TAEHVEncoder needs GPU tensors (no CPU fallback)")
+        B, Cc, T, H, W = z.shape
+        if B != 1 or Cc != 3:
+            raise NotImplementedError("TAEHV encoder: batch 1, RGB frames")
+        fresh = feat_cache is None or len(feat_cache) == 0 or feat_cache[0] is None
+        rule = ("TAEHV encoder time contract: a fresh cache takes T = 1 + 4k frames (frame 0 is presented four times), "
+                "a carried cache with stream=True takes T = 4k")
+        if fresh:
+            if T < 1 or (T - 1) % 4:
+                raise ValueError(f"{rule}; got a fresh cache with T = {T}")
+        elif not stream or T < 4 or T % 4:
+            raise ValueError(f"{rule}; got a carried cache with T = {T}, stream={bool(stream)}")
+        if H % 8 or W % 8 or enc_arena_bytes(H, W, self.GROUP) == 0:
+            raise ValueError(f"TAEHV encoder: frame size {H}x{W} not supported (H and W must be multiples of 8)")
+        frames = z[0].to(torch.float16)
+        if fresh:
+            frames = torch.cat([frames[:, :1].expand(-1, 3, -1, -1), frames], 1)
+            ent = self._arenas.recycle((H, W))   # the arena of a dropped stream of this size, if any
+            arena, base = ent if ent is not None else (None, 0)
+            if arena is None:
+                arena = self._new_arena(H, W)
+                base = (-arena.data_ptr()) % 256
+            views = self._state_views(arena, base, H, W)
+        else:
+            views = feat_cache if isinstance(feat_cache, list) else list(feat_cache)
+            if len(views) != 9:
+                raise ValueError(f"TAEHV encoder: a carried cache is the nine state slices a previous call returned, got {len(views)} slots")
+            arena, base = self._arenas.lookup(views, (H, W), lambda: self._new_arena(H, W),
+                                              lambda a, b: self._state_views(a, b, H, W))
+        frames = frames.contiguous()
+        Tt = frames.shape[1]
+        n_out = Tt // 4
+        mu = torch.empty((16, n_out, H // 8, W // 8), dtype=torch.float16, device=z.device)
+        st = c_vp(torch.cuda.current_stream().cuda_stream)
+        for t0 in range(0, Tt, self.GROUP):
+            tn = min(self.GROUP, Tt - t0)
+            _lib.call("rtv_taehv_encode", ctypes.byref(self._w), c_vp(frames.data_ptr()), Tt, t0, tn, H, W, int(fresh and t0 == 0),
+                      c_vp(arena.data_ptr() + base), ctypes.c_size_t(arena.numel() - base), c_vp(mu.data_ptr()), n_out, t0 // 4, st)
+        return mu.unsqueeze(0).to(z.dtype), views
 
     __call__ = forward
