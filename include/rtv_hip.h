@@ -469,6 +469,32 @@ int rtv_vae_enc_cache_slot(int H, int W, int slot, size_t* offset, int* C, int* 
 int rtv_vae_encode(const rtv_vae_enc_weights* w, const void* frames, int Ttot, int t0, int tn, int H, int W, int first,
                    void* arena, size_t arena_bytes, void* mu, int Tout_tot, int tout, rtv_stream_t stream);
 
+/* ---- single pieces of the Wan VAE paths (used by the tests): each runs what rtv_vae_decode / rtv_vae_encode run at that
+ * point - the same function or kernel with the same grid - on caller-supplied buffers, after checking its arguments. */
+/* Mid-block AttentionBlock (vae.py:212-251) on one frame: x, y fp16 channels-last [h*w][384], y = x + proj(attention(norm(x))),
+ * x != y; weights as the decoder prepares them (wq / bq pre-scaled by 1/sqrt(384)).  arena: 256-byte aligned scratch of
+ * rtv_vae_attn_arena_bytes(h, w) bytes (0 = unsupported size; h*w % 8 == 0), contents irrelevant. */
+size_t rtv_vae_attn_arena_bytes(int h, int w);
+int rtv_vae_mid_attention(const rtv_vae_attn* a, const void* x, void* y, int h, int w, void* arena, size_t arena_bytes,
+                          rtv_stream_t stream);
+/* Decoder prologue: latent frame t of z fp16 [T][16][hw] -> conv2(z / fp16(1 / std) + mean) (fp16 rounding points of
+ * vae_block3.py:206-211, the 16x16 matrix in float32) -> out fp16 channels-last [hw][32], channels 16..31 zero.
+ * mean, std, conv2_w [16][16], conv2_b: float32. */
+int rtv_vae_prep(const void* z, int T, int t, int hw, const void* mean, const void* std, const void* conv2_w,
+                 const void* conv2_b, void* out, rtv_stream_t stream);
+/* Decoder epilogue: head output fp16 [T][in_hw][8] (3 real channels), pixels skip_px .. skip_px + hw of every frame ->
+ * float32 [T][3][hw] clamped to [-1, 1]. */
+int rtv_vae_final(const void* in, void* pixels, int T, int64_t hw, int64_t in_hw, int64_t skip_px, rtv_stream_t stream);
+/* Temporal-upsampling cache update after a one-frame call (vae_block3.py:56-62) on buf = [c0 | c1 | x], three fp16 slices of
+ * `slice` elements: c0 <- where(c1 == 0, 0, x), c1 <- x. */
+int rtv_vae_upsample_cache_t1(void* buf, int64_t slice, rtv_stream_t stream);
+/* Encoder prologue: frames t0 .. t0 + T of fp16 planar [3][Ttot][hw] -> out fp16 channels-last [T][hw][32], channels 3..31 zero. */
+int rtv_vae_enc_prep(const void* frames, int Ttot, int t0, int T, int64_t hw, void* out, rtv_stream_t stream);
+/* Encoder epilogue: head output fp16 [T][hw][32] -> the wrapper's conv1 (float32 [32][32], [32]; first 16 outputs = mu) ->
+ * fp16((fp16(mu) - fp16(mean)) * fp16(1 / fp16(std))) -> mu fp16 [16][Tout_tot][hw], frames tout .. tout + T. */
+int rtv_vae_enc_final(const void* in, int T, int64_t hw, const void* conv1x1_w, const void* conv1x1_b, const void* mean,
+                      const void* std, void* mu, int Tout_tot, int tout, rtv_stream_t stream);
+
 /* ---- TAEHV tiny-VAE streaming decoder (opt-in fast decode, `use_taehv`; csrc/taehv.hip) ----------------------------
  * The `decoder` of demo_utils/taehv.py:159-234 (checkpoint taew2_1.pth): Clamp, conv 16 -> 256, three stages of three
  * MemBlocks (256, 128, 64 channels) with nearest-2x upsampling + TGrow between them, conv 64 -> 64, ReLU, conv 64 -> 3.
@@ -503,6 +529,10 @@ int rtv_taehv_decode(const rtv_taehv_weights* w, const void* z, int T, int h, in
 int rtv_taehv_conv(const void* in, const void* w, const void* bias, const void* residual, void* out, int T, int H, int W,
                    int Cin, int Cout, int kt, int ups, int n_split, int relu, int head, const void* zeros,
                    rtv_stream_t stream);
+
+/* The prologue of rtv_taehv_decode on its own (tests): z fp16 [T][16][hw] -> tanh(z / 3) * 3 -> out fp16 channels-last
+ * [T][hw][32], channels 16..31 zero. */
+int rtv_taehv_prep(const void* z, int T, int hw, void* out, rtv_stream_t stream);
 
 /* ---- TAEHV tiny-VAE streaming encoder (pixel -> latent side of `use_taehv`; csrc/taehv.hip) -------------------------
  * The `encoder` of demo_utils/taehv.py:172-178 (checkpoint taew2_1.pth): conv 3 -> 64 + ReLU, then three stages of

@@ -362,6 +362,12 @@ __global__ void taehv_prep_kernel(const f16_t* __restrict__ z, int T, int hw, f1
   dst[2] = o[2];
   dst[3] = o[3];
 }
+// its launch: rtv_taehv_decode and the test entry rtv_taehv_prep both go through it
+static int launch_prep(const void* z, int T, int hw, void* out, hipStream_t stream) {
+  const int n = T * hw;
+  hipLaunchKernelGGL(taehv_prep_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, (const f16_t*)z, T, hw, (f16_t*)out);
+  return check_launch("taehv_prep");
+}
 
 // ---------------------------------------------------------------- arena
 // [9 MemBlock state slices | scratch for calls of up to t_max latent frames].  The state slices come first, at offsets that
@@ -632,6 +638,14 @@ extern "C" int rtv_taehv_conv(const void* in, const void* w, const void* bias, c
   return tae::launch_conv(p, head ? 1 : 0, (hipStream_t)stream);
 }
 
+// the Clamp + layout prologue of rtv_taehv_decode on its own, used by the tests
+extern "C" int rtv_taehv_prep(const void* z, int T, int hw, void* out, rtv_stream_t stream) {
+  if (!z || !out) return set_error(-1, "taehv_prep: null argument");
+  if (T <= 0 || hw <= 0 || (int64_t)T * hw > (1 << 26)) return set_error(-1, "taehv_prep: T and hw must be positive");
+  if (((uintptr_t)out) & 15) return set_error(-1, "taehv_prep: out must be 16-byte aligned");
+  return tae::launch_prep(z, T, hw, out, (hipStream_t)stream);
+}
+
 extern "C" int rtv_taehv_decode(const rtv_taehv_weights* wt, const void* z, int T, int h, int w, int first, void* arena,
                                 size_t arena_bytes, void* pixels, rtv_stream_t stream_) {
   if (!wt || !z || !arena || !pixels) return set_error(-1, "taehv_decode: null argument");
@@ -672,10 +686,7 @@ extern "C" int rtv_taehv_decode(const rtv_taehv_weights* wt, const void* z, int 
 
   // decoder.0 (Clamp) + layout, decoder.1 / 2: conv 16 -> 256 + bias, ReLU -> slices 1..T of the first MemBlock's concat buffer
   {
-    const int n = T * h * w;
-    hipLaunchKernelGGL(tae::taehv_prep_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, (const f16_t*)z, T, h * w,
-                       (f16_t*)at(L.x0));
-    TAE_TRY(check_launch("taehv_prep"));
+    TAE_TRY(tae::launch_prep(z, T, h * w, at(L.x0), stream));
     const size_t sl = (size_t)h * w * 256;
     TAE_TRY(conv(at(L.x0), wt->conv_in.w, wt->conv_in.b, nullptr, at(L.cat[0][0]) + sl, T, h, w, 32, 256, 1, 0, 0, 1, 0));
   }

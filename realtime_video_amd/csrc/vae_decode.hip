@@ -287,6 +287,20 @@ struct VaeLayout {
   int ldp;
 };
 
+// scratch of mid_attention() for one frame of P = h * w latent pixels, taken in this order by the decoder's and the encoder's
+// arena layouts and by the stand-alone layout of rtv_vae_mid_attention
+template <class Take>
+static void take_attn(VaeLayout* L, size_t P, Take&& take) {
+  L->ldp = (int)((P + 63) / 64 * 64);
+  L->s_off = take(P * P * 2);
+  L->p_off = take(P * (size_t)L->ldp * 2);
+  L->q_off = take(P * 384 * 2);
+  L->k_off = take(P * 384 * 2);
+  L->vt_off = take((size_t)384 * L->ldp * 2);
+  L->o_off = take(P * 384 * 2);
+  L->xn_off = take(P * 384 * 2);
+}
+
 constexpr int SLIDE_FRAMES = 3;   // latent frames a decoder concat buffer takes before its cache slices are copied to the front
 
 // concat-buffer table in execution order: (channels, stage, Tmax)
@@ -331,15 +345,7 @@ static void build_layout(int h, int w, const RowPlan& plan, VaeLayout* L) {
     }
   }
   for (int i = 0; i < 4; ++i) L->act_off[i] = take(amax);
-  const size_t P = (size_t)h * w;
-  L->ldp = (int)((P + 63) / 64 * 64);
-  L->s_off = take(P * P * 2);
-  L->p_off = take(P * (size_t)L->ldp * 2);
-  L->q_off = take(P * 384 * 2);
-  L->k_off = take(P * 384 * 2);
-  L->vt_off = take((size_t)384 * L->ldp * 2);
-  L->o_off = take(P * 384 * 2);
-  L->xn_off = take(P * 384 * 2);
+  take_attn(L, (size_t)h * w, take);
   L->head_off = take((size_t)4 * (plan.b[3] - plan.a[3]) * (w << 3) * 8 * 2);
   L->zeros_off = take(256);
   L->total = off + 256;
@@ -511,6 +517,28 @@ static int mid_attention(Ctx& c, const rtv_vae_attn& a, const uint16_t* x, uint1
   return 0;
 }
 
+// V^T pad columns (K padding of the P.V GEMM) must be zero: once per call, before the first mid_attention()
+static bool clear_vt_pad(char* arena, const VaeLayout& L, int P, hipStream_t stream) {
+  if (L.ldp == P) return true;
+  return hipMemsetAsync(arena + L.vt_off, 0, (size_t)384 * L.ldp * 2, stream) == hipSuccess;
+}
+
+// the launches of the decoder's glue kernels: the decode path and the test entries (rtv_vae_prep, ...) both go through these
+static int launch_vae_prep(const void* z, int t, int hw, const void* mean, const void* stdv, const void* w2, const void* b2,
+                           void* out, hipStream_t stream) {
+  hipLaunchKernelGGL(vae_prep_kernel, dim3((hw + 127) / 128), dim3(128), 0, stream, (const f16_t*)z, t, hw, (const float*)mean,
+                     (const float*)stdv, (const float*)w2, (const float*)b2, (f16_t*)out);
+  return check_launch("vae_prep");
+}
+static int launch_vae_final(const void* in, void* out, int T, int64_t hw, int64_t in_hw, int64_t skip_px, hipStream_t stream) {
+  hipLaunchKernelGGL(vae_final_kernel, dim3(2048), dim3(256), 0, stream, (const f16_t*)in, (float*)out, T, hw, in_hw, skip_px);
+  return check_launch("vae_final");
+}
+static int launch_upsample_cache_t1(void* buf, int64_t slice, hipStream_t stream) {
+  hipLaunchKernelGGL(upsample_cache_t1_kernel, dim3(1024), dim3(256), 0, stream, (f16_t*)buf, slice);
+  return check_launch("upsample_cache_t1");
+}
+
 }  // namespace
 
 extern "C" int rtv_conv_cl_win(const void* in, const void* w, const void* bias, const void* residual, int res_ld,
@@ -543,10 +571,7 @@ static int vae_decode_impl(const rtv_vae_weights* w, const void* z, int T, int h
   const int W8 = wd * 8;
   const int64_t out_hw = (int64_t)(row1 - row0) * W8;
   int out_frame = 0;
-  // V^T pad columns (K padding of the P.V GEMM) must be zero
-  if (L.ldp != h * wd)
-    if (hipMemsetAsync((char*)arena + L.vt_off, 0, (size_t)384 * L.ldp * 2, stream) != hipSuccess)
-      return set_error(-1, "vae_decode: memset failed");
+  if (!clear_vt_pad((char*)arena, L, h * wd, stream)) return set_error(-1, "vae_decode: memset failed");
 
   for (int f = 0; f < T; ++f) {
     const bool is_first = first && f == 0;
@@ -555,10 +580,7 @@ static int vae_decode_impl(const rtv_vae_weights* w, const void* z, int T, int h
     // conv2 (1x1x1, 16->16) + de-normalisation, written into conv1's concat buffer (32-channel padded)
     {
       const size_t sl = (size_t)H * W * 32;
-      hipLaunchKernelGGL(vae_prep_kernel, dim3((H * W + 127) / 128), dim3(128), 0, stream, (const f16_t*)z, f, H * W,
-                         (const float*)w->mean, (const float*)w->std, (const float*)w->conv2_w,
-                         (const float*)w->conv2_b, (f16_t*)(c.cat(0) + 2 * sl));
-      RTV_TRY(check_launch("vae_prep"));
+      RTV_TRY(launch_vae_prep(z, f, H * W, w->mean, w->std, w->conv2_w, w->conv2_b, c.cat(0) + 2 * sl, stream));
     }
     RTV_TRY(cached_conv3(c, 0, 1, H, W, 32, w->conv1, 384, nullptr, a0, 384));
     RTV_TRY(res_block(c, 1, 1, H, W, 384, 384, w->mid0, a0, a1, a2, a3));
@@ -609,8 +631,7 @@ static int vae_decode_impl(const rtv_vae_weights* w, const void* z, int T, int h
                 hipMemcpyAsync(buf + sl, buf + 2 * sl, sl * 2, hipMemcpyDeviceToDevice, stream) != hipSuccess)
               return set_error(-1, "vae_decode: memset / memcpy failed");
           } else if (Tn == 1) {
-            hipLaunchKernelGGL(upsample_cache_t1_kernel, dim3(1024), dim3(256), 0, stream, (f16_t*)buf, (int64_t)sl);
-            RTV_TRY(check_launch("upsample_cache_t1"));
+            RTV_TRY(launch_upsample_cache_t1(buf, (int64_t)sl, stream));
           } else {
             if (hipMemcpyAsync(buf, buf + (size_t)Tn * sl, 2 * sl * 2, hipMemcpyDeviceToDevice, stream) != hipSuccess)
               return set_error(-1, "vae_decode: memcpy failed");
@@ -638,10 +659,8 @@ static int vae_decode_impl(const rtv_vae_weights* w, const void* z, int T, int h
       RTV_TRY(rtv_rmsnorm_silu_cl(x, c.cat(31) + 2 * sl, w->head_gamma, 96, (int64_t)Tn * H * W, 1, stream));
       uint16_t* ho = (uint16_t*)((char*)arena + L.head_off);
       RTV_TRY(cached_conv3(c, 31, Tn, H, W, 96, w->head, 8, nullptr, ho, 8));
-      hipLaunchKernelGGL(vae_final_kernel, dim3(2048), dim3(256), 0, stream, (const f16_t*)ho,
-                         (float*)pixels + (size_t)out_frame * 3 * out_hw, Tn, out_hw, (int64_t)H * W,
-                         (int64_t)(row0 - P.a[3]) * W);
-      RTV_TRY(check_launch("vae_final"));
+      RTV_TRY(launch_vae_final(ho, (float*)pixels + (size_t)out_frame * 3 * out_hw, Tn, out_hw, (int64_t)H * W,
+                               (int64_t)(row0 - P.a[3]) * W, stream));
       out_frame += Tn;
     }
   }
@@ -661,6 +680,71 @@ extern "C" int rtv_vae_decode(const rtv_vae_weights* w, const void* z, int T, in
 extern "C" int rtv_vae_decode_single(const rtv_vae_weights* w, const void* z, int h, int wd, int is_first_frame, void* arena,
                                      size_t arena_bytes, void* pixels, rtv_stream_t stream) {
   return vae_decode_impl(w, z, 1, h, wd, is_first_frame ? 1 : 0, 0, h << 3, arena, arena_bytes, pixels, stream, true);
+}
+
+// ------------------------------------------------------------------ single pieces of the decode path, used by the tests
+// Each entry checks its arguments on the host and then runs exactly what rtv_vae_decode runs: mid_attention() and the
+// launch_* helpers above (same kernel, same grid).
+static bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+
+extern "C" size_t rtv_vae_attn_arena_bytes(int h, int w) {
+  if (h <= 0 || w <= 0 || (int64_t)h * w > (1 << 20) || (h * w) % 8) return 0;
+  VaeLayout L;
+  size_t off = 0;
+  take_attn(&L, (size_t)h * w, [&](size_t bytes) {
+    size_t a = (off + 255) & ~(size_t)255;
+    off = a + bytes;
+    return a;
+  });
+  return off + 256;
+}
+
+extern "C" int rtv_vae_mid_attention(const rtv_vae_attn* a, const void* x, void* y, int h, int w, void* arena,
+                                     size_t arena_bytes, rtv_stream_t stream_) {
+  if (!a || !x || !y || !arena) return set_error(-1, "vae_mid_attention: null argument");
+  if (!a->gamma || !a->wq || !a->bq || !a->wk || !a->bk || !a->wv || !a->bv || !a->wproj || !a->bproj)
+    return set_error(-1, "vae_mid_attention: null weight");
+  if (x == y) return set_error(-1, "vae_mid_attention: x and y must be different buffers (x is the residual)");
+  if (h <= 0 || w <= 0 || (int64_t)h * w > (1 << 20) || (h * w) % 8)
+    return set_error(-1, "vae_mid_attention: h*w must be a positive multiple of 8");
+  if ((((uintptr_t)arena) & 255) || !aligned16(x) || !aligned16(y))
+    return set_error(-1, "vae_mid_attention: arena must be 256-byte aligned, x / y 16-byte aligned");
+  VaeLayout L;
+  size_t off = 0;
+  take_attn(&L, (size_t)h * w, [&](size_t bytes) {
+    size_t at = (off + 255) & ~(size_t)255;
+    off = at + bytes;
+    return at;
+  });
+  L.total = off + 256;
+  if (arena_bytes < L.total) return set_error(-1, "vae_mid_attention: arena too small (see rtv_vae_attn_arena_bytes)");
+  hipStream_t stream = (hipStream_t)stream_;
+  Ctx c{(char*)arena, &L, h, w, stream, 0};
+  if (!clear_vt_pad((char*)arena, L, h * w, stream)) return set_error(-1, "vae_mid_attention: memset failed");
+  return mid_attention(c, *a, (const uint16_t*)x, (uint16_t*)y);
+}
+
+extern "C" int rtv_vae_prep(const void* z, int T, int t, int hw, const void* mean, const void* stdv, const void* conv2_w,
+                            const void* conv2_b, void* out, rtv_stream_t stream) {
+  if (!z || !mean || !stdv || !conv2_w || !conv2_b || !out) return set_error(-1, "vae_prep: null argument");
+  if (T <= 0 || t < 0 || t >= T || hw <= 0 || hw > (1 << 24)) return set_error(-1, "vae_prep: frame index or size out of range");
+  if (!aligned16(out)) return set_error(-1, "vae_prep: out must be 16-byte aligned");
+  return launch_vae_prep(z, t, hw, mean, stdv, conv2_w, conv2_b, out, (hipStream_t)stream);
+}
+
+extern "C" int rtv_vae_final(const void* in, void* pixels, int T, int64_t hw, int64_t in_hw, int64_t skip_px,
+                             rtv_stream_t stream) {
+  if (!in || !pixels) return set_error(-1, "vae_final: null argument");
+  if (T <= 0 || hw <= 0 || skip_px < 0 || skip_px + hw > in_hw || in_hw > ((int64_t)1 << 32) / T)
+    return set_error(-1, "vae_final: the row window [skip_px, skip_px + hw) must lie inside a frame of in_hw pixels");
+  if (!aligned16(in)) return set_error(-1, "vae_final: in must be 16-byte aligned");
+  return launch_vae_final(in, pixels, T, hw, in_hw, skip_px, (hipStream_t)stream);
+}
+
+extern "C" int rtv_vae_upsample_cache_t1(void* buf, int64_t slice, rtv_stream_t stream) {
+  if (!buf) return set_error(-1, "vae_upsample_cache_t1: null argument");
+  if (slice <= 0 || slice > ((int64_t)1 << 32)) return set_error(-1, "vae_upsample_cache_t1: slice must be positive");
+  return launch_upsample_cache_t1(buf, slice, (hipStream_t)stream);
 }
 
 // ====================================================================================== streaming encoder
@@ -723,6 +807,18 @@ __global__ void vae_enc_final_kernel(const f16_t* __restrict__ in, int T, int64_
 
 namespace {
 
+// the launches of the encoder's glue kernels: rtv_vae_encode and the test entries (rtv_vae_enc_prep, rtv_vae_enc_final)
+static int launch_vae_enc_prep(const void* frames, int Ttot, int t0, int T, int64_t hw, void* out, hipStream_t stream) {
+  hipLaunchKernelGGL(vae_enc_prep_kernel, dim3(2048), dim3(256), 0, stream, (const f16_t*)frames, Ttot, t0, T, hw, (f16_t*)out);
+  return check_launch("vae_enc_prep");
+}
+static int launch_vae_enc_final(const void* in, int T, int64_t hw, const void* w1, const void* b1, const void* mean,
+                                const void* stdv, void* mu, int Tout_tot, int tout, hipStream_t stream) {
+  hipLaunchKernelGGL(vae_enc_final_kernel, dim3((unsigned)((T * hw + 127) / 128)), dim3(128), 0, stream, (const f16_t*)in, T, hw,
+                     (const float*)w1, (const float*)b1, (const float*)mean, (const float*)stdv, (f16_t*)mu, Tout_tot, tout);
+  return check_launch("vae_enc_final");
+}
+
 // concat buffers of the encoder in execution order: (input channels, stage = log2 of the spatial reduction, max new slices)
 static void build_enc_layout(int H, int W, VaeLayout* L) {
   const int C[24] = {32, 96, 96, 96, 96,        // conv1, downsamples.0 (a,b), .1 (a,b)
@@ -755,14 +851,7 @@ static void build_enc_layout(int H, int W, VaeLayout* L) {
   const size_t amax = (size_t)4 * H * W * 96 * 2;
   for (int i = 0; i < 4; ++i) L->act_off[i] = take(amax);
   const size_t P = (size_t)(H >> 3) * (W >> 3);
-  L->ldp = (int)((P + 63) / 64 * 64);
-  L->s_off = take(P * P * 2);
-  L->p_off = take(P * (size_t)L->ldp * 2);
-  L->q_off = take(P * 384 * 2);
-  L->k_off = take(P * 384 * 2);
-  L->vt_off = take((size_t)384 * L->ldp * 2);
-  L->o_off = take(P * 384 * 2);
-  L->xn_off = take(P * 384 * 2);
+  take_attn(L, P, take);
   L->head_off = take(P * 32 * 2);
   L->zeros_off = take(256);
   L->total = off + 256;
@@ -818,9 +907,7 @@ extern "C" int rtv_vae_encode(const rtv_vae_enc_weights* w, const void* frames, 
   const int h = H >> 3, wd = W >> 3;
   Ctx c{(char*)arena, &L, h, wd, stream, 0};
   c.fresh = first && g_fresh_tap_skip.load(std::memory_order_relaxed);
-  if (L.ldp != h * wd)
-    if (hipMemsetAsync((char*)arena + L.vt_off, 0, (size_t)384 * L.ldp * 2, stream) != hipSuccess)
-      return set_error(-1, "vae_encode: memset failed");
+  if (!clear_vt_pad((char*)arena, L, h * wd, stream)) return set_error(-1, "vae_encode: memset failed");
 
   if (first) {
     // a fresh stream reads zeros wherever the reference has no cache yet (vae.py:17-36: zero padding in front of the first
@@ -836,9 +923,7 @@ extern "C" int rtv_vae_encode(const rtv_vae_enc_weights* w, const void* frames, 
   }
   int T = tn, Hs = H, Ws = W;
   // pixels -> conv1's concat buffer (channels-last, 32-channel padded)
-  hipLaunchKernelGGL(vae_enc_prep_kernel, dim3(2048), dim3(256), 0, stream, (const f16_t*)frames, Ttot, t0, T,
-                     (int64_t)H * W, (f16_t*)(c.cat(0) + 2 * (size_t)H * W * 32));
-  RTV_TRY(check_launch("vae_enc_prep"));
+  RTV_TRY(launch_vae_enc_prep(frames, Ttot, t0, T, (int64_t)H * W, c.cat(0) + 2 * (size_t)H * W * 32, stream));
   uint16_t* x = c.act(0);
   RTV_TRY(cached_conv3(c, 0, T, Hs, Ws, 32, w->conv1, 96, nullptr, x, 96));
   auto others = [&](uint16_t** out3) {  // the three activation buffers that do not hold x
@@ -902,12 +987,27 @@ extern "C" int rtv_vae_encode(const rtv_vae_enc_weights* w, const void* frames, 
     uint16_t* ho = (uint16_t*)((char*)arena + L.head_off);
     RTV_TRY(cached_conv3(c, ci, T, Hs, Ws, 384, w->head, 32, nullptr, ho, 32));
     const int64_t hw = (int64_t)Hs * Ws;
-    hipLaunchKernelGGL(vae_enc_final_kernel, dim3((unsigned)((T * hw + 127) / 128)), dim3(128), 0, stream, (const f16_t*)ho,
-                       T, hw, (const float*)w->conv1x1_w, (const float*)w->conv1x1_b, (const float*)w->mean,
-                       (const float*)w->std, (f16_t*)mu, Tout_tot, tout);
-    RTV_TRY(check_launch("vae_enc_final"));
+    RTV_TRY(launch_vae_enc_final(ho, T, hw, w->conv1x1_w, w->conv1x1_b, w->mean, w->std, mu, Tout_tot, tout, stream));
   }
   return flush_caches(c, 24);   // (a no-op today: the encoder's buffers hold one chunk, every roll copies)
+}
+
+// ------------------------------------------------------------------ single pieces of the encode path, used by the tests
+extern "C" int rtv_vae_enc_prep(const void* frames, int Ttot, int t0, int T, int64_t hw, void* out, rtv_stream_t stream) {
+  if (!frames || !out) return set_error(-1, "vae_enc_prep: null argument");
+  if (T <= 0 || t0 < 0 || t0 + T > Ttot || hw <= 0 || hw > ((int64_t)1 << 28) / T)
+    return set_error(-1, "vae_enc_prep: frame range outside the clip");
+  if (!aligned16(out)) return set_error(-1, "vae_enc_prep: out must be 16-byte aligned");
+  return launch_vae_enc_prep(frames, Ttot, t0, T, hw, out, (hipStream_t)stream);
+}
+
+extern "C" int rtv_vae_enc_final(const void* in, int T, int64_t hw, const void* conv1x1_w, const void* conv1x1_b,
+                                 const void* mean, const void* stdv, void* mu, int Tout_tot, int tout, rtv_stream_t stream) {
+  if (!in || !conv1x1_w || !conv1x1_b || !mean || !stdv || !mu) return set_error(-1, "vae_enc_final: null argument");
+  if (T <= 0 || hw <= 0 || hw > ((int64_t)1 << 28) / T || tout < 0 || tout + T > Tout_tot)
+    return set_error(-1, "vae_enc_final: latent frame range outside the output");
+  if (!aligned16(in)) return set_error(-1, "vae_enc_final: in must be 16-byte aligned");
+  return launch_vae_enc_final(in, T, hw, conv1x1_w, conv1x1_b, mean, stdv, mu, Tout_tot, tout, (hipStream_t)stream);
 }
 
 extern "C" int rtv_vae_set_fresh_tap_skip(int on) {   // include/rtv_hip_lab.h

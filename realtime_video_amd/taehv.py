@@ -47,6 +47,7 @@ _lib.EXTRA_SIGNATURES.update({
     "rtv_taehv_state_slot": [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_size_t)] + [ctypes.POINTER(ctypes.c_int)] * 3,
     "rtv_taehv_decode": [ctypes.POINTER(_TaehvWeights), c_vp] + [ctypes.c_int] * 4 + [c_vp, ctypes.c_size_t, c_vp, c_vp],
     "rtv_taehv_conv": [c_vp] * 5 + [ctypes.c_int] * 10 + [c_vp, c_vp],
+    "rtv_taehv_prep": [c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp],                        # used by the tests
     "rtv_taehv_enc_state_slot": [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_size_t)] + [ctypes.POINTER(ctypes.c_int)] * 3,
     "rtv_taehv_encode": [ctypes.POINTER(_TaehvEncWeights), c_vp] + [ctypes.c_int] * 6 + [c_vp, ctypes.c_size_t, c_vp,
                                                                                       ctypes.c_int, ctypes.c_int, c_vp],

@@ -55,6 +55,13 @@ _lib.EXTRA_SIGNATURES.update({
                               c_vp, c_vp],
     "rtv_conv_set_halo": [ctypes.c_int],
     "rtv_vae_cache_slot_rows": [ctypes.c_int] * 5 + [ctypes.POINTER(ctypes.c_size_t)] + [ctypes.POINTER(ctypes.c_int)] * 4,
+    # single pieces of the decode / encode paths (used by the tests)
+    "rtv_vae_mid_attention": [ctypes.POINTER(_Attn), c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, ctypes.c_size_t, c_vp],
+    "rtv_vae_prep": [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "rtv_vae_final": [c_vp, c_vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, c_vp],
+    "rtv_vae_upsample_cache_t1": [c_vp, ctypes.c_int64, c_vp],
+    "rtv_vae_enc_prep": [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64, c_vp, c_vp],
+    "rtv_vae_enc_final": [c_vp, ctypes.c_int, ctypes.c_int64, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp],
 })
 
 MEAN = [-0.7571, -0.7089, -0.9113, 0.1075, -0.1745, 0.9653, -0.1517, 1.5508,

@@ -28,6 +28,23 @@ def _conv_call(x, w, bias, res, out, T, H, W, Cin, Cout, kt, ups, n_split, relu,
     torch.cuda.synchronize()
 
 
+@pytest.mark.parametrize("T,hw", [(1, 96), (3, 60 * 104), (2, 777)])
+def test_prep_kernel_clamp_and_layout(T, hw):
+    """taehv_prep_kernel alone: z fp16 [T][16][hw] -> tanh(z / 3) * 3 -> channels-last [T][hw][32], within 1 fp16 ulp of the fp64
+    evaluation (the kernel rounds an fp32 tanhf); +-0, +-60, +-65504 and a subnormal among the inputs; channels 16..31 exact
+    zeros; nothing written behind the last pixel.  Inputs, reference and acceptance: tests/test_vae_units_cpu.py."""
+    import test_vae_units_cpu as U
+    from realtime_video_amd import _lib, taehv  # noqa: F401  (registers the signatures)
+    z = U.taehv_prep_inputs(T, hw, device=DEV)
+    out = torch.full((T * hw + 2, 32), float("nan"), dtype=torch.float16, device=DEV)
+    _lib.call("rtv_taehv_prep", _ptr(z), T, hw, _ptr(out), c_vp(torch.cuda.current_stream().cuda_stream))
+    torch.cuda.synchronize()
+    v = U.taehv_prep_violation(out[:T * hw].view(T, hw, 32), z)
+    print(f"taehv_prep T={T} hw={hw}: {v} ulp (bound 1)")
+    assert v <= 1
+    assert bool(torch.isnan(out[T * hw:]).all())
+
+
 FORMS = [
     # name, T, H, W, Cin, Cout, kt, ups, n_split, relu, residual, bias, head
     ("plain_relu_64", 2, 13, 21, 64, 64, 1, 0, 0, 1, False, True, False),
