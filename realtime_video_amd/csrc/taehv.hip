@@ -25,6 +25,8 @@
 #include "gemm_core.h"
 #include "rtv_internal.h"
 
+#include <string>
+
 namespace rtv {
 namespace tae {
 
@@ -315,32 +317,72 @@ static int launch_cfg(ConvParams p, hipStream_t stream) {
   return check_launch("taehv_conv");
 }
 
-// One layer.  The kernel configuration is a function of the layer only (head or Cout), never of T / H / W.
-static int launch_conv(ConvParams p, int head, hipStream_t stream) {
-  if (!p.in || !p.w || !p.out || !p.zeros) return set_error(-1, "taehv_conv: null pointer");
+// The common layer: one time tap, bias, no residual / upsampling / frame scatter / ReLU.  A call site sets what differs.
+static ConvParams make_params(const void* in, rtv_vae_conv c, void* out, const void* zeros, int T, int H, int W, int Cin, int Cout) {
+  ConvParams p{};
+  p.in = (const uint16_t*)in;
+  p.w = (const uint16_t*)c.w;
+  p.bias = (const uint16_t*)c.b;
+  p.out = out;
+  p.zeros = (const uint16_t*)zeros;
+  p.T = T;
+  p.H = H;
+  p.W = W;
+  p.Cin = Cin;
+  p.Cout = Cout;
+  p.kt = 1;
+  return p;
+}
+
+static int fail(const char* who, const char* what) { return set_error(-1, (std::string(who) + ": " + what).c_str()); }
+
+// PLAIN (also the upsampled and frame-scattering forms) and RGB_HEAD are the layers of rtv_taehv_conv; DOWN (stride 2, the
+// folded TPool's time taps) and LATENT_HEAD those of rtv_taehv_enc_conv
+enum Form { PLAIN, RGB_HEAD, DOWN, LATENT_HEAD };
+
+// One layer.  The kernel configuration is a function of the layer only (form or Cout), never of T / H / W.
+static int launch_layer(ConvParams p, Form form, hipStream_t stream) {
+  const bool enc = form == DOWN || form == LATENT_HEAD, head = form == RGB_HEAD || form == LATENT_HEAD;
+  const char* who = enc ? "taehv_enc_conv" : "taehv_conv";
+  if (!p.in || !p.w || !p.out || !p.zeros) return fail(who, "null pointer");
   if (p.T <= 0) return 0;
-  if (p.H <= 0 || p.W <= 0) return set_error(-1, "taehv_conv: bad size");
-  if (p.kt != 1 && p.kt != 2) return set_error(-1, "taehv_conv: kt must be 1 or 2");
-  if (p.ups != 0 && p.ups != 1) return set_error(-1, "taehv_conv: ups must be 0 or 1");
-  if (p.ups && ((p.H | p.W) & 1)) return set_error(-1, "taehv_conv: upsampled output dims must be even");
-  if (p.Cin <= 0 || p.Cin % 32) return set_error(-1, "taehv_conv: Cin must be a multiple of 32 (pad channels)");
-  if (head ? p.Cout != 8 : (p.Cout != 64 && p.Cout % 128 != 0))
-    return set_error(-1, "taehv_conv: Cout must be 8 (head), 64 or a multiple of 128");
-  if (head && (p.residual || p.n_split || p.relu)) return set_error(-1, "taehv_conv: the head has a bias-only epilogue");
-  if (p.n_split && (p.n_split % 8 || p.Cout != 2 * p.n_split)) return set_error(-1, "taehv_conv: n_split must be Cout / 2");
-  if ((((uintptr_t)p.in | (uintptr_t)p.w | (uintptr_t)p.out | (uintptr_t)p.residual | (uintptr_t)p.zeros) & 15) ||
-      ((uintptr_t)p.bias & 7))
-    return set_error(-1, "taehv_conv: pointers must be 16-byte aligned (bias 8)");
-  p.inH = p.H >> p.ups;
-  p.inW = p.W >> p.ups;
-  p.tstride = 1;
-  // the gather indexes the input with 32-bit element offsets
-  if ((size_t)(p.T + p.kt - 1) * p.inH * p.inW * p.Cin >= 0x7fffffffull || (size_t)p.T * p.H * p.W >= 0x7fffffffull)
-    return set_error(-1, "taehv_conv: input too large for 32-bit offsets");
+  if (p.H <= 0 || p.W <= 0) return fail(who, "bad size");
+  if (p.kt != 1 && p.kt != 2) return fail(who, "kt must be 1 or 2");
+  if (!enc) {
+    if (p.ups != 0 && p.ups != 1) return fail(who, "ups must be 0 or 1");
+    if (p.ups && ((p.H | p.W) & 1)) return fail(who, "upsampled output dims must be even");
+    if (p.Cin <= 0 || p.Cin % 32) return fail(who, "Cin must be a multiple of 32 (pad channels)");
+    if (head ? p.Cout != 8 : (p.Cout != 64 && p.Cout % 128 != 0)) return fail(who, "Cout must be 8 (head), 64 or a multiple of 128");
+    if (head && (p.residual || p.n_split || p.relu)) return fail(who, "the head has a bias-only epilogue");
+    if (p.n_split && (p.n_split % 8 || p.Cout != 2 * p.n_split)) return fail(who, "n_split must be Cout / 2");
+    p.inH = p.H >> p.ups;
+    p.inW = p.W >> p.ups;
+    p.tstride = 1;
+  } else {
+    if (p.Cin != 64) return fail(who, "Cin must be 64");
+    if (p.Cout != (head ? 16 : 64)) return fail(who, "Cout must be 64 (stride 2) or 16 (head)");
+    if (head && (p.kt != 1 || p.out_j < 0 || p.out_T <= 0 || p.out_j + p.T > p.out_T))
+      return fail(who, "head frames outside the output tensor");
+    p.ups = 0;
+    p.n_split = 0;
+    p.relu = 0;
+    p.residual = nullptr;
+    p.inH = head ? p.H : 2 * p.H;
+    p.inW = head ? p.W : 2 * p.W;
+    p.tstride = head ? 1 : p.kt;   // the folded TPool(64, 2) reads the frame pair (2t, 2t + 1): windows do not overlap
+  }
+  // the latent head stores single 2-byte elements
+  if ((((uintptr_t)p.in | (uintptr_t)p.w | (uintptr_t)p.residual | (uintptr_t)p.zeros) & 15) ||
+      ((uintptr_t)p.out & (form == LATENT_HEAD ? 1 : 15)) || ((uintptr_t)p.bias & 7))
+    return fail(who, "pointers must be 16-byte aligned (bias 8)");
+  // the gather indexes the input (slices 0 .. (T - 1) * tstride + kt - 1) with 32-bit element offsets
+  if (((size_t)(p.T - 1) * p.tstride + p.kt) * p.inH * p.inW * p.Cin >= 0x7fffffffull || (size_t)p.T * p.H * p.W >= 0x7fffffffull)
+    return fail(who, "input too large for 32-bit offsets");
   p.M = p.T * p.H * p.W;
-  if (head) return launch_cfg<128, 32, 32, 2, 1, 1>(p, stream);
-  if (p.Cout == 64) return launch_cfg<256, 64, 32, 4, 1, 0>(p, stream);
-  return launch_cfg<128, 128, 32, 2, 2, 0>(p, stream);
+  if (form == RGB_HEAD) return launch_cfg<128, 32, 32, 2, 1, 1>(p, stream);
+  if (form == PLAIN) return p.Cout == 64 ? launch_cfg<256, 64, 32, 4, 1, 0>(p, stream) : launch_cfg<128, 128, 32, 2, 2, 0>(p, stream);
+  if (form == LATENT_HEAD) return launch_cfg<128, 32, 32, 2, 1, 2>(p, stream);
+  return launch_cfg<256, 64, 32, 4, 1, 0, true>(p, stream);
 }
 
 // z fp16 [T][16][h][w] -> Clamp (tanh(x / 3) * 3) -> channels-last [T][h][w][32] (16 real + 16 zero channels)
@@ -370,46 +412,101 @@ static int launch_prep(const void* z, int T, int hw, void* out, hipStream_t stre
 }
 
 // ---------------------------------------------------------------- arena
-// [9 MemBlock state slices | scratch for calls of up to t_max latent frames].  The state slices come first, at offsets that
-// depend on (h, w) only, so a stream can move to a larger arena by copying that prefix.
-constexpr int kStageC[3] = {256, 128, 64};
+// [9 MemBlock state slices | codec region `pre` | per stage: two concat and two scratch buffers for calls of up to t_max
+// frames | codec region `post` | zero page].  The state slices come first, at offsets that depend on the frame size only, so a
+// stream can move to a larger arena by copying that prefix.
+struct Stage {
+  int H, W, C, F;   // geometry and frames per call of the stage's three MemBlocks
+  // cat: [state | F new slices]; cat[0] takes the stage's input in slices 1..F, cat[1] holds its output there after three blocks
+  size_t state[3], cat[2], tmp[2];
+  size_t slice() const { return (size_t)H * W * C; }   // elements
+};
 struct Layout {
-  size_t state[9], state_bytes;
-  size_t x0, cat[3][2], tmp[3][2], fin, zeros, total;
+  Stage st[3];
+  size_t state_bytes, pre, post, zeros, total;
 };
 
 static size_t al(size_t b) { return (b + 255) & ~(size_t)255; }
 
-static bool make_layout(int h, int w, int t_max, Layout* L) {
-  if (h <= 0 || w <= 0 || h > 1024 || w > 1024 || t_max < 0 || t_max > 4096) return false;
+// L->st[s].{H, W, C, F} are set by the caller
+static void make_layout(Layout* L, size_t pre_bytes, size_t post_bytes) {
   size_t off = 0;
-  for (int k = 0; k < 9; ++k) {
-    const int s = k / 3;
-    L->state[k] = off;
-    off += al((size_t)(h << s) * (w << s) * kStageC[s] * 2);
-  }
+  for (Stage& g : L->st)
+    for (size_t& o : g.state) {
+      o = off;
+      off += al(g.slice() * 2);
+    }
   L->state_bytes = off;
-  const size_t T = (size_t)t_max;
-  L->x0 = off;
-  off += al(T * h * w * 32 * 2);
-  for (int s = 0; s < 3; ++s) {
-    const size_t sl = (size_t)(h << s) * (w << s) * kStageC[s] * 2;
-    const size_t F = s < 2 ? T : 2 * T;
-    for (int j = 0; j < 2; ++j) {
-      L->cat[s][j] = off;
-      off += al((F + 1) * sl);
+  L->pre = off;
+  off += al(pre_bytes);
+  for (Stage& g : L->st) {
+    for (size_t& o : g.cat) {
+      o = off;
+      off += al((size_t)(g.F + 1) * g.slice() * 2);
     }
-    for (int j = 0; j < 2; ++j) {
-      L->tmp[s][j] = off;
-      off += al(F * sl);
+    for (size_t& o : g.tmp) {
+      o = off;
+      off += al((size_t)g.F * g.slice() * 2);
     }
   }
-  L->fin = off;
-  off += al((size_t)2 * (8 * h) * (8 * w) * 64 * 2);
+  L->post = off;
+  off += al(post_bytes);
   L->zeros = off;
   off += 256;
   L->total = off;
+}
+
+// Decoder: stages at (h, w) x 256, (2h, 2w) x 128, (4h, 4w) x 64 channels, the last at twice the latent frame rate.  pre = x0
+// (the prepped latents, 32 channels), post = fin (one 64-channel frame pair at 8h x 8w)
+static bool make_dec_layout(int h, int w, int t_max, Layout* L) {
+  if (h <= 0 || w <= 0 || h > 1024 || w > 1024 || t_max < 0 || t_max > 4096) return false;
+  for (int s = 0; s < 3; ++s) L->st[s] = Stage{h << s, w << s, 256 >> s, s < 2 ? t_max : 2 * t_max, {}, {}, {}};
+  make_layout(L, (size_t)t_max * h * w * 32 * 2, (size_t)2 * (8 * h) * (8 * w) * 64 * 2);
   return true;
+}
+
+// One helper behind rtv_taehv_state_slot and rtv_taehv_enc_state_slot
+static int state_slot(const Layout& L, const char* who, int slot, size_t* offset, int* C, int* H, int* W) {
+  if (slot < 0 || slot >= 9) return fail(who, "state slot must be 0..8");
+  const Stage& g = L.st[slot / 3];
+  if (offset) *offset = g.state[slot % 3];
+  if (C) *C = g.C;
+  if (H) *H = g.H;
+  if (W) *W = g.W;
+  return 0;
+}
+
+// The three MemBlocks of a stage, each ReLU(conv.4(ReLU(conv.2(ReLU(conv.0 over [x_{t-1} | x_t])))) + x_t).  The stage's input
+// is in slices 1..F of cat[0]; its output ends up in slices 1..F of cat[1].
+static int run_memblocks(char* A, const Stage& g, const rtv_vae_conv (*mem)[3], const uint16_t* zeros, const char* who,
+                         hipStream_t stream) {
+  auto at = [&](size_t off) { return (uint16_t*)(A + off); };
+  const size_t sl = g.slice();
+  auto conv = [&](const void* in, rtv_vae_conv c, const uint16_t* res, void* out, int kt) {
+    ConvParams p = make_params(in, c, out, zeros, g.F, g.H, g.W, g.C, g.C);
+    p.residual = res;
+    p.kt = kt;
+    p.relu = 1;
+    return launch_layer(p, PLAIN, stream);
+  };
+  for (int b = 0; b < 3; ++b) {
+    uint16_t *cur = at(g.cat[b & 1]), *nxt = at(g.cat[(b + 1) & 1]), *state = at(g.state[b]);
+    // [x_{t-1} | x_t] window: slice 0 = the block's input at the previous frame (carried across calls)
+    if (hipMemcpyAsync(cur, state, sl * 2, hipMemcpyDeviceToDevice, stream) != hipSuccess) return fail(who, "copy failed");
+    if (int st = conv(cur, mem[b][0], nullptr, at(g.tmp[0]), 2)) return st;
+    if (hipMemcpyAsync(state, cur + (size_t)g.F * sl, sl * 2, hipMemcpyDeviceToDevice, stream) != hipSuccess)
+      return fail(who, "copy failed");
+    if (int st = conv(at(g.tmp[0]), mem[b][1], nullptr, at(g.tmp[1]), 1)) return st;
+    if (int st = conv(at(g.tmp[1]), mem[b][2], cur + sl, nxt + sl, 1)) return st;
+  }
+  return 0;
+}
+
+// The start of a decode / encode call: the zero page, and on a stream's first call the state
+static int zero_fill(char* A, const Layout& L, int first, const char* who, hipStream_t stream) {
+  if (hipMemsetAsync(A + L.zeros, 0, 256, stream) != hipSuccess) return fail(who, "memset failed");
+  if (first && hipMemsetAsync(A, 0, L.state_bytes, stream) != hipSuccess) return fail(who, "memset failed");
+  return 0;
 }
 
 
@@ -420,34 +517,6 @@ static bool make_layout(int h, int w, int t_max, Layout* L) {
 // a plain stride-2 conv to H/8; three MemBlocks; conv 64 -> 16 + bias written as planar f16 latents.  The MemBlock convs are
 // the decoder's Cout = 64 forms above.  A call holds a multiple of 4 frames, so no TPool pair straddles two calls and the
 // carried state is the nine MemBlock inputs of the previous frame only.
-
-// One stride-2 layer or the latent head.  The kernel configuration is a function of the layer only.
-static int launch_enc_conv(ConvParams p, int head, hipStream_t stream) {
-  if (!p.in || !p.w || !p.out || !p.zeros) return set_error(-1, "taehv_enc_conv: null pointer");
-  if (p.T <= 0) return 0;
-  if (p.H <= 0 || p.W <= 0) return set_error(-1, "taehv_enc_conv: bad size");
-  if (p.kt != 1 && p.kt != 2) return set_error(-1, "taehv_enc_conv: kt must be 1 or 2");
-  if (p.Cin != 64) return set_error(-1, "taehv_enc_conv: Cin must be 64");
-  if (p.Cout != (head ? 16 : 64)) return set_error(-1, "taehv_enc_conv: Cout must be 64 (stride 2) or 16 (head)");
-  if (head && (p.kt != 1 || p.out_j < 0 || p.out_T <= 0 || p.out_j + p.T > p.out_T))
-    return set_error(-1, "taehv_enc_conv: head frames outside the output tensor");
-  if ((((uintptr_t)p.in | (uintptr_t)p.w | (uintptr_t)p.zeros) & 15) || ((uintptr_t)p.out & (head ? 1 : 15)) ||
-      ((uintptr_t)p.bias & 7))
-    return set_error(-1, "taehv_enc_conv: pointers must be 16-byte aligned (bias 8)");
-  p.ups = 0;
-  p.n_split = 0;
-  p.relu = 0;
-  p.residual = nullptr;
-  p.inH = head ? p.H : 2 * p.H;
-  p.inW = head ? p.W : 2 * p.W;
-  p.tstride = head ? 1 : p.kt;   // the folded TPool(64, 2) reads the frame pair (2t, 2t + 1): windows do not overlap
-  // the gather indexes the input with 32-bit element offsets
-  if ((size_t)p.T * p.kt * p.inH * p.inW * p.Cin >= 0x7fffffffull || (size_t)p.T * p.H * p.W >= 0x7fffffffull)
-    return set_error(-1, "taehv_enc_conv: input too large for 32-bit offsets");
-  p.M = p.T * p.H * p.W;
-  if (head) return launch_cfg<128, 32, 32, 2, 1, 2>(p, stream);
-  return launch_cfg<256, 64, 32, 4, 1, 0, true>(p, stream);
-}
 
 struct FirstParams {
   const uint16_t* frames;   // f16 planar [3][T_total][H][W] in [-1, 1]
@@ -550,40 +619,13 @@ static int launch_enc_first(FirstParams p, hipStream_t stream) {
   return check_launch("taehv_enc_first");
 }
 
-// [9 MemBlock state slices | two full-resolution 64-channel frames | per-stage concat / scratch buffers for calls of up to
-// t_max frames].  Layer 0 and the first folded down-conv run one frame pair at a time, so the full-resolution activations
-// never take more than two frames.
-struct EncLayout {
-  size_t state[9], state_bytes;
-  size_t full, cat[3][2], tmp[3][2], zeros, total;
-};
-
-static bool make_enc_layout(int H, int W, int t_max, EncLayout* L) {
+// Encoder: three 64-channel stages at H/2 (half the frame rate), H/4 and H/8 (a quarter).  pre = two full-resolution 64-channel
+// frames: layer 0 and the first folded down-conv run one frame pair at a time, so the full-resolution activations never take
+// more than two frames.  No post region.
+static bool make_enc_layout(int H, int W, int t_max, Layout* L) {
   if (H <= 0 || W <= 0 || H > 8192 || W > 8192 || (H & 7) || (W & 7) || t_max < 0 || t_max > 4096 || (t_max & 3)) return false;
-  size_t off = 0;
-  for (int k = 0; k < 9; ++k) {
-    const int s = k / 3;
-    L->state[k] = off;
-    off += al((size_t)(H >> (s + 1)) * (W >> (s + 1)) * 64 * 2);
-  }
-  L->state_bytes = off;
-  L->full = off;
-  off += al((size_t)2 * H * W * 64 * 2);
-  for (int s = 0; s < 3; ++s) {
-    const size_t sl = (size_t)(H >> (s + 1)) * (W >> (s + 1)) * 64 * 2;
-    const size_t F = s == 0 ? t_max / 2 : t_max / 4;
-    for (int j = 0; j < 2; ++j) {
-      L->cat[s][j] = off;
-      off += al((F + 1) * sl);
-    }
-    for (int j = 0; j < 2; ++j) {
-      L->tmp[s][j] = off;
-      off += al(F * sl);
-    }
-  }
-  L->zeros = off;
-  off += 256;
-  L->total = off;
+  for (int s = 0; s < 3; ++s) L->st[s] = Stage{H >> (s + 1), W >> (s + 1), 64, s == 0 ? t_max / 2 : t_max / 4, {}, {}, {}};
+  make_layout(L, (size_t)2 * H * W * 64 * 2, 0);
   return true;
 }
 
@@ -600,42 +642,26 @@ using namespace rtv;
 
 extern "C" size_t rtv_taehv_arena_bytes(int h, int w, int t_max) {
   tae::Layout L;
-  if (t_max <= 0 || !tae::make_layout(h, w, t_max, &L)) return 0;
+  if (t_max <= 0 || !tae::make_dec_layout(h, w, t_max, &L)) return 0;
   return L.total;
 }
 
 extern "C" int rtv_taehv_state_slot(int h, int w, int slot, size_t* offset, int* C, int* H, int* W) {
   tae::Layout L;
-  if (!tae::make_layout(h, w, 0, &L)) return set_error(-1, "taehv: bad latent size");
-  if (slot < 0 || slot >= 9) return set_error(-1, "taehv: state slot must be 0..8");
-  const int s = slot / 3;
-  if (offset) *offset = L.state[slot];
-  if (C) *C = tae::kStageC[s];
-  if (H) *H = h << s;
-  if (W) *W = w << s;
-  return 0;
+  if (!tae::make_dec_layout(h, w, 0, &L)) return set_error(-1, "taehv: bad latent size");
+  return tae::state_slot(L, "taehv", slot, offset, C, H, W);
 }
 
 extern "C" int rtv_taehv_conv(const void* in, const void* w, const void* bias, const void* residual, void* out, int T, int H,
                               int W, int Cin, int Cout, int kt, int ups, int n_split, int relu, int head, const void* zeros,
                               rtv_stream_t stream) {
-  tae::ConvParams p{};
-  p.in = (const uint16_t*)in;
-  p.w = (const uint16_t*)w;
-  p.bias = (const uint16_t*)bias;
+  tae::ConvParams p = tae::make_params(in, {w, bias}, out, zeros, T, H, W, Cin, Cout);
   p.residual = (const uint16_t*)residual;
-  p.out = out;
-  p.zeros = (const uint16_t*)zeros;
-  p.T = T;
-  p.H = H;
-  p.W = W;
-  p.Cin = Cin;
-  p.Cout = Cout;
   p.kt = kt;
   p.ups = ups;
   p.n_split = n_split;
   p.relu = relu ? 1 : 0;
-  return tae::launch_conv(p, head ? 1 : 0, (hipStream_t)stream);
+  return tae::launch_layer(p, head ? tae::RGB_HEAD : tae::PLAIN, (hipStream_t)stream);
 }
 
 // the Clamp + layout prologue of rtv_taehv_decode on its own, used by the tests
@@ -652,7 +678,7 @@ extern "C" int rtv_taehv_decode(const rtv_taehv_weights* wt, const void* z, int 
   if (T <= 0) return set_error(-1, "taehv_decode: T must be positive");
   if (((uintptr_t)arena) & 255) return set_error(-1, "taehv_decode: arena must be 256-byte aligned");
   tae::Layout L;
-  if (!tae::make_layout(h, w, T, &L)) return set_error(-1, "taehv_decode: unsupported latent size or T");
+  if (!tae::make_dec_layout(h, w, T, &L)) return set_error(-1, "taehv_decode: unsupported latent size or T");
   if (arena_bytes < L.total) return set_error(-1, "taehv_decode: arena too small for T (see rtv_taehv_arena_bytes)");
   // the largest gather input (the 64-channel MemBlock concat buffers, 2T + 1 slices) must stay within 32-bit offsets
   if ((size_t)(2 * T + 1) * (4 * h) * (4 * w) * 64 >= 0x7fffffffull) return set_error(-1, "taehv_decode: T too large");
@@ -660,76 +686,46 @@ extern "C" int rtv_taehv_decode(const rtv_taehv_weights* wt, const void* z, int 
   char* A = (char*)arena;
   auto at = [&](size_t off) { return (uint16_t*)(A + off); };
   const uint16_t* zeros = at(L.zeros);
-  if (hipMemsetAsync(A + L.zeros, 0, 256, stream) != hipSuccess) return set_error(-1, "taehv_decode: memset failed");
-  if (first && hipMemsetAsync(A, 0, L.state_bytes, stream) != hipSuccess) return set_error(-1, "taehv_decode: memset failed");
-
-  auto conv = [&](const void* in, const void* wts, const void* bias, const void* res, void* out, int Tn, int H, int W, int Cin,
-                  int Cout, int kt, int ups, int n_split, int relu, int head) {
-    tae::ConvParams p{};
-    p.in = (const uint16_t*)in;
-    p.w = (const uint16_t*)wts;
-    p.bias = (const uint16_t*)bias;
-    p.residual = (const uint16_t*)res;
-    p.out = out;
-    p.zeros = zeros;
-    p.T = Tn;
-    p.H = H;
-    p.W = W;
-    p.Cin = Cin;
-    p.Cout = Cout;
-    p.kt = kt;
-    p.ups = ups;
-    p.n_split = n_split;
-    p.relu = relu;
-    return tae::launch_conv(p, head, stream);
-  };
+  TAE_TRY(tae::zero_fill(A, L, first, "taehv_decode", stream));
 
   // decoder.0 (Clamp) + layout, decoder.1 / 2: conv 16 -> 256 + bias, ReLU -> slices 1..T of the first MemBlock's concat buffer
   {
-    TAE_TRY(tae::launch_prep(z, T, h * w, at(L.x0), stream));
-    const size_t sl = (size_t)h * w * 256;
-    TAE_TRY(conv(at(L.x0), wt->conv_in.w, wt->conv_in.b, nullptr, at(L.cat[0][0]) + sl, T, h, w, 32, 256, 1, 0, 0, 1, 0));
+    TAE_TRY(tae::launch_prep(z, T, h * w, at(L.pre), stream));
+    tae::ConvParams p = tae::make_params(at(L.pre), wt->conv_in, at(L.st[0].cat[0]) + L.st[0].slice(), zeros, T, h, w, 32, 256);
+    p.relu = 1;
+    TAE_TRY(tae::launch_layer(p, tae::PLAIN, stream));
   }
-  uint16_t* cur = nullptr;
-  int F = T;
   for (int s = 0; s < 3; ++s) {
-    const int C = tae::kStageC[s], H = h << s, W = w << s;
-    const size_t sl = (size_t)H * W * C;
-    F = s < 2 ? T : 2 * T;
-    cur = at(L.cat[s][0]);
-    for (int b = 0; b < 3; ++b) {
-      const int k = s * 3 + b;
-      const rtv_vae_conv* mb = wt->mem[k];
-      uint16_t* nxt = at(L.cat[s][(b + 1) & 1]);
-      uint16_t* state = at(L.state[k]);
-      // [x_{t-1} | x_t] window: slice 0 = the input of the previous frame (carried across calls)
-      if (hipMemcpyAsync(cur, state, sl * 2, hipMemcpyDeviceToDevice, stream) != hipSuccess)
-        return set_error(-1, "taehv_decode: copy failed");
-      TAE_TRY(conv(cur, mb[0].w, mb[0].b, nullptr, at(L.tmp[s][0]), F, H, W, C, C, 2, 0, 0, 1, 0));
-      if (hipMemcpyAsync(state, cur + (size_t)F * sl, sl * 2, hipMemcpyDeviceToDevice, stream) != hipSuccess)
-        return set_error(-1, "taehv_decode: copy failed");
-      TAE_TRY(conv(at(L.tmp[s][0]), mb[1].w, mb[1].b, nullptr, at(L.tmp[s][1]), F, H, W, C, C, 1, 0, 0, 1, 0));
-      TAE_TRY(conv(at(L.tmp[s][1]), mb[2].w, mb[2].b, cur + sl, nxt + sl, F, H, W, C, C, 1, 0, 0, 1, 0));
-      cur = nxt;
-    }
+    const tae::Stage& g = L.st[s];
+    TAE_TRY(tae::run_memblocks(A, g, wt->mem + 3 * s, zeros, "taehv_decode", stream));
     if (s < 2) {   // decoder.{6,7,8} / {12,13,14}: up 2x, TGrow folded into the conv -> slices 1.. of the next stage's buffer
-      const size_t sl2 = (size_t)(2 * H) * (2 * W) * tae::kStageC[s + 1];
-      TAE_TRY(conv(cur + sl, wt->up[s], nullptr, nullptr, at(L.cat[s + 1][0]) + sl2, F, 2 * H, 2 * W, C, 128, 1, 1,
-                   s == 0 ? 0 : 64, 0, 0));
+      const tae::Stage& n = L.st[s + 1];
+      tae::ConvParams p = tae::make_params(at(g.cat[1]) + g.slice(), {wt->up[s], nullptr}, at(n.cat[0]) + n.slice(), zeros, g.F,
+                                           n.H, n.W, g.C, 128);
+      p.ups = 1;
+      p.n_split = s == 0 ? 0 : 64;
+      TAE_TRY(tae::launch_layer(p, tae::PLAIN, stream));
     }
   }
   // decoder.{18..22}: up 2x + TGrow(64, 2) folded into conv 64 -> 64, ReLU, conv 64 -> 3, one 64-channel frame j (= output frames
   // 2j, 2j + 1) at a time; on a stream's first call the output frames 0..2 are TAEHV's warm-up frames and are not produced
   {
+    const tae::Stage& g = L.st[2];
     const int H = 8 * h, W = 8 * w;
-    const size_t sl = (size_t)(4 * h) * (4 * w) * 64, fsl = (size_t)H * W * 64;
+    const size_t fsl = (size_t)H * W * 64;
     const int skip = first ? 3 : 0;
-    for (int j = 0; j < F; ++j) {
+    for (int j = 0; j < g.F; ++j) {
       const int lo = 2 * j > skip ? 2 * j : skip;
       if (lo >= 2 * j + 2) continue;
-      TAE_TRY(conv(cur + (size_t)(1 + j) * sl, wt->up[2], nullptr, nullptr, at(L.fin), 1, H, W, 64, 128, 1, 1, 64, 1, 0));
-      TAE_TRY(conv(at(L.fin) + (size_t)(lo - 2 * j) * fsl, wt->head.w, wt->head.b, nullptr,
-                   (float*)pixels + (size_t)(lo - skip) * 3 * H * W, 2 * j + 2 - lo, H, W, 64, 8, 1, 0, 0, 0, 1));
+      tae::ConvParams p = tae::make_params(at(g.cat[1]) + (size_t)(1 + j) * g.slice(), {wt->up[2], nullptr}, at(L.post), zeros, 1, H,
+                                           W, 64, 128);
+      p.ups = 1;
+      p.n_split = 64;
+      p.relu = 1;
+      TAE_TRY(tae::launch_layer(p, tae::PLAIN, stream));
+      p = tae::make_params(at(L.post) + (size_t)(lo - 2 * j) * fsl, wt->head, (float*)pixels + (size_t)(lo - skip) * 3 * H * W, zeros,
+                           2 * j + 2 - lo, H, W, 64, 8);
+      TAE_TRY(tae::launch_layer(p, tae::RGB_HEAD, stream));
     }
   }
   return 0;
@@ -737,54 +733,29 @@ extern "C" int rtv_taehv_decode(const rtv_taehv_weights* wt, const void* z, int 
 
 // ---------------------------------------------------------------- encoder C ABI
 extern "C" size_t rtv_taehv_enc_arena_bytes(int H, int W, int t_max) {
-  tae::EncLayout L;
+  tae::Layout L;
   if (t_max <= 0 || !tae::make_enc_layout(H, W, t_max, &L)) return 0;
   return L.total;
 }
 
 extern "C" int rtv_taehv_enc_state_slot(int H, int W, int slot, size_t* offset, int* C, int* h, int* w) {
-  tae::EncLayout L;
+  tae::Layout L;
   if (!tae::make_enc_layout(H, W, 0, &L)) return set_error(-1, "taehv_enc: frame size must be positive multiples of 8");
-  if (slot < 0 || slot >= 9) return set_error(-1, "taehv_enc: state slot must be 0..8");
-  const int s = slot / 3;
-  if (offset) *offset = L.state[slot];
-  if (C) *C = 64;
-  if (h) *h = H >> (s + 1);
-  if (w) *w = W >> (s + 1);
-  return 0;
+  return tae::state_slot(L, "taehv_enc", slot, offset, C, h, w);
 }
 
 extern "C" int rtv_taehv_enc_conv(const void* in, const void* w, const void* bias, void* out, int form, int T, int H, int W,
                                   int kt, int n_total, int n0, const void* zeros, rtv_stream_t stream) {
   if (form == 0) {
-    tae::FirstParams f{};
-    f.frames = (const uint16_t*)in;
-    f.w = (const uint16_t*)w;
-    f.bias = (const uint16_t*)bias;
-    f.out = (uint16_t*)out;
-    f.T_total = n_total;
-    f.t0 = n0;
-    f.T = T;
-    f.H = H;
-    f.W = W;
+    const tae::FirstParams f{(const uint16_t*)in, (const uint16_t*)w, (const uint16_t*)bias, (uint16_t*)out, n_total, n0, T, H, W, 0};
     return tae::launch_enc_first(f, (hipStream_t)stream);
   }
   if (form != 1 && form != 2) return set_error(-1, "taehv_enc_conv: form must be 0 (first), 1 (stride 2) or 2 (head)");
-  tae::ConvParams p{};
-  p.in = (const uint16_t*)in;
-  p.w = (const uint16_t*)w;
-  p.bias = (const uint16_t*)bias;
-  p.out = out;
-  p.zeros = (const uint16_t*)zeros;
-  p.T = T;
-  p.H = H;
-  p.W = W;
-  p.Cin = 64;
-  p.Cout = form == 2 ? 16 : 64;
+  tae::ConvParams p = tae::make_params(in, {w, bias}, out, zeros, T, H, W, 64, form == 2 ? 16 : 64);
   p.kt = kt;
   p.out_T = n_total;
   p.out_j = n0;
-  return tae::launch_enc_conv(p, form == 2, (hipStream_t)stream);
+  return tae::launch_layer(p, form == 2 ? tae::LATENT_HEAD : tae::DOWN, (hipStream_t)stream);
 }
 
 extern "C" int rtv_taehv_encode(const rtv_taehv_enc_weights* wt, const void* frames, int T_total, int t0, int tn, int H, int W,
@@ -795,111 +766,44 @@ extern "C" int rtv_taehv_encode(const rtv_taehv_enc_weights* wt, const void* fra
   if (t0 < 0 || t0 + tn > T_total) return set_error(-1, "taehv_encode: frames t0 .. t0 + tn outside the clip");
   if (j < 0 || j + tn / 4 > T_out) return set_error(-1, "taehv_encode: latent frames outside the output tensor");
   if (((uintptr_t)arena) & 255) return set_error(-1, "taehv_encode: arena must be 256-byte aligned");
-  tae::EncLayout L;
+  tae::Layout L;
   if (!tae::make_enc_layout(H, W, tn, &L)) return set_error(-1, "taehv_encode: H and W must be multiples of 8 (or tn too large)");
   if (arena_bytes < L.total) return set_error(-1, "taehv_encode: arena too small for tn (see rtv_taehv_enc_arena_bytes)");
   hipStream_t stream = (hipStream_t)stream_;
   char* A = (char*)arena;
   auto at = [&](size_t off) { return (uint16_t*)(A + off); };
   const uint16_t* zeros = at(L.zeros);
-  if (hipMemsetAsync(A + L.zeros, 0, 256, stream) != hipSuccess) return set_error(-1, "taehv_encode: memset failed");
-  if (first && hipMemsetAsync(A, 0, L.state_bytes, stream) != hipSuccess) return set_error(-1, "taehv_encode: memset failed");
-
-  auto conv = [&](const void* in, const rtv_vae_conv& c, const void* res, void* out, int Tn, int Hh, int Ww, int kt) {
-    tae::ConvParams p{};
-    p.in = (const uint16_t*)in;
-    p.w = (const uint16_t*)c.w;
-    p.bias = (const uint16_t*)c.b;
-    p.residual = (const uint16_t*)res;
-    p.out = out;
-    p.zeros = zeros;
-    p.T = Tn;
-    p.H = Hh;
-    p.W = Ww;
-    p.Cin = 64;
-    p.Cout = 64;
-    p.kt = kt;
-    p.relu = 1;
-    return tae::launch_conv(p, 0, stream);
-  };
+  TAE_TRY(tae::zero_fill(A, L, first, "taehv_encode", stream));
+  // a folded TPool + stride-2 conv onto the output grid (Hh, Ww); kt = the TPool's time stride
   auto down = [&](const void* in, const void* wts, void* out, int Tn, int Hh, int Ww, int kt) {
-    tae::ConvParams p{};
-    p.in = (const uint16_t*)in;
-    p.w = (const uint16_t*)wts;
-    p.out = out;
-    p.zeros = zeros;
-    p.T = Tn;
-    p.H = Hh;
-    p.W = Ww;
-    p.Cin = 64;
-    p.Cout = 64;
+    tae::ConvParams p = tae::make_params(in, {wts, nullptr}, out, zeros, Tn, Hh, Ww, 64, 64);
     p.kt = kt;
-    return tae::launch_enc_conv(p, 0, stream);
+    return tae::launch_layer(p, tae::DOWN, stream);
   };
 
   // encoder.{0..3}: conv 3 -> 64 + ReLU on a frame pair, then TPool(64, 2) + stride-2 conv as one layer -> slice 1 + q of the
   // first MemBlock's concat buffer at H/2
-  {
-    const size_t sl = (size_t)(H / 2) * (W / 2) * 64;
-    for (int q = 0; q < tn / 2; ++q) {
-      tae::FirstParams f{};
-      f.frames = (const uint16_t*)frames;
-      f.w = (const uint16_t*)wt->conv_in.w;
-      f.bias = (const uint16_t*)wt->conv_in.b;
-      f.out = at(L.full);
-      f.T_total = T_total;
-      f.t0 = t0 + 2 * q;
-      f.T = 2;
-      f.H = H;
-      f.W = W;
-      TAE_TRY(tae::launch_enc_first(f, stream));
-      TAE_TRY(down(at(L.full), wt->down[0], at(L.cat[0][0]) + (size_t)(1 + q) * sl, 1, H / 2, W / 2, 2));
-    }
+  for (int q = 0; q < tn / 2; ++q) {
+    const tae::FirstParams f{(const uint16_t*)frames, (const uint16_t*)wt->conv_in.w, (const uint16_t*)wt->conv_in.b, at(L.pre),
+                             T_total, t0 + 2 * q, 2, H, W, 0};
+    TAE_TRY(tae::launch_enc_first(f, stream));
+    TAE_TRY(down(at(L.pre), wt->down[0], at(L.st[0].cat[0]) + (size_t)(1 + q) * L.st[0].slice(), 1, H / 2, W / 2, 2));
   }
-  uint16_t* cur = nullptr;
   for (int s = 0; s < 3; ++s) {
-    const int Hs = H >> (s + 1), Ws = W >> (s + 1);
-    const int F = s == 0 ? tn / 2 : tn / 4;
-    const size_t sl = (size_t)Hs * Ws * 64;
-    cur = at(L.cat[s][0]);
-    for (int b = 0; b < 3; ++b) {
-      const int k = s * 3 + b;
-      const rtv_vae_conv* mb = wt->mem[k];
-      uint16_t* nxt = at(L.cat[s][(b + 1) & 1]);
-      uint16_t* state = at(L.state[k]);
-      // [x_{t-1} | x_t] window: slice 0 = the block's input at the previous frame (carried across calls)
-      if (hipMemcpyAsync(cur, state, sl * 2, hipMemcpyDeviceToDevice, stream) != hipSuccess)
-        return set_error(-1, "taehv_encode: copy failed");
-      TAE_TRY(conv(cur, mb[0], nullptr, at(L.tmp[s][0]), F, Hs, Ws, 2));
-      if (hipMemcpyAsync(state, cur + (size_t)F * sl, sl * 2, hipMemcpyDeviceToDevice, stream) != hipSuccess)
-        return set_error(-1, "taehv_encode: copy failed");
-      TAE_TRY(conv(at(L.tmp[s][0]), mb[1], nullptr, at(L.tmp[s][1]), F, Hs, Ws, 1));
-      TAE_TRY(conv(at(L.tmp[s][1]), mb[2], cur + sl, nxt + sl, F, Hs, Ws, 1));
-      cur = nxt;
-    }
+    const tae::Stage& g = L.st[s];
+    TAE_TRY(tae::run_memblocks(A, g, wt->mem + 3 * s, zeros, "taehv_encode", stream));
     if (s < 2) {   // encoder.{7,8}: TPool(64, 2) + stride-2 conv; encoder.{12,13}: TPool(64, 1) + stride-2 conv
-      const size_t sl2 = (size_t)(Hs / 2) * (Ws / 2) * 64;
-      TAE_TRY(down(cur + sl, wt->down[s + 1], at(L.cat[s + 1][0]) + sl2, tn / 4, Hs / 2, Ws / 2, s == 0 ? 2 : 1));
+      const tae::Stage& n = L.st[s + 1];
+      TAE_TRY(down(at(g.cat[1]) + g.slice(), wt->down[s + 1], at(n.cat[0]) + n.slice(), n.F, n.H, n.W, s == 0 ? 2 : 1));
     }
   }
   // encoder.17: conv 64 -> 16 + bias -> latent frames j .. j + tn / 4 of the planar output
   {
-    const size_t sl = (size_t)(H / 8) * (W / 8) * 64;
-    tae::ConvParams p{};
-    p.in = cur + sl;
-    p.w = (const uint16_t*)wt->head.w;
-    p.bias = (const uint16_t*)wt->head.b;
-    p.out = latents;
-    p.zeros = zeros;
-    p.T = tn / 4;
-    p.H = H / 8;
-    p.W = W / 8;
-    p.Cin = 64;
-    p.Cout = 16;
-    p.kt = 1;
+    const tae::Stage& g = L.st[2];
+    tae::ConvParams p = tae::make_params(at(g.cat[1]) + g.slice(), wt->head, latents, zeros, g.F, g.H, g.W, 64, 16);
     p.out_T = T_out;
     p.out_j = j;
-    TAE_TRY(tae::launch_enc_conv(p, 1, stream));
+    TAE_TRY(tae::launch_layer(p, tae::LATENT_HEAD, stream));
   }
   return 0;
 }

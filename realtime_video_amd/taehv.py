@@ -15,6 +15,7 @@ previous frame of its rate) as [1, C, H, W] views into the stream's arena, updat
 is the call contract of `VAEEncoderWrapper`, so `encode_video_latent(vae=TAEHVEncoder, ...)` works unchanged; see the class.
 """
 import ctypes
+import functools
 import hashlib
 import math
 
@@ -30,36 +31,45 @@ MEM_CHANNELS = (256, 256, 256, 128, 128, 128, 64, 64, 64)
 TGROWS = ((7, 8, 256, 128, 1), (13, 14, 128, 64, 2), (19, 20, 64, 64, 2))   # (TGrow idx, conv idx, C in, C out, stride)
 WARMUP_FRAMES = 3                                  # TAEHV.frames_to_trim with the default decoder_time_upscale
 
+ENC_MEMBLOCKS = (4, 5, 6, 9, 10, 11, 14, 15, 16)  # encoder indices of the nine MemBlocks (64 channels each)
+TPOOLS = ((2, 3, 2), (7, 8, 2), (12, 13, 1))      # (TPool idx, stride-2 conv idx, time stride)
+
 
 class _TaehvWeights(ctypes.Structure):
     _fields_ = [("conv_in", _Conv), ("mem", (_Conv * 3) * 9), ("up", c_vp * 3), ("head", _Conv)]
-
-
-ENC_MEMBLOCKS = (4, 5, 6, 9, 10, 11, 14, 15, 16)  # encoder indices of the nine MemBlocks (64 channels each)
-TPOOLS = ((2, 3, 2), (7, 8, 2), (12, 13, 1))      # (TPool idx, stride-2 conv idx, time stride)
 
 
 class _TaehvEncWeights(ctypes.Structure):
     _fields_ = [("conv_in", _Conv), ("down", c_vp * 3), ("mem", (_Conv * 3) * 9), ("head", _Conv)]
 
 
+_SLOT_SIG = [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_size_t)] + [ctypes.POINTER(ctypes.c_int)] * 3
 _lib.EXTRA_SIGNATURES.update({
-    "rtv_taehv_state_slot": [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_size_t)] + [ctypes.POINTER(ctypes.c_int)] * 3,
+    "rtv_taehv_state_slot": _SLOT_SIG,
     "rtv_taehv_decode": [ctypes.POINTER(_TaehvWeights), c_vp] + [ctypes.c_int] * 4 + [c_vp, ctypes.c_size_t, c_vp, c_vp],
     "rtv_taehv_conv": [c_vp] * 5 + [ctypes.c_int] * 10 + [c_vp, c_vp],
     "rtv_taehv_prep": [c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp],                        # used by the tests
-    "rtv_taehv_enc_state_slot": [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_size_t)] + [ctypes.POINTER(ctypes.c_int)] * 3,
+    "rtv_taehv_enc_state_slot": _SLOT_SIG,
     "rtv_taehv_encode": [ctypes.POINTER(_TaehvEncWeights), c_vp] + [ctypes.c_int] * 6 + [c_vp, ctypes.c_size_t, c_vp,
                                                                                       ctypes.c_int, ctypes.c_int, c_vp],
     "rtv_taehv_enc_conv": [c_vp] * 4 + [ctypes.c_int] * 7 + [c_vp, c_vp],
 })
 
 
+@functools.lru_cache(None)
+def _arena_fn(name):
+    """`size_t name(int, int, int)` of the library, its signature registered once."""
+    fn = getattr(_lib.load(), name)
+    fn.restype, fn.argtypes = ctypes.c_size_t, [ctypes.c_int] * 3
+    return fn
+
+
 def arena_bytes(h, w, t_max):
-    lib = _lib.load()
-    lib.rtv_taehv_arena_bytes.restype = ctypes.c_size_t
-    lib.rtv_taehv_arena_bytes.argtypes = [ctypes.c_int] * 3
-    return int(lib.rtv_taehv_arena_bytes(h, w, t_max))
+    return int(_arena_fn("rtv_taehv_arena_bytes")(h, w, t_max))
+
+
+def enc_arena_bytes(H, W, t_max):
+    return int(_arena_fn("rtv_taehv_enc_arena_bytes")(H, W, t_max))
 
 
 def fold_tgrow(tgrow_w, conv_w, stride):
@@ -71,13 +81,6 @@ def fold_tgrow(tgrow_w, conv_w, stride):
     C = tg.shape[1]
     parts = [torch.einsum("okyx,kc->ocyx", cw, tg[s * C:(s + 1) * C]) for s in range(stride)]
     return torch.cat(parts, 0)
-
-
-def enc_arena_bytes(H, W, t_max):
-    lib = _lib.load()
-    lib.rtv_taehv_enc_arena_bytes.restype = ctypes.c_size_t
-    lib.rtv_taehv_enc_arena_bytes.argtypes = [ctypes.c_int] * 3
-    return int(lib.rtv_taehv_enc_arena_bytes(H, W, t_max))
 
 
 def fold_tpool(tpool_w, conv_w, stride):
@@ -92,12 +95,18 @@ def fold_tpool(tpool_w, conv_w, stride):
     return parts[0] if stride == 1 else torch.stack(parts, 2)
 
 
-class TAEHVDecoder:
+class _TAEHVCodec:
+    """What the two halves share: the state-dict loader with the MemBlock repack, the synthetic weights, and a stream's arena
+    with its nine state views.  A subclass gives
+        NAME, HALF / OTHER_HALF   its name in error texts; the state-dict prefix it loads / ignores
+        WEIGHTS, MEM              the C struct of its weights; (module index, channels) of its nine MemBlocks
+        GAINS, BIAS_MEANS         random_state_dict's exceptions by tensor name
+        SLOT_FN                   the library's state-slot function of its arena
+        state_dict_spec(), _pack_layers(), _arena_bytes(), forward()"""
     z_dim = 16
+    BIAS_MEANS = {}
 
-    def __init__(self, device="cuda", decoder_time_upscale=(True, True), decoder_space_upscale=(True, True, True)):
-        if tuple(decoder_time_upscale) != (True, True) or tuple(decoder_space_upscale) != (True, True, True):
-            raise NotImplementedError("TAEHVDecoder: only the default decoder_time_upscale / decoder_space_upscale")
+    def __init__(self, device="cuda"):
         self.device = torch.device(device)
         self._t = {}
         self._w = None
@@ -113,6 +122,150 @@ class TAEHVDecoder:
         return self
 
     # ------------------------------------------------------------------ weights
+    def _checkpoint_view(self, sd):
+        return sd
+
+    def load_state_dict(self, sd, strict=True):
+        """Reference key names (`decoder.{i}...` / `encoder.{i}...`); the keys of the other half (a real taew2_1.pth carries
+        both) are ignored."""
+        who = f"{type(self).__name__}.load_state_dict"
+        spec = dict(self.state_dict_spec())
+        sd = self._checkpoint_view({k: v for k, v in sd.items() if not k.startswith(self.OTHER_HALF)})
+        missing = [k for k in spec if k not in sd]
+        unexpected = [k for k in sd if k not in spec]
+        if strict and (missing or unexpected):
+            raise KeyError(f"{who}: missing {missing}, unexpected {unexpected}")
+        if missing:
+            raise KeyError(f"{who}: missing {missing}")
+        for k, shape in spec.items():
+            if tuple(sd[k].shape) != shape:
+                raise ValueError(f"{who}: {k} has shape {tuple(sd[k].shape)}, expected {shape}")
+        dev, f16 = self.device, torch.float16
+        t = {}
+        W = self.WEIGHTS()
+
+        def put(name, x):
+            t[name] = x.to(dev).contiguous()
+            return t[name].data_ptr()
+
+        def conv(dst, wname, w, b, cin_pad=None, cout_pad=None):
+            dst.w = put(wname + ".w", pack_conv_weight(w, cin_pad, cout_pad))
+            b = b.detach().to(f16).reshape(-1)
+            if cout_pad and cout_pad > b.numel():
+                b = torch.cat([b, b.new_zeros(cout_pad - b.numel())])
+            dst.b = put(wname + ".b", b)
+
+        for k, (idx, C) in enumerate(self.MEM):
+            pre = f"{self.HALF}{idx}.conv"
+            w0 = sd[pre + ".0.weight"]
+            # cat([x_t, x_{t-1}]) input channels -> time taps [x_{t-1} | x_t] of a 2-slice conv
+            conv(W.mem[k][0], pre + ".0", torch.stack([w0[:, C:], w0[:, :C]], dim=2), sd[pre + ".0.bias"])
+            conv(W.mem[k][1], pre + ".2", sd[pre + ".2.weight"], sd[pre + ".2.bias"])
+            conv(W.mem[k][2], pre + ".4", sd[pre + ".4.weight"], sd[pre + ".4.bias"])
+        self._pack_layers(sd, W, put, conv)
+        self._t, self._w = t, W
+        return [], []
+
+    @classmethod
+    def random_state_dict(cls, seed=0):
+        """Deterministic synthetic weights (CPU generator, float32) that keep the signal alive through the layers: He-scaled
+        convs in front of a ReLU, each MemBlock's last conv scaled down (its branch adds to the identity), unit gain for
+        TGrow / TPool (no ReLU behind them), small biases; cls.GAINS / cls.BIAS_MEANS hold the class's exceptions."""
+        g = torch.Generator().manual_seed(seed)
+        sd = {}
+        for name, shape in cls.state_dict_spec():
+            if name.endswith(".bias"):
+                sd[name] = 0.02 * torch.randn(shape, generator=g)
+                if name in cls.BIAS_MEANS:
+                    sd[name] = cls.BIAS_MEANS[name] + sd[name]
+                continue
+            fan_in = math.prod(shape[1:])
+            gain = math.sqrt(2.0)
+            if name.endswith(".conv.4.weight"):
+                gain = 0.3
+            elif ".conv.weight" in name:
+                gain = 1.0
+            elif name in cls.GAINS:
+                gain = cls.GAINS[name]
+            sd[name] = torch.randn(shape, generator=g) * (gain / math.sqrt(fan_in))
+        return sd
+
+    @classmethod
+    def checksum(cls, sd):
+        """sha256 over the float32 bytes of the class's tensors in state_dict_spec order."""
+        h = hashlib.sha256()
+        for name, _ in cls.state_dict_spec():
+            h.update(sd[name].detach().float().contiguous().cpu().numpy().tobytes())
+        return h.hexdigest()
+
+    def init_random_weights(self, seed=0):
+        self.load_state_dict(self.random_state_dict(seed))
+        return self
+
+    # ------------------------------------------------------------------ arena / state views
+    def _new_arena(self, size, t_max):
+        n = self._arena_bytes(*size, t_max)
+        if n == 0:
+            raise ValueError(f"{self.NAME}: unsupported size {size[0]}x{size[1]} / {t_max} frames per call")
+        arena = torch.empty(n + 256, dtype=torch.uint8, device=self.device)   # the state is zeroed by a stream's first call
+        return arena, (-arena.data_ptr()) % 256
+
+    def _state_views(self, arena, base, size):
+        views = []
+        off, C, H, W = ctypes.c_size_t(0), ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+        for i in range(9):
+            _lib.call(self.SLOT_FN, *size, i, ctypes.byref(off), ctypes.byref(C), ctypes.byref(H), ctypes.byref(W))
+            start = base + off.value
+            v = arena[start:start + C.value * H.value * W.value * 2].view(torch.float16).view(H.value, W.value, C.value)
+            views.append(v.permute(2, 0, 1).unsqueeze(0))     # [1, C, H, W] (channels-last in memory)
+        self._arenas.register(views, arena, base, size)
+        return views
+
+    def _acquire(self, views, size, t_max, need):
+        """(arena, base, views) of a stream of frame size `size` for a call that needs `need` bytes.  views None: a new stream,
+        on the arena of a dropped stream of this size if there is one that is large enough, else on a new one for calls of
+        up to t_max frames.  Otherwise the stream whose state views these are; a call longer than its arena was sized for
+        moves the state to a larger one."""
+        if views is None:
+            ent = self._arenas.recycle(size)
+            if ent is None or ent[0].numel() - ent[1] < need:
+                ent = self._new_arena(size, t_max)
+            arena, base = ent
+            return arena, base, self._state_views(arena, base, size)
+        arena, base = self._arenas.lookup(views, size, lambda: self._new_arena(size, t_max)[0],
+                                          lambda a, b: self._state_views(a, b, size))
+        if arena.numel() - base < need:
+            self._arenas.forget(views)
+            arena, base = self._new_arena(size, t_max)
+            old, views = views, self._state_views(arena, base, size)
+            for dst, src in zip(views, old):
+                dst.copy_(src)
+        return arena, base, views
+
+    def _check_input(self, z):
+        if self._w is None:
+            raise RuntimeError(f"{self.NAME}: weights not loaded")
+        if not z.is_cuda:
+            raise RuntimeError(f"realtime_video_amd.{type(self).__name__} needs GPU tensors (no CPU fallback)")
+
+    def __call__(self, *a, **k):
+        return self.forward(*a, **k)
+
+
+class TAEHVDecoder(_TAEHVCodec):
+    NAME, HALF, OTHER_HALF = "TAEHV decoder", "decoder.", "encoder."
+    WEIGHTS, MEM, SLOT_FN = _TaehvWeights, tuple(zip(MEMBLOCKS, MEM_CHANNELS)), "rtv_taehv_state_slot"
+    # the conv behind a TGrow: no ReLU in between / after (decoder.20 has one); a head that maps to about 0.5 +- 0.1 (std), inside
+    # TAEHV's [0, 1]
+    GAINS = {"decoder.8.weight": 1.0, "decoder.14.weight": 1.0, "decoder.22.weight": 0.13}
+    BIAS_MEANS = {"decoder.22.bias": 0.5}
+    _arena_bytes = staticmethod(arena_bytes)
+
+    def __init__(self, device="cuda", decoder_time_upscale=(True, True), decoder_space_upscale=(True, True, True)):
+        if tuple(decoder_time_upscale) != (True, True) or tuple(decoder_space_upscale) != (True, True, True):
+            raise NotImplementedError("TAEHVDecoder: only the default decoder_time_upscale / decoder_space_upscale")
+        super().__init__(device)
+
     @staticmethod
     def state_dict_spec():
         """(name, shape) of every tensor of the reference module's `decoder` state_dict, in module order."""
@@ -136,114 +289,17 @@ class TAEHVDecoder:
                 sd[key] = sd[key][-cin * stride:]
         return sd
 
-    def load_state_dict(self, sd, strict=True):
-        """Reference key names (`decoder.{i}...`); `encoder.*` keys (a real taew2_1.pth carries both) are ignored."""
-        spec = dict(self.state_dict_spec())
-        sd = self.patch_tgrow_layers({k: v for k, v in sd.items() if not k.startswith("encoder.")})
-        missing = [k for k in spec if k not in sd]
-        unexpected = [k for k in sd if k not in spec]
-        if strict and (missing or unexpected):
-            raise KeyError(f"TAEHVDecoder.load_state_dict: missing {missing}, unexpected {unexpected}")
-        if missing:
-            raise KeyError(f"TAEHVDecoder.load_state_dict: missing {missing}")
-        for k, shape in spec.items():
-            if tuple(sd[k].shape) != shape:
-                raise ValueError(f"TAEHVDecoder.load_state_dict: {k} has shape {tuple(sd[k].shape)}, expected {shape}")
-        dev, f16 = self.device, torch.float16
-        t = {}
-        W = _TaehvWeights()
+    _checkpoint_view = patch_tgrow_layers
 
-        def put(name, x):
-            t[name] = x.to(dev).contiguous()
-            return t[name].data_ptr()
-
-        def conv(dst, wname, w, b, cin_pad=None, cout_pad=None):
-            dst.w = put(wname + ".w", pack_conv_weight(w, cin_pad, cout_pad))
-            b = b.detach().to(f16).reshape(-1)
-            if cout_pad and cout_pad > b.numel():
-                b = torch.cat([b, b.new_zeros(cout_pad - b.numel())])
-            dst.b = put(wname + ".b", b)
-
+    @staticmethod
+    def _pack_layers(sd, W, put, conv):
         conv(W.conv_in, "decoder.1", sd["decoder.1.weight"], sd["decoder.1.bias"], cin_pad=32)
-        for k, (idx, C) in enumerate(zip(MEMBLOCKS, MEM_CHANNELS)):
-            pre = f"decoder.{idx}.conv"
-            w0 = sd[pre + ".0.weight"]
-            # cat([x_t, x_{t-1}]) input channels -> time taps [x_{t-1} | x_t] of a 2-slice conv
-            conv(W.mem[k][0], pre + ".0", torch.stack([w0[:, C:], w0[:, :C]], dim=2), sd[pre + ".0.bias"])
-            conv(W.mem[k][1], pre + ".2", sd[pre + ".2.weight"], sd[pre + ".2.bias"])
-            conv(W.mem[k][2], pre + ".4", sd[pre + ".4.weight"], sd[pre + ".4.bias"])
         for s, (tg, cv, _cin, _cout, stride) in enumerate(TGROWS):
             W.up[s] = put(f"up{s}", pack_conv_weight(fold_tgrow(sd[f"decoder.{tg}.conv.weight"], sd[f"decoder.{cv}.weight"], stride)))
         conv(W.head, "decoder.22", sd["decoder.22.weight"], sd["decoder.22.bias"], cout_pad=8)
-        self._t, self._w = t, W
-        return [], []
 
-    @classmethod
-    def random_state_dict(cls, seed=0):
-        """Deterministic synthetic decoder weights (CPU generator, float32) that keep the signal alive through the 23 layers:
-        He-scaled convs in front of a ReLU, variance-preserving transitions, each MemBlock's last conv scaled down (its
-        branch adds to the identity), small biases, and a head that maps to about 0.5 +- 0.1 (std) (inside TAEHV's [0, 1])."""
-        g = torch.Generator().manual_seed(seed)
-        sd = {}
-        for name, shape in cls.state_dict_spec():
-            if name.endswith(".bias"):
-                sd[name] = 0.5 + 0.02 * torch.randn(shape, generator=g) if name == "decoder.22.bias" else 0.02 * torch.randn(shape, generator=g)
-                continue
-            fan_in = math.prod(shape[1:])
-            gain = math.sqrt(2.0)
-            if name.endswith(".conv.4.weight"):
-                gain = 0.3
-            elif ".conv.weight" in name or name in ("decoder.8.weight", "decoder.14.weight"):
-                gain = 1.0             # TGrow and the conv behind it: no ReLU in between / after
-            elif name == "decoder.22.weight":
-                gain = 0.13
-            sd[name] = torch.randn(shape, generator=g) * (gain / math.sqrt(fan_in))
-        return sd
-
-    @staticmethod
-    def checksum(sd):
-        """sha256 over the float32 bytes of the decoder tensors in state_dict_spec order."""
-        h = hashlib.sha256()
-        for name, _ in TAEHVDecoder.state_dict_spec():
-            h.update(sd[name].detach().float().contiguous().cpu().numpy().tobytes())
-        return h.hexdigest()
-
-    def init_random_weights(self, seed=0):
-        self.load_state_dict(self.random_state_dict(seed))
-        return self
-
-    # ------------------------------------------------------------------ arena / state views
-    def _new_arena(self, h, w, t_max):
-        n = arena_bytes(h, w, t_max)
-        if n == 0:
-            raise ValueError(f"TAEHV decoder: unsupported latent size {h}x{w} / T {t_max}")
-        arena = torch.empty(n + 256, dtype=torch.uint8, device=self.device)   # the state is zeroed by a stream's first call
-        return arena, (-arena.data_ptr()) % 256
-
-    @staticmethod
-    def _slots(h, w):
-        out = []
-        off, C, H, Wd = ctypes.c_size_t(0), ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
-        for i in range(9):
-            _lib.call("rtv_taehv_state_slot", h, w, i, ctypes.byref(off), ctypes.byref(C), ctypes.byref(H), ctypes.byref(Wd))
-            out.append((off.value, C.value, H.value, Wd.value))
-        return out
-
-    def _state_views(self, arena, base, h, w):
-        views = []
-        for off, C, H, Wd in self._slots(h, w):
-            start = base + off
-            v = arena[start:start + C * H * Wd * 2].view(torch.float16).view(H, Wd, C)
-            views.append(v.permute(2, 0, 1).unsqueeze(0))     # [1, C, H, W] (channels-last in memory)
-        self._arenas.register(views, arena, base, (h, w))
-        return views
-
-    # ------------------------------------------------------------------ forward
     def forward(self, z, *state):
-        if self._w is None:
-            raise RuntimeError("TAEHV decoder: weights not loaded")
-        if not z.is_cuda:
-            raise RuntimeError("realtime_video_amd.TAEHVDecoder needs GPU tensors (no CPU fallback)")
+        self._check_input(z)
         B, T, C, h, w = z.shape
         if B != 1 or C != 16:
             raise NotImplementedError("TAEHV decoder: batch 1, 16 latent channels")
@@ -252,24 +308,7 @@ class TAEHVDecoder:
         need = arena_bytes(h, w, T)
         if need == 0:
             raise ValueError(f"TAEHV decoder: unsupported latent size {h}x{w} / T {T}")
-        t_max = max(T, 3)
-        if first:
-            ent = self._arenas.recycle((h, w))   # the arena of a dropped stream of this size, if any
-            if ent is None or ent[0].numel() - ent[1] < need:
-                ent = self._new_arena(h, w, t_max)
-            arena, base = ent
-            views = self._state_views(arena, base, h, w)
-        else:
-            views = list(state[:9])
-            arena, base = self._arenas.lookup(views, (h, w), lambda: self._new_arena(h, w, t_max)[0],
-                                              lambda a, b: self._state_views(a, b, h, w))
-            if arena.numel() - base < need:
-                # a longer call than this stream's arena was sized for: move the state to a larger one
-                self._arenas.forget(views)
-                arena, base = self._new_arena(h, w, t_max)
-                old, views = views, self._state_views(arena, base, h, w)
-                for dst, src in zip(views, old):
-                    dst.copy_(src)
+        arena, base, views = self._acquire(None if first else list(state[:9]), (h, w), max(T, 3), need)
         n_out = 4 * T - WARMUP_FRAMES if first else 4 * T
         pixels = torch.empty((n_out, 3, 8 * h, 8 * w), dtype=torch.float32, device=z.device)
         _lib.call("rtv_taehv_decode", ctypes.byref(self._w), c_vp(zz.data_ptr()), T, h, w, int(first),
@@ -277,10 +316,8 @@ class TAEHVDecoder:
                   c_vp(torch.cuda.current_stream().cuda_stream))
         return pixels.unsqueeze(0), views
 
-    __call__ = forward
 
-
-class TAEHVEncoder:
+class TAEHVEncoder(_TAEHVCodec):
     """The `encoder` of demo_utils/taehv.py:172-178 behind the call contract of `VAEEncoderWrapper`: preview grade, not the
     Wan encoder.  No latent mean / std scaling (taew2_1 works in the DiT's latent space, as TAEHVDecoder assumes).
 
@@ -291,25 +328,13 @@ class TAEHVEncoder:
 
     The returned cache is the nine MemBlock state slices ([1, 64, h, w] views into the stream's arena, updated in place by the
     next call).  Backed by `rtv_taehv_encode`; no CPU fallback."""
-    z_dim = 16
     GROUP = 12     # frames per rtv_taehv_encode call (sizes the arena: longer clips run in groups, bit-identical)
+    NAME, HALF, OTHER_HALF = "TAEHV encoder", "encoder.", "decoder."
+    WEIGHTS, MEM, SLOT_FN = _TaehvEncWeights, tuple((idx, 64) for idx in ENC_MEMBLOCKS), "rtv_taehv_enc_state_slot"
+    # the conv behind a TPool and the head: no ReLU in between / after
+    GAINS = {"encoder.3.weight": 1.0, "encoder.8.weight": 1.0, "encoder.13.weight": 1.0, "encoder.17.weight": 1.0}
+    _arena_bytes = staticmethod(enc_arena_bytes)
 
-    def __init__(self, device="cuda"):
-        self.device = torch.device(device)
-        self._t = {}
-        self._w = None
-        self._arenas = CacheArenas()
-
-    def eval(self):
-        return self
-
-    def to(self, *a, **k):
-        return self
-
-    def half(self):
-        return self
-
-    # ------------------------------------------------------------------ weights
     @staticmethod
     def state_dict_spec():
         """(name, shape) of every tensor of the reference module's `encoder` state_dict, in module order."""
@@ -323,104 +348,18 @@ class TAEHVEncoder:
         spec += [("encoder.17.weight", (16, 64, 3, 3)), ("encoder.17.bias", (16,))]
         return spec
 
-    def load_state_dict(self, sd, strict=True):
-        """Reference key names (`encoder.{i}...`); `decoder.*` keys (a real taew2_1.pth carries both) are ignored."""
-        spec = dict(self.state_dict_spec())
-        sd = {k: v for k, v in sd.items() if not k.startswith("decoder.")}
-        missing = [k for k in spec if k not in sd]
-        unexpected = [k for k in sd if k not in spec]
-        if strict and (missing or unexpected):
-            raise KeyError(f"TAEHVEncoder.load_state_dict: missing {missing}, unexpected {unexpected}")
-        if missing:
-            raise KeyError(f"TAEHVEncoder.load_state_dict: missing {missing}")
-        for k, shape in spec.items():
-            if tuple(sd[k].shape) != shape:
-                raise ValueError(f"TAEHVEncoder.load_state_dict: {k} has shape {tuple(sd[k].shape)}, expected {shape}")
-        dev, f16 = self.device, torch.float16
-        t = {}
-        W = _TaehvEncWeights()
-
-        def put(name, x):
-            t[name] = x.to(dev).contiguous()
-            return t[name].data_ptr()
-
-        def conv(dst, wname, w, b):
-            dst.w = put(wname + ".w", pack_conv_weight(w))
-            dst.b = put(wname + ".b", b.detach().to(f16).reshape(-1))
-
+    @staticmethod
+    def _pack_layers(sd, W, put, conv):
         # first conv: K order c * 9 + dy * 3 + dx (the weight's own flattening), 27 taps padded to the MFMA's 32
-        w0 = sd["encoder.0.weight"].detach().to(f16).reshape(64, 27)
+        w0 = sd["encoder.0.weight"].detach().to(torch.float16).reshape(64, 27)
         W.conv_in.w = put("encoder.0.w", torch.cat([w0, w0.new_zeros(64, 5)], 1))
-        W.conv_in.b = put("encoder.0.b", sd["encoder.0.bias"].detach().to(f16).reshape(-1))
+        W.conv_in.b = put("encoder.0.b", sd["encoder.0.bias"].detach().to(torch.float16).reshape(-1))
         for s, (tp, cv, stride) in enumerate(TPOOLS):
             W.down[s] = put(f"down{s}", pack_conv_weight(fold_tpool(sd[f"encoder.{tp}.conv.weight"], sd[f"encoder.{cv}.weight"], stride)))
-        for k, idx in enumerate(ENC_MEMBLOCKS):
-            pre = f"encoder.{idx}.conv"
-            w0 = sd[pre + ".0.weight"]
-            # cat([x_t, x_{t-1}]) input channels -> time taps [x_{t-1} | x_t] of a 2-slice conv
-            conv(W.mem[k][0], pre + ".0", torch.stack([w0[:, 64:], w0[:, :64]], dim=2), sd[pre + ".0.bias"])
-            conv(W.mem[k][1], pre + ".2", sd[pre + ".2.weight"], sd[pre + ".2.bias"])
-            conv(W.mem[k][2], pre + ".4", sd[pre + ".4.weight"], sd[pre + ".4.bias"])
         conv(W.head, "encoder.17", sd["encoder.17.weight"], sd["encoder.17.bias"])
-        self._t, self._w = t, W
-        return [], []
 
-    @classmethod
-    def random_state_dict(cls, seed=0):
-        """Deterministic synthetic encoder weights (CPU generator, float32), the recipe of TAEHVDecoder.random_state_dict:
-        He-scaled convs in front of a ReLU, variance-preserving TPool / stride-2 convs, each MemBlock's last conv scaled
-        down, small biases, a unit-gain head."""
-        g = torch.Generator().manual_seed(seed)
-        sd = {}
-        for name, shape in cls.state_dict_spec():
-            if name.endswith(".bias"):
-                sd[name] = 0.02 * torch.randn(shape, generator=g)
-                continue
-            fan_in = math.prod(shape[1:])
-            gain = math.sqrt(2.0)
-            if name.endswith(".conv.4.weight"):
-                gain = 0.3
-            elif ".conv.weight" in name or name in ("encoder.3.weight", "encoder.8.weight", "encoder.13.weight", "encoder.17.weight"):
-                gain = 1.0             # TPool, the conv behind it and the head: no ReLU in between / after
-            sd[name] = torch.randn(shape, generator=g) * (gain / math.sqrt(fan_in))
-        return sd
-
-    @staticmethod
-    def checksum(sd):
-        """sha256 over the float32 bytes of the encoder tensors in state_dict_spec order."""
-        h = hashlib.sha256()
-        for name, _ in TAEHVEncoder.state_dict_spec():
-            h.update(sd[name].detach().float().contiguous().cpu().numpy().tobytes())
-        return h.hexdigest()
-
-    def init_random_weights(self, seed=0):
-        self.load_state_dict(self.random_state_dict(seed))
-        return self
-
-    # ------------------------------------------------------------------ arena / state views
-    def _new_arena(self, H, W):
-        n = enc_arena_bytes(H, W, self.GROUP)
-        if n == 0:
-            raise ValueError(f"TAEHV encoder: frame size {H}x{W} not supported (H and W must be multiples of 8)")
-        return torch.empty(n + 256, dtype=torch.uint8, device=self.device)   # the state is zeroed by a stream's first call
-
-    def _state_views(self, arena, base, H, W):
-        views = []
-        off, C, h, w = ctypes.c_size_t(0), ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
-        for i in range(9):
-            _lib.call("rtv_taehv_enc_state_slot", H, W, i, ctypes.byref(off), ctypes.byref(C), ctypes.byref(h), ctypes.byref(w))
-            start = base + off.value
-            v = arena[start:start + C.value * h.value * w.value * 2].view(torch.float16).view(h.value, w.value, C.value)
-            views.append(v.permute(2, 0, 1).unsqueeze(0))     # [1, C, h, w] (channels-last in memory)
-        self._arenas.register(views, arena, base, (H, W))
-        return views
-
-    # ------------------------------------------------------------------ forward
     def forward(self, z, feat_cache=None, stream=False):
-        if self._w is None:
-            raise RuntimeError("TAEHV encoder: weights not loaded")
-        if not z.is_cuda:
-            raise RuntimeError("realtime_video_amd.TAEHVEncoder needs GPU tensors (no CPU fallback)")
+        self._check_input(z)
         B, Cc, T, H, W = z.shape
         if B != 1 or Cc != 3:
             raise NotImplementedError("TAEHV encoder: batch 1, RGB frames")
@@ -432,23 +371,18 @@ class TAEHVEncoder:
                 raise ValueError(f"{rule}; got a fresh cache with T = {T}")
         elif not stream or T < 4 or T % 4:
             raise ValueError(f"{rule}; got a carried cache with T = {T}, stream={bool(stream)}")
-        if H % 8 or W % 8 or enc_arena_bytes(H, W, self.GROUP) == 0:
+        need = 0 if H % 8 or W % 8 else enc_arena_bytes(H, W, self.GROUP)
+        if need == 0:
             raise ValueError(f"TAEHV encoder: frame size {H}x{W} not supported (H and W must be multiples of 8)")
         frames = z[0].to(torch.float16)
+        views = None
         if fresh:
             frames = torch.cat([frames[:, :1].expand(-1, 3, -1, -1), frames], 1)
-            ent = self._arenas.recycle((H, W))   # the arena of a dropped stream of this size, if any
-            arena, base = ent if ent is not None else (None, 0)
-            if arena is None:
-                arena = self._new_arena(H, W)
-                base = (-arena.data_ptr()) % 256
-            views = self._state_views(arena, base, H, W)
         else:
             views = feat_cache if isinstance(feat_cache, list) else list(feat_cache)
             if len(views) != 9:
                 raise ValueError(f"TAEHV encoder: a carried cache is the nine state slices a previous call returned, got {len(views)} slots")
-            arena, base = self._arenas.lookup(views, (H, W), lambda: self._new_arena(H, W),
-                                              lambda a, b: self._state_views(a, b, H, W))
+        arena, base, views = self._acquire(views, (H, W), self.GROUP, need)
         frames = frames.contiguous()
         Tt = frames.shape[1]
         n_out = Tt // 4
@@ -459,5 +393,3 @@ class TAEHVEncoder:
             _lib.call("rtv_taehv_encode", ctypes.byref(self._w), c_vp(frames.data_ptr()), Tt, t0, tn, H, W, int(fresh and t0 == 0),
                       c_vp(arena.data_ptr() + base), ctypes.c_size_t(arena.numel() - base), c_vp(mu.data_ptr()), n_out, t0 // 4, st)
         return mu.unsqueeze(0).to(z.dtype), views
-
-    __call__ = forward

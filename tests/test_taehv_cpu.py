@@ -1,7 +1,7 @@
 """CPU tests of the TAEHV tiny-VAE decoder (opt-in fast decode, realtime_video_amd/taehv.py, csrc/taehv.hip): the loader's key
 set against the reference module's manifest, the synthetic weights against the golden's checksum, a torch restatement of
 demo_utils/taehv.py's decoder against the golden (the restatement the GPU tests evaluate at production size), the library's
-new symbols and a scratch-free compile of the kernels."""
+new symbols, a scratch-free compile of the kernels and the arena layout of both halves against recorded values."""
 import ctypes
 import json
 import os
@@ -134,7 +134,9 @@ def test_library_exports_taehv_symbols():
     assert lib.rtv_taehv_state_slot(60, 104, 9, ctypes.byref(off), ctypes.byref(C), ctypes.byref(H), ctypes.byref(W)) != 0
 
 
-def test_taehv_kernels_use_no_scratch(tmp_path):
+def kernel_scratch_sizes(tmp_path):
+    """Compile csrc/taehv.hip with the library's flags -> (function names, scratch bytes per lane, the compiler's remarks), from
+    the kernel-resource-usage remarks.  Shared with tests/test_taehv_encoder_cpu.py."""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     if not os.path.exists(hipcc):
         pytest.skip("hipcc not installed")
@@ -144,6 +146,48 @@ def test_taehv_kernels_use_no_scratch(tmp_path):
     assert r.returncode == 0, r.stderr[-4000:]
     names = re.findall(r"Function Name: (\S+)", r.stderr)
     scratch = [int(v) for v in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", r.stderr)]
+    return names, scratch, r.stderr
+
+
+def test_taehv_kernels_use_no_scratch(tmp_path):
+    names, scratch, remarks = kernel_scratch_sizes(tmp_path)
     kernels = [n for n in names if "taehv" in n]
-    assert len(kernels) >= 4 and len(names) == len(scratch), r.stderr[-4000:]
+    assert len(kernels) >= 4 and len(names) == len(scratch), remarks[-4000:]
     assert all(s == 0 for n, s in zip(names, scratch) if "taehv" in n), list(zip(names, scratch))
+
+
+# What the four layout functions returned before the decoder's and the encoder's layouts were folded into one: Python holds
+# state views at these offsets and sizes its arenas by these totals.  Literals on purpose - not to be regenerated from the library.
+DEC_ARENA = {(7, 11, 3): 7860480, (8, 12, 6): 16306432, (60, 104, 3): 636979456}
+ENC_ARENA = {(56, 88, 12): 6673408, (64, 96, 12): 8319232, (480, 832, 12): 540733696}
+DEC_SLOTS = {
+    (7, 11): [(0, 256, 7, 11), (39424, 256, 7, 11), (78848, 256, 7, 11), (118272, 128, 14, 22), (197120, 128, 14, 22),
+              (275968, 128, 14, 22), (354816, 64, 28, 44), (512512, 64, 28, 44), (670208, 64, 28, 44)],
+    (60, 104): [(0, 256, 60, 104), (3194880, 256, 60, 104), (6389760, 256, 60, 104), (9584640, 128, 120, 208),
+                (15974400, 128, 120, 208), (22364160, 128, 120, 208), (28753920, 64, 240, 416), (41533440, 64, 240, 416),
+                (54312960, 64, 240, 416)],
+}
+ENC_SLOTS = {
+    (56, 88): [(0, 64, 28, 44), (157696, 64, 28, 44), (315392, 64, 28, 44), (473088, 64, 14, 22), (512512, 64, 14, 22),
+               (551936, 64, 14, 22), (591360, 64, 7, 11), (601344, 64, 7, 11), (611328, 64, 7, 11)],
+    (480, 832): [(0, 64, 240, 416), (12779520, 64, 240, 416), (25559040, 64, 240, 416), (38338560, 64, 120, 208),
+                 (41533440, 64, 120, 208), (44728320, 64, 120, 208), (47923200, 64, 60, 104), (48721920, 64, 60, 104),
+                 (49520640, 64, 60, 104)],
+}
+
+
+def test_arena_layout_is_pinned():
+    from realtime_video_amd.taehv import arena_bytes, enc_arena_bytes
+
+    def slots(fn, a, b):
+        off, C, H, W = ctypes.c_size_t(0), ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+        out = []
+        for i in range(9):
+            _lib.call(fn, a, b, i, ctypes.byref(off), ctypes.byref(C), ctypes.byref(H), ctypes.byref(W))
+            out.append((off.value, C.value, H.value, W.value))
+        return out
+
+    assert {k: arena_bytes(*k) for k in DEC_ARENA} == DEC_ARENA
+    assert {k: enc_arena_bytes(*k) for k in ENC_ARENA} == ENC_ARENA
+    assert {k: slots("rtv_taehv_state_slot", *k) for k in DEC_SLOTS} == DEC_SLOTS
+    assert {k: slots("rtv_taehv_enc_state_slot", *k) for k in ENC_SLOTS} == ENC_SLOTS

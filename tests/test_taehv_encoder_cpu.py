@@ -5,8 +5,6 @@ against the two-layer form, the library's new symbols and a scratch-free compile
 import ctypes
 import json
 import os
-import re
-import subprocess
 
 import pytest
 import torch
@@ -15,8 +13,7 @@ import torch.nn.functional as F
 from conftest import GOLDEN, rel_l2
 from realtime_video_amd import _lib
 from realtime_video_amd.taehv import ENC_MEMBLOCKS, TPOOLS, TAEHVDecoder, TAEHVEncoder, fold_tpool
-
-CSRC = os.path.join(os.path.dirname(GOLDEN), "..", "realtime_video_amd", "csrc")
+from test_taehv_cpu import kernel_scratch_sizes
 
 
 def golden_frames(H, W, T, seed):   # scripts/make_taehv_encoder_golden.py frames01()
@@ -157,16 +154,8 @@ def test_library_exports_taehv_encoder_symbols():
 
 
 def test_taehv_encoder_kernels_use_no_scratch(tmp_path):
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not installed")
-    r = subprocess.run([hipcc, "--offload-arch=" + os.environ.get("ARCH", "gfx950"), "-O3", "-std=c++17", "-fPIC", "-c",
-                        os.path.join(CSRC, "taehv.hip"), "-o", str(tmp_path / "taehv.o"),
-                        "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-    names = re.findall(r"Function Name: (\S+)", r.stderr)
-    scratch = [int(v) for v in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", r.stderr)]
-    assert len(names) == len(scratch), r.stderr[-4000:]
+    names, scratch, remarks = kernel_scratch_sizes(tmp_path)
+    assert len(names) == len(scratch), remarks[-4000:]
     # the first layer, the stride-2 gather form (..., HEAD 0, DOWN true) and the latent head (HEAD 2) of taehv_conv_kernel
     new = [n for n in names if "taehv_enc_first" in n or n.endswith("ELi0ELb1EEEvNS0_10ConvParamsE")
            or n.endswith("ELi2ELb0EEEvNS0_10ConvParamsE")]

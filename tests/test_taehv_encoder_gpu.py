@@ -1,9 +1,9 @@
 """GPU tests of the TAEHV tiny-VAE encoder (csrc/taehv.hip behind realtime_video_amd/taehv.py TAEHVEncoder): every new
 convolution form of rtv_taehv_enc_conv against torch fp32 conv2d, the streamed encode against the reference's goldens,
 bit-identical results however a stream is split into calls, the production size against the CPU-pinned restatement
-(tests/test_taehv_encoder_cpu.py) evaluated on the GPU, the time contract's errors, the session's encode sites and a
-frame-count round trip through the TAEHV decoder."""
-import ctypes
+(tests/test_taehv_encoder_cpu.py) evaluated on the GPU, the time contract's errors, the two live streams on one instance
+(a dropped stream's arena is recycled), the session's encode sites and a frame-count round trip through the TAEHV decoder."""
+import gc
 
 import pytest
 import torch
@@ -11,22 +11,15 @@ import torch.nn.functional as F
 
 from conftest import max_abs, rel_l2
 from test_taehv_encoder_cpu import golden_frames, restate_encode
+from test_taehv_gpu import _ptr, lib_call
 
 DEV = "cuda"
-c_vp = ctypes.c_void_p
 pytestmark = pytest.mark.gpu
 
 
-def _ptr(t):
-    return c_vp(t.data_ptr()) if t is not None else None
-
-
 def _enc_conv(x, w, bias, out, form, T, H, W, kt, n_total, n0):
-    from realtime_video_amd import _lib, taehv  # noqa: F401  (registers the signatures)
     zeros = torch.zeros(64, dtype=torch.float16, device=DEV)
-    _lib.call("rtv_taehv_enc_conv", _ptr(x), _ptr(w), _ptr(bias), _ptr(out), form, T, H, W, kt, n_total, n0, _ptr(zeros),
-              c_vp(torch.cuda.current_stream().cuda_stream))
-    torch.cuda.synchronize()
+    lib_call("rtv_taehv_enc_conv", _ptr(x), _ptr(w), _ptr(bias), _ptr(out), form, T, H, W, kt, n_total, n0, _ptr(zeros))
 
 
 def _check(name, got, ref):
@@ -148,6 +141,44 @@ def test_split_invariance_bit_identical(golden):
     assert len(sa) == len(sb) == len(sc) == 9
     for x, y, u in zip(sa, sb, sc):
         assert x.data_ptr() != y.data_ptr() and torch.equal(x, y) and torch.equal(x, u)
+
+
+def test_two_live_streams_and_recycle():
+    """Streams A (9 frames fresh, then 12 streamed) and B (21 frames fresh: two GROUP calls) interleaved on one instance give
+    what each gives alone on a fresh instance, latents and state, bit for bit; a stream started after A's cache list is gone
+    runs on A's arena.  (No grow path: the arena is sized by GROUP.)"""
+    from realtime_video_amd.taehv import TAEHVEncoder
+    sd = TAEHVEncoder.random_state_dict(2)
+
+    def fresh():
+        enc = TAEHVEncoder(DEV)
+        enc.load_state_dict(sd)
+        return enc
+
+    fa, fb, fc = (golden_frames(56, 88, 21, seed) for seed in (31, 32, 33))
+    (ra, rsa), (rb, rsb), (rc, rsc) = _stream(fresh(), fa, [9, 12]), _stream(fresh(), fb, [21]), _stream(fresh(), fc[:9], [9])
+    enc = fresh()
+
+    def call(fr, t0, t1, cache):
+        x = (2 * fr[t0:t1] - 1).transpose(0, 1)[None].to(DEV).half()
+        return enc(x, cache, stream=t0 > 0)
+
+    a0, sa = call(fa, 0, 9, [None] * 55)
+    b0, sb = call(fb, 0, 21, [None] * 55)
+    a1, sa = call(fa, 9, 21, sa)
+    torch.cuda.synchronize()
+    assert torch.equal(torch.cat([a0, a1], 2), ra) and torch.equal(b0, rb)
+    assert len(sa) == len(sb) == 9
+    assert all(torch.equal(x, y) for x, y in zip(sa, rsa)) and all(torch.equal(x, y) for x, y in zip(sb, rsb))
+    arenas, a_ptr = len(enc._arenas._by_ptr), sa[0].data_ptr()
+    assert arenas == 2
+    del sa
+    gc.collect()
+    c0, sc = call(fc, 0, 9, [None] * 55)
+    torch.cuda.synchronize()
+    assert torch.equal(c0, rc) and all(torch.equal(x, y) for x, y in zip(sc, rsc))
+    assert len(enc._arenas._by_ptr) == arenas and sc[0].data_ptr() == a_ptr
+    assert all(torch.equal(x, y) for x, y in zip(sb, rsb))   # B's state is untouched by C
 
 
 def test_production_size_matches_restatement():

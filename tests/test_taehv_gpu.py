@@ -1,8 +1,9 @@
 """GPU tests of the TAEHV tiny-VAE decoder (csrc/taehv.hip behind realtime_video_amd/taehv.py): every convolution form of
 rtv_taehv_conv against torch fp32 conv2d, the streamed decode against the reference's golden, bit-identical results however
 a stream is split into calls, the production size against the CPU-pinned restatement (tests/test_taehv_cpu.py) evaluated on
-the GPU, and the session's use_taehv switch."""
+the GPU, two live streams on one instance (grow and recycle of a stream's arena), and the session's use_taehv switch."""
 import ctypes
+import gc
 
 import pytest
 import torch
@@ -20,12 +21,17 @@ def _ptr(t):
     return c_vp(t.data_ptr()) if t is not None else None
 
 
-def _conv_call(x, w, bias, res, out, T, H, W, Cin, Cout, kt, ups, n_split, relu, head):
+def lib_call(name, *args):
+    """One library call on the current stream, then a device synchronise.  Shared with tests/test_taehv_encoder_gpu.py."""
     from realtime_video_amd import _lib, taehv  # noqa: F401  (registers the signatures)
-    zeros = torch.zeros(64, dtype=torch.float16, device=DEV)
-    _lib.call("rtv_taehv_conv", _ptr(x), _ptr(w), _ptr(bias), _ptr(res), _ptr(out), T, H, W, Cin, Cout, kt, ups, n_split, relu,
-              head, _ptr(zeros), c_vp(torch.cuda.current_stream().cuda_stream))
+    _lib.call(name, *args, c_vp(torch.cuda.current_stream().cuda_stream))
     torch.cuda.synchronize()
+
+
+def _conv_call(x, w, bias, res, out, T, H, W, Cin, Cout, kt, ups, n_split, relu, head):
+    zeros = torch.zeros(64, dtype=torch.float16, device=DEV)
+    lib_call("rtv_taehv_conv", _ptr(x), _ptr(w), _ptr(bias), _ptr(res), _ptr(out), T, H, W, Cin, Cout, kt, ups, n_split, relu,
+             head, _ptr(zeros))
 
 
 @pytest.mark.parametrize("T,hw", [(1, 96), (3, 60 * 104), (2, 777)])
@@ -34,11 +40,9 @@ def test_prep_kernel_clamp_and_layout(T, hw):
     evaluation (the kernel rounds an fp32 tanhf); +-0, +-60, +-65504 and a subnormal among the inputs; channels 16..31 exact
     zeros; nothing written behind the last pixel.  Inputs, reference and acceptance: tests/test_vae_units_cpu.py."""
     import test_vae_units_cpu as U
-    from realtime_video_amd import _lib, taehv  # noqa: F401  (registers the signatures)
     z = U.taehv_prep_inputs(T, hw, device=DEV)
     out = torch.full((T * hw + 2, 32), float("nan"), dtype=torch.float16, device=DEV)
-    _lib.call("rtv_taehv_prep", _ptr(z), T, hw, _ptr(out), c_vp(torch.cuda.current_stream().cuda_stream))
-    torch.cuda.synchronize()
+    lib_call("rtv_taehv_prep", _ptr(z), T, hw, _ptr(out))
     v = U.taehv_prep_violation(out[:T * hw].view(T, hw, 32), z)
     print(f"taehv_prep T={T} hw={hw}: {v} ulp (bound 1)")
     assert v <= 1
@@ -155,6 +159,46 @@ def test_split_invariance_bit_identical(golden):
     assert torch.equal(a, b) and torch.equal(a, c)
     for x, y, u in zip(sa, sb, sc):
         assert torch.equal(x, y) and torch.equal(x, u)
+
+
+def test_two_live_streams_grow_and_recycle():
+    """Streams A (T = 2, then 4: longer than the arena sized on its first call, so its state moves to a larger one) and B
+    (T = 3, 3) interleaved on one instance give what each gives alone on a fresh instance, pixels and state, bit for bit; a
+    stream started after A's state list is gone runs on A's arena."""
+    from realtime_video_amd.taehv import TAEHVDecoder
+    sd = TAEHVDecoder.random_state_dict(2)
+
+    def fresh():
+        dec = TAEHVDecoder(DEV)
+        dec.load_state_dict(sd)
+        return dec
+
+    za, zb, zc = (golden_latents(7, 11, seed, 6) for seed in (11, 12, 13))
+    (ra, rsa), (rb, rsb), (rc, rsc) = _stream(fresh(), za, [2, 4]), _stream(fresh(), zb, [3, 3]), _stream(fresh(), zc[:, :3], [3])
+    dec = fresh()
+
+    def call(z, t0, t1, state):
+        return dec(z[:, t0:t1].to(DEV).half(), *state)
+
+    a0, sa = call(za, 0, 2, [None] * 55)
+    small = sa[0].data_ptr()
+    b0, sb = call(zb, 0, 3, [None] * 55)
+    a1, sa = call(za, 2, 6, sa)
+    b1, sb = call(zb, 3, 6, sb)
+    torch.cuda.synchronize()
+    assert sa[0].data_ptr() != small                      # A has moved
+    assert torch.equal(torch.cat([a0, a1], 1), ra) and torch.equal(torch.cat([b0, b1], 1), rb)
+    assert len(sa) == len(sb) == 9
+    assert all(torch.equal(x, y) for x, y in zip(sa, rsa)) and all(torch.equal(x, y) for x, y in zip(sb, rsb))
+    arenas, a_ptr = len(dec._arenas._by_ptr), sa[0].data_ptr()
+    assert arenas == 2
+    del sa
+    gc.collect()
+    c0, sc = call(zc, 0, 3, [None] * 55)
+    torch.cuda.synchronize()
+    assert torch.equal(c0, rc) and all(torch.equal(x, y) for x, y in zip(sc, rsc))
+    assert len(dec._arenas._by_ptr) == arenas and sc[0].data_ptr() == a_ptr
+    assert all(torch.equal(x, y) for x, y in zip(sb, rsb))   # B's state is untouched by C
 
 
 def test_production_size_matches_restatement():
