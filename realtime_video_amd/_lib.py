@@ -1,4 +1,6 @@
-"""ctypes binding of librtv_hip.so (the C-ABI HIP kernel library, see include/rtv_hip.h).
+"""ctypes binding of librtv_hip.so (the C-ABI HIP kernel library), generated from include/rtv_hip.h and include/rtv_hip_lab.h:
+STRUCTS (the ABI structs as ctypes.Structure classes), PROTOTYPES (restype / argtypes of every declared function, which load()
+puts on the library) and ABI_VERSION are parsed from the headers at import; nothing restates them by hand.
 
 The product path has no CPU / eager fallback: if the library is missing or a kernel reports an
 error, a RuntimeError is raised (the reference's attention()/pipeline API reports errors as Python
@@ -6,6 +8,7 @@ exceptions, wan/modules/attention.py:72-73,129).
 """
 import ctypes
 import os
+import re
 import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -13,66 +16,88 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RTV_LIB_PATH") or os.path.join(_HERE, "librtv_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
 
-ABI_VERSION = 103   # include/rtv_hip.h RTV_ABI_VERSION this binding's structs / signatures mirror
+_INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
+HEADERS = ("rtv_hip.h", "rtv_hip_lab.h")
 
 _lib = None
 
-c_int, c_i64, c_f32, c_vp = ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
+_SCALARS = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "double": ctypes.c_double,
+            "size_t": ctypes.c_size_t}
+_RETURNS = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "const char*": ctypes.c_char_p}
+_STARS = r"(\*(?:\s*const\s*\*)?)?"     # nothing, `*` or `* const*`
 
-# name -> argtypes (restype is always int except where noted); mirrors include/rtv_hip.h
-SIGNATURES = {
-    "rtv_version": [],
-    "rtv_quantize_fp8": [c_vp, c_i64, c_int, c_int, c_vp, c_i64, c_vp, c_vp, c_vp],
-    "rtv_gemm_fp8": [c_vp, c_int, c_vp, c_int, c_vp, c_f32, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp, c_int,
-                     c_int, c_int, c_vp, c_int, c_vp],
-    "rtv_prof_enable": [c_int],
-    "rtv_prof_read": [c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_i64),
-                      ctypes.POINTER(ctypes.c_double)],
-    "rtv_prof_reset": [],
-    "rtv_prof_set_stride": [c_int, c_int],
-    "rtv_prof_read_seen": [c_int, ctypes.POINTER(c_i64), ctypes.POINTER(ctypes.c_double)],
-    "rtv_prof_bracket_overhead": [c_int, c_vp, ctypes.POINTER(ctypes.c_double)],
-    "rtv_attn_fwd": [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int,
-                     c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64,
-                     c_f32, c_int, c_int, c_int, c_vp],
-    "rtv_attn_fwd_win": [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                         c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64,
-                         c_f32, c_int, c_int, c_int, c_vp],
-    "rtv_attn_fwd_dup": [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int,
-                         c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64,
-                         c_f32, c_int, c_int, c_int, c_vp],
-    "rtv_attn_fwd_split": [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                           c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64,
-                           c_f32, c_int, c_int, c_int, c_vp, ctypes.c_size_t, c_int, c_vp],
-    "rtv_attn_set_waves": [c_int],             # include/rtv_hip_lab.h (variant switches for tests / scripts)
-    "rtv_attn_set_skip_idle": [c_int],
-    "rtv_gemm_set_half_tail": [c_int],
-    "rtv_gemm_set_skip_idle": [c_int],
-    "rtv_gemm_set_ragged_strips": [c_int],
-    "rtv_lab_build": [],
-    "rtv_rope_set_wave": [c_int],
-    "rtv_gemm": [c_vp, c_int, c_vp, c_int, c_vp, c_int, c_int, c_int, c_int,
-                 c_vp, c_int, c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_int, c_vp],
-    "rtv_layernorm_modulate": [c_vp, c_vp, c_int, c_int, c_f32, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp],
-    "rtv_rmsnorm": [c_vp, c_int, c_vp, c_int, c_int, c_int, c_f32, c_vp, c_vp],
-    "rtv_qk_norm_rope_cache": [c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_int, c_int, c_f32,
-                               c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp],
-    "rtv_qk_norm_rope_cache_ring": [c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_int, c_int, c_f32,
-                                    c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp],
-    "rtv_modulation_table": [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp],
-    "rtv_sinusoidal_embedding": [c_vp, c_vp, c_int, c_int, c_vp],
-    "rtv_patchify": [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp],
-    "rtv_unpatchify": [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp],
-    "rtv_scheduler_step": [c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_int, c_vp, c_vp, c_int,
-                           c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp],
-    "rtv_pixels_to_rgb8": [c_vp, c_vp, c_int, c_int, c_int, c_vp],
-    "rtv_gemm_set_workspace": [c_vp, ctypes.c_size_t],
-    "rtv_gemm_set_stream_workspace": [c_vp, c_vp, ctypes.c_size_t],
-    "rtv_probe_mfma": [c_vp, c_vp, c_vp, c_vp],
-    "rtv_probe_tr": [c_vp, c_vp, c_int, c_int, c_vp],
-}
-# later sections (DiT forward, VAE) register their signatures here as well
-EXTRA_SIGNATURES = {}
+
+def _field_type(base, stars, structs):
+    value = _SCALARS.get(base) or structs.get(base)
+    if not stars:
+        return value                                  # None for `void` and unknown names: the caller raises
+    if base == "void":
+        return ctypes.c_void_p if stars == "*" else ctypes.POINTER(ctypes.c_void_p)
+    return ctypes.POINTER(value) if value and stars == "*" else None
+
+
+def _param_type(base, stars, structs):
+    if not stars:
+        return ctypes.c_void_p if base == "rtv_stream_t" else _SCALARS.get(base)
+    if base in structs:
+        return ctypes.POINTER(structs[base]) if stars == "*" else None
+    # device addresses arrive as Python ints, out-parameters as byref() / ctypes arrays: c_void_p takes all of them
+    return ctypes.c_void_p if base == "void" or base in _SCALARS else None
+
+
+def parse_header(text, structs):
+    """One C header of the ABI -> {function: (restype, argtypes)}; its struct typedefs are added to `structs` as generated
+    ctypes.Structure classes (header order, so nested structs resolve).  The headers are the only statement of the ABI: a
+    declaration this parser does not understand raises, it never gets a default type."""
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = re.sub(r"#ifdef __cplusplus.*?#endif", "", text, flags=re.S)          # the extern "C" braces
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    text = re.sub(r"\benum\s*\{[^}]*\}\s*;|\btypedef\s+void\s*\*\s*rtv_stream_t\s*;", "", text)
+
+    def struct(m):
+        name, fields = m.group(2), []
+        for decl in filter(None, (d.strip() for d in m.group(1).split(";"))):
+            head = re.match(r"(?:const\s+)?(\w+)\s*", decl)
+            for item in decl[head.end():].split(","):
+                d = re.fullmatch(_STARS + r"\s*(\w+)((?:\s*\[\d+\])*)", item.strip())
+                t = d and _field_type(head.group(1), re.sub(r"\s", "", d.group(1) or ""), structs)
+                if not t:
+                    raise ValueError(f"{name}: cannot bind field declaration `{decl}`")
+                for n in reversed(re.findall(r"\d+", d.group(3))):
+                    t = t * int(n)
+                fields.append((d.group(2), t))
+        structs[name] = type(name, (ctypes.Structure,), {"_fields_": fields})
+        return ""
+
+    text = re.sub(r"\btypedef\s+struct\s*\w*\s*\{([^}]*)\}\s*(\w+)\s*;", struct, text)
+    protos = {}
+    for stmt in filter(None, (" ".join(s.split()) for s in text.split(";"))):
+        m = re.fullmatch(r"(.*?)\s*\b(\w+)\s*\((.*)\)", stmt)
+        if not m:
+            raise ValueError(f"cannot bind declaration `{stmt}`")
+        ret, name, params = m.group(1).replace(" *", "*"), m.group(2), m.group(3).strip()
+        if ret not in _RETURNS:
+            raise ValueError(f"{name}: cannot bind return type `{ret}`")
+        argtypes = []
+        for param in ([] if params == "void" else params.split(",")):
+            d = re.fullmatch(r"(?:const\s+)?(\w+)\s*" + _STARS + r"\s*(\w+)?", param.strip())
+            t = d and _param_type(d.group(1), re.sub(r"\s", "", d.group(2) or ""), structs)
+            if not t:
+                raise ValueError(f"{name}: cannot bind parameter `{param.strip()}`")
+            argtypes.append(t)
+        protos[name] = (_RETURNS[ret], argtypes)
+    return protos
+
+
+def _read(name):
+    with open(os.path.join(_INCLUDE, name)) as f:
+        return f.read()
+
+
+STRUCTS, PROTOTYPES = {}, {}      # struct name -> ctypes.Structure class; function name -> (restype, argtypes)
+for _name in HEADERS:
+    PROTOTYPES.update(parse_header(_read(_name), STRUCTS))
+ABI_VERSION = int(re.search(r"^#define\s+RTV_ABI_VERSION\s+(\d+)", _read(HEADERS[0]), flags=re.M).group(1))
 
 
 def build(verbose=False):
@@ -92,11 +117,9 @@ def build(verbose=False):
 def declared_symbols(lab=True):
     """Every extern "C" function declared in include/rtv_hip.h - the drop-in boundary - and, with `lab`, in
     include/rtv_hip_lab.h (test / measurement hooks, not part of the boundary), parsed from the headers."""
-    import re
     out = set()
-    for name in ("rtv_hip.h",) + (("rtv_hip_lab.h",) if lab else ()):
-        text = open(os.path.join(os.path.dirname(_HERE), "include", name)).read()
-        text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    for name in HEADERS if lab else HEADERS[:1]:
+        text = re.sub(r"/\*.*?\*/", "", _read(name), flags=re.S)
         out.update(re.findall(r"\b(rtv_[a-z0-9_]+)\s*\(", text))
     return sorted(out)
 
@@ -111,26 +134,20 @@ def load():
             f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C realtime_video_amd/csrc`). There is no CPU fallback for the HIP path.")
     lib = ctypes.CDLL(LIB_PATH)
-    lib.rtv_version.restype, lib.rtv_version.argtypes = c_int, []
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(lib, name, None)
+        if fn is None:
+            # RTV_LIB_PATH = an older build of the same C ABI (A/B measurements): entry points added since are simply absent
+            if os.environ.get("RTV_LIB_PATH"):
+                continue
+            raise RuntimeError(f"librtv_hip.so does not export {name}")
+        fn.restype, fn.argtypes = restype, argtypes
     have = lib.rtv_version()
     if have != ABI_VERSION:
         # struct layouts (rtv_dit_config, rtv_dit_step, ...) are part of the ABI: a library of another revision would read
         # garbage for fields it does not know.  RTV_LIB_PATH (A/B against an older build) is no exception.
-        raise RuntimeError(f"{LIB_PATH} reports ABI revision {have}, this binding is written against {ABI_VERSION} "
-                           "(include/rtv_hip.h RTV_ABI_VERSION): rebuild the library (`make -C realtime_video_amd/csrc`)")
-    lib.rtv_last_error.restype = ctypes.c_char_p
-    lib.rtv_last_error.argtypes = []
-    sigs = dict(SIGNATURES)
-    sigs.update(EXTRA_SIGNATURES)
-    for name, argtypes in sigs.items():
-        fn = getattr(lib, name, None)
-        if fn is None:
-            # RTV_LIB_PATH = an older build of the same C ABI (A/B measurements): entry points added since are simply absent
-            if name in SIGNATURES and not os.environ.get("RTV_LIB_PATH"):
-                raise RuntimeError(f"librtv_hip.so does not export {name}")
-            continue
-        fn.argtypes = argtypes
-        fn.restype = c_int
+        raise RuntimeError(f"{LIB_PATH} reports ABI revision {have}, include/rtv_hip.h declares RTV_ABI_VERSION {ABI_VERSION}: "
+                           "rebuild the library (`make -C realtime_video_amd/csrc`)")
     _lib = lib
     return lib
 
@@ -142,9 +159,4 @@ def check(status, what):
 
 
 def call(name, *args):
-    lib = load()
-    fn = getattr(lib, name)
-    if fn.argtypes is None and name in EXTRA_SIGNATURES:   # registered by a module imported after load()
-        fn.argtypes = EXTRA_SIGNATURES[name]
-        fn.restype = c_int
-    check(fn(*args), name)
+    check(getattr(load(), name)(*args), name)

@@ -23,65 +23,19 @@ c_vp = ctypes.c_void_p
 _IncompatibleKeys = collections.namedtuple("_IncompatibleKeys", ["missing_keys", "unexpected_keys"])   # torch's return type
 
 
-class _Cfg(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_int) for n in ("dim", "ffn_dim", "num_heads", "num_layers", "freq_dim", "text_dim",
-                                            "text_len", "in_dim", "out_dim")] + [("eps", ctypes.c_float),
-                                                                                  ("use_fp8", ctypes.c_int),
-                                                                                  ("max_attn_kv_splits", ctypes.c_int)]
-
-
-_LAYER_FIELDS = ("qkv_w", "qkv_b", "norm_q_w", "norm_k_w", "o_w", "o_b", "norm3_w", "norm3_b",
-                 "cq_w", "cq_b", "ck_w", "ck_b", "cv_w", "cv_b", "co_w", "co_b", "cnorm_q_w", "cnorm_k_w",
-                 "ffn0_w", "ffn0_b", "ffn2_w", "ffn2_b")
-
-
-class _LayerW(ctypes.Structure):
-    _fields_ = [(n, c_vp) for n in _LAYER_FIELDS]
-
-
-_TOP_FIELDS = ("patch_w", "patch_b", "text0_w", "text0_b", "text2_w", "text2_b", "time0_w", "time0_b",
-               "time2_w", "time2_b", "tproj_w", "tproj_b", "head_w", "head_b", "modulation",
-               "head_modulation", "rope_cs")
-
-
-class _Weights(ctypes.Structure):
-    _fields_ = [(n, c_vp) for n in _TOP_FIELDS] + [("layers", ctypes.POINTER(_LayerW)),
-                                                   ("fp8_scales", ctypes.POINTER(ctypes.c_float))]
-
+# the ABI structs of include/rtv_hip.h, generated from the header
+_Cfg = _lib.STRUCTS["rtv_dit_config"]
+_LayerW = _lib.STRUCTS["rtv_dit_layer_weights"]
+_Weights = _lib.STRUCTS["rtv_dit_weights"]
+_Step = _lib.STRUCTS["rtv_dit_step"]
+_LAYER_FIELDS = tuple(n for n, _ in _LayerW._fields_)
+_TOP_FIELDS = tuple(n for n, t in _Weights._fields_ if t is c_vp)      # the device tensors; `layers` / `fp8_scales` are host arrays
 
 # nn.Linear weights in the order of rtv_dit_weights.fp8_scales (include/rtv_hip.h)
 _FP8_TOP = ("text0_w", "text2_w", "time0_w", "time2_w", "tproj_w", "head_w")
 _FP8_LAYER = ("qkv_w", "o_w", "cq_w", "ck_w", "cv_w", "co_w", "ffn0_w", "ffn2_w")
 
-
-class _Step(ctypes.Structure):
-    _fields_ = [("x", c_vp), ("t", c_vp), ("context", c_vp), ("out", c_vp),
-                ("F", ctypes.c_int), ("gh", ctypes.c_int), ("gw", ctypes.c_int),
-                ("kv_k", ctypes.POINTER(c_vp)), ("kv_v", ctypes.POINTER(c_vp)), ("kv_row_stride", ctypes.c_int64),
-                ("ca_k", ctypes.POINTER(c_vp)), ("ca_v", ctypes.POINTER(c_vp)),
-                ("compute_cross_kv", ctypes.c_int), ("cache_row0", ctypes.c_int),
-                ("kv_lo", ctypes.c_int), ("kv_hi", ctypes.c_int), ("start_frame", ctypes.c_int),
-                ("causal_block", ctypes.c_int), ("gemm_tile_cfg", ctypes.c_int),
-                ("row_begin", ctypes.c_int), ("row_count", ctypes.c_int),
-                ("ring_lo", ctypes.c_int), ("ring_size", ctypes.c_int), ("ring_shift", ctypes.c_int),
-                ("text_rows", ctypes.c_int), ("kv_only", ctypes.c_int),
-                ("attn_kv_splits", ctypes.c_int)]
-
-
-_lib.EXTRA_SIGNATURES["rtv_dit_forward"] = [ctypes.POINTER(_Cfg), ctypes.POINTER(_Weights), ctypes.POINTER(_Step),
-                                            c_vp, ctypes.c_size_t, c_vp]
-_lib.EXTRA_SIGNATURES["rtv_silu"] = [c_vp, c_vp, ctypes.c_int64, c_vp]
-_P3 = [ctypes.POINTER(_Cfg), ctypes.POINTER(_Weights), ctypes.POINTER(_Step)]
-_lib.EXTRA_SIGNATURES["rtv_dit_begin"] = _P3 + [c_vp, ctypes.c_size_t, c_vp]
-_lib.EXTRA_SIGNATURES["rtv_dit_layer_qkv"] = _P3 + [ctypes.c_int, c_vp, ctypes.c_size_t, c_vp]
-_lib.EXTRA_SIGNATURES["rtv_dit_layer_rest"] = _P3 + [ctypes.c_int, c_vp, ctypes.c_size_t, c_vp]
-_lib.EXTRA_SIGNATURES["rtv_dit_layer_proj"] = _P3 + [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp]
 PROJ_LN, PROJ_Q, PROJ_KV = 1, 2, 4
-_lib.EXTRA_SIGNATURES["rtv_dit_layer_qkv_hp"] = _P3 + [ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp]
-_lib.EXTRA_SIGNATURES["rtv_dit_layer_attn_hp"] = _P3 + [ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp]
-_lib.EXTRA_SIGNATURES["rtv_dit_layer_rest_hp"] = _P3 + [ctypes.c_int, ctypes.c_int, c_vp, c_vp, ctypes.c_size_t, c_vp]
-_lib.EXTRA_SIGNATURES["rtv_dit_head"] = _P3 + [c_vp, c_vp, ctypes.c_size_t, c_vp]
-_lib.EXTRA_SIGNATURES["rtv_dit_finish"] = [ctypes.POINTER(_Cfg), ctypes.POINTER(_Step), c_vp, c_vp]
 
 
 class BlockCausalMask:
@@ -394,10 +348,7 @@ class CausalWanModel:
         key = (F, gh, gw, slot)
         ws = self._ws.get(key)
         if ws is None:
-            lib = _lib.load()
-            lib.rtv_dit_workspace_bytes.restype = ctypes.c_size_t
-            lib.rtv_dit_workspace_bytes.argtypes = [ctypes.POINTER(_Cfg), ctypes.c_int, ctypes.c_int, ctypes.c_int]
-            n = lib.rtv_dit_workspace_bytes(ctypes.byref(self._cfg), F, gh, gw)
+            n = _lib.load().rtv_dit_workspace_bytes(ctypes.byref(self._cfg), F, gh, gw)
             ws = torch.empty(n + 256, dtype=torch.uint8, device=self.device)
             self._ws[key] = ws
         return ws

@@ -68,14 +68,11 @@ def dispatch_counts(reset=False):
     """{kernel variant name: launches since load / the last reset} for the variants that ran (rtv_dispatch_counts): which GEMM /
     attention / conv kernels the dispatch rules actually chose."""
     lib = _lib.load()
-    lib.rtv_dispatch_counts.restype, lib.rtv_dispatch_counts.argtypes = ctypes.c_int, [ctypes.POINTER(ctypes.c_int64), ctypes.c_int]
-    lib.rtv_dispatch_name.restype, lib.rtv_dispatch_name.argtypes = ctypes.c_char_p, [ctypes.c_int]
     n = lib.rtv_dispatch_counts(None, 0)
     buf = (ctypes.c_int64 * n)()
     lib.rtv_dispatch_counts(buf, n)
     out = {lib.rtv_dispatch_name(i).decode(): int(buf[i]) for i in range(n) if buf[i]}
     if reset:
-        lib.rtv_dispatch_reset.restype, lib.rtv_dispatch_reset.argtypes = ctypes.c_int, []
         lib.rtv_dispatch_reset()
     return out
 
@@ -185,10 +182,7 @@ def attn_fwd_split(q, k_cache, v_cache, seg0, seg1=(0, 0), kv_splits=2, out=None
     if scale is None:
         scale = 1.0 / math.sqrt(D)
     if workspace is None:
-        lib = _lib.load()
-        lib.rtv_attn_split_workspace_bytes.restype = ctypes.c_size_t
-        lib.rtv_attn_split_workspace_bytes.argtypes = [ctypes.c_int] * 4
-        need = lib.rtv_attn_split_workspace_bytes(B, Lq, H, int(kv_splits))
+        need = _lib.load().rtv_attn_split_workspace_bytes(B, Lq, H, int(kv_splits))
         workspace = torch.empty(max(need, 16) // 4, dtype=torch.float32, device=q.device)
     k, v = k_cache[:, r0:], v_cache[:, r0:]
     _lib.call("rtv_attn_fwd_split", _ptr(q), _ptr(k), _ptr(v), _ptr(out), B, Lq, n0, n1,
@@ -213,10 +207,7 @@ def ensure_gemm_workspace(device, stream=None):
     key = (idx, int(stream))
     if key in _gemm_ws:
         return
-    lib = _lib.load()
-    lib.rtv_gemm_workspace_bytes.restype = ctypes.c_size_t
-    lib.rtv_gemm_workspace_bytes.argtypes = []
-    n = lib.rtv_gemm_workspace_bytes()
+    n = _lib.load().rtv_gemm_workspace_bytes()
     with torch.cuda.device(idx):
         ws = torch.zeros(n + 256, dtype=torch.uint8, device=torch.device("cuda", idx))
         off = (-ws.data_ptr()) % 256

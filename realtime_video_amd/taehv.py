@@ -15,14 +15,13 @@ previous frame of its rate) as [1, C, H, W] views into the stream's arena, updat
 is the call contract of `VAEEncoderWrapper`, so `encode_video_latent(vae=TAEHVEncoder, ...)` works unchanged; see the class.
 """
 import ctypes
-import functools
 import hashlib
 import math
 
 import torch
 
 from . import _lib
-from .vae_decoder import CacheArenas, _Conv, pack_conv_weight
+from .vae_decoder import CacheArenas, pack_conv_weight
 
 c_vp = ctypes.c_void_p
 
@@ -35,41 +34,16 @@ ENC_MEMBLOCKS = (4, 5, 6, 9, 10, 11, 14, 15, 16)  # encoder indices of the nine 
 TPOOLS = ((2, 3, 2), (7, 8, 2), (12, 13, 1))      # (TPool idx, stride-2 conv idx, time stride)
 
 
-class _TaehvWeights(ctypes.Structure):
-    _fields_ = [("conv_in", _Conv), ("mem", (_Conv * 3) * 9), ("up", c_vp * 3), ("head", _Conv)]
-
-
-class _TaehvEncWeights(ctypes.Structure):
-    _fields_ = [("conv_in", _Conv), ("down", c_vp * 3), ("mem", (_Conv * 3) * 9), ("head", _Conv)]
-
-
-_SLOT_SIG = [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_size_t)] + [ctypes.POINTER(ctypes.c_int)] * 3
-_lib.EXTRA_SIGNATURES.update({
-    "rtv_taehv_state_slot": _SLOT_SIG,
-    "rtv_taehv_decode": [ctypes.POINTER(_TaehvWeights), c_vp] + [ctypes.c_int] * 4 + [c_vp, ctypes.c_size_t, c_vp, c_vp],
-    "rtv_taehv_conv": [c_vp] * 5 + [ctypes.c_int] * 10 + [c_vp, c_vp],
-    "rtv_taehv_prep": [c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp],                        # used by the tests
-    "rtv_taehv_enc_state_slot": _SLOT_SIG,
-    "rtv_taehv_encode": [ctypes.POINTER(_TaehvEncWeights), c_vp] + [ctypes.c_int] * 6 + [c_vp, ctypes.c_size_t, c_vp,
-                                                                                      ctypes.c_int, ctypes.c_int, c_vp],
-    "rtv_taehv_enc_conv": [c_vp] * 4 + [ctypes.c_int] * 7 + [c_vp, c_vp],
-})
-
-
-@functools.lru_cache(None)
-def _arena_fn(name):
-    """`size_t name(int, int, int)` of the library, its signature registered once."""
-    fn = getattr(_lib.load(), name)
-    fn.restype, fn.argtypes = ctypes.c_size_t, [ctypes.c_int] * 3
-    return fn
+_TaehvWeights = _lib.STRUCTS["rtv_taehv_weights"]
+_TaehvEncWeights = _lib.STRUCTS["rtv_taehv_enc_weights"]
 
 
 def arena_bytes(h, w, t_max):
-    return int(_arena_fn("rtv_taehv_arena_bytes")(h, w, t_max))
+    return int(_lib.load().rtv_taehv_arena_bytes(h, w, t_max))
 
 
 def enc_arena_bytes(H, W, t_max):
-    return int(_arena_fn("rtv_taehv_enc_arena_bytes")(H, W, t_max))
+    return int(_lib.load().rtv_taehv_enc_arena_bytes(H, W, t_max))
 
 
 def fold_tgrow(tgrow_w, conv_w, stride):

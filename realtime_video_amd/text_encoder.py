@@ -21,26 +21,13 @@ import torch
 from . import _lib
 
 c_vp = ctypes.c_void_p
-c_int = ctypes.c_int
 
 UMT5_XXL = dict(vocab=256384, dim=4096, dim_attn=4096, dim_ffn=10240, num_heads=64, num_layers=24, num_buckets=32)
 
 
-class _T5Cfg(ctypes.Structure):
-    _fields_ = [(n, c_int) for n in ("vocab", "dim", "dim_attn", "dim_ffn", "num_heads", "num_layers")] + [("eps", ctypes.c_float)]
-
-
-class _T5Layer(ctypes.Structure):
-    _fields_ = [(n, c_vp) for n in ("norm1_w", "qk_w", "v_w", "o_w", "norm2_w", "gate_fc1_w", "fc2_w", "pos_bias")]
-
-
-class _T5Weights(ctypes.Structure):
-    _fields_ = [("token_embedding", c_vp), ("final_norm_w", c_vp), ("layers", ctypes.POINTER(_T5Layer)), ("max_len", c_int)]
-
-
-_lib.EXTRA_SIGNATURES.update({
-    "rtv_t5_encode": [ctypes.POINTER(_T5Cfg), ctypes.POINTER(_T5Weights), c_vp, c_int, c_int, c_vp, ctypes.c_size_t, c_vp, c_vp],
-})
+_T5Cfg = _lib.STRUCTS["rtv_t5_config"]
+_T5Layer = _lib.STRUCTS["rtv_t5_layer_weights"]
+_T5Weights = _lib.STRUCTS["rtv_t5_weights"]
 
 
 def relative_position_bucket(rel_pos, num_buckets=32, max_dist=128):
@@ -168,8 +155,6 @@ class WanTextEncoder:
         dim = self.cfg["dim"]
         out = torch.empty((B, L, dim), dtype=torch.float32, device=self.device)
         lens = mask.gt(0).sum(dim=1).tolist()
-        _lib.load().rtv_t5_workspace_bytes.restype = ctypes.c_size_t
-        _lib.load().rtv_t5_workspace_bytes.argtypes = [ctypes.POINTER(_T5Cfg), c_int]
         stream = c_vp(torch.cuda.current_stream().cuda_stream)
         for b in range(B):
             n = int(lens[b])

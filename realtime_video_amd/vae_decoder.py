@@ -20,49 +20,11 @@ from . import _lib
 c_vp = ctypes.c_void_p
 
 
-class _Conv(ctypes.Structure):
-    _fields_ = [("w", c_vp), ("b", c_vp)]
-
-
-class _Res(ctypes.Structure):
-    _fields_ = [("gamma0", c_vp), ("conv_a", _Conv), ("gamma3", c_vp), ("conv_b", _Conv), ("shortcut", _Conv)]
-
-
-class _Attn(ctypes.Structure):
-    _fields_ = [(n, c_vp) for n in ("gamma", "wq", "bq", "wk", "bk", "wv", "bv", "wproj", "bproj")]
-
-
-class _VaeWeights(ctypes.Structure):
-    _fields_ = [("conv2_w", c_vp), ("conv2_b", c_vp), ("mean", c_vp), ("std", c_vp), ("conv1", _Conv),
-                ("mid0", _Res), ("mid2", _Res), ("up", _Res * 12), ("attn", _Attn),
-                ("time_conv", _Conv * 2), ("resample", _Conv * 3), ("head_gamma", c_vp), ("head", _Conv)]
-
-
-_lib.EXTRA_SIGNATURES.update({
-    "rtv_conv_cl": [c_vp, c_vp, c_vp, c_vp, ctypes.c_int, c_vp, ctypes.c_int] + [ctypes.c_int] * 10 + [c_vp, c_vp],
-    "rtv_rmsnorm_silu_cl": [c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, c_vp],
-    "rtv_conv3_norm_silu_cl": [c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_int] + [ctypes.c_int] * 6 + [c_vp, c_vp],
-    "rtv_conv_set_fuse_norm": [ctypes.c_int],
-    "rtv_softmax_rows": [c_vp, ctypes.c_int, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp],
-    "rtv_vae_decode": [ctypes.POINTER(_VaeWeights), c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                       c_vp, ctypes.c_size_t, c_vp, c_vp],
-    "rtv_vae_cache_slot": [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t),
-                           ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)],
-    "rtv_conv_cl_win": [c_vp, c_vp, c_vp, c_vp, ctypes.c_int, c_vp, ctypes.c_int] + [ctypes.c_int] * 10 + [c_vp]
-                       + [ctypes.c_int] * 4 + [c_vp],
-    "rtv_vae_decode_rows": [ctypes.POINTER(_VaeWeights), c_vp] + [ctypes.c_int] * 6 + [c_vp, ctypes.c_size_t, c_vp, c_vp],
-    "rtv_vae_decode_single": [ctypes.POINTER(_VaeWeights), c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, ctypes.c_size_t,
-                              c_vp, c_vp],
-    "rtv_conv_set_halo": [ctypes.c_int],
-    "rtv_vae_cache_slot_rows": [ctypes.c_int] * 5 + [ctypes.POINTER(ctypes.c_size_t)] + [ctypes.POINTER(ctypes.c_int)] * 4,
-    # single pieces of the decode / encode paths (used by the tests)
-    "rtv_vae_mid_attention": [ctypes.POINTER(_Attn), c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, ctypes.c_size_t, c_vp],
-    "rtv_vae_prep": [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
-    "rtv_vae_final": [c_vp, c_vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, c_vp],
-    "rtv_vae_upsample_cache_t1": [c_vp, ctypes.c_int64, c_vp],
-    "rtv_vae_enc_prep": [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64, c_vp, c_vp],
-    "rtv_vae_enc_final": [c_vp, ctypes.c_int, ctypes.c_int64, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp],
-})
+# the ABI structs of include/rtv_hip.h, generated from the header
+_Conv = _lib.STRUCTS["rtv_vae_conv"]
+_Res = _lib.STRUCTS["rtv_vae_res"]
+_Attn = _lib.STRUCTS["rtv_vae_attn"]
+_VaeWeights = _lib.STRUCTS["rtv_vae_weights"]
 
 MEAN = [-0.7571, -0.7089, -0.9113, 0.1075, -0.1745, 0.9653, -0.1517, 1.5508,
         0.4134, -0.0715, 0.5517, -0.3632, -0.1922, -0.9497, 0.2503, -0.2921]
@@ -241,10 +203,7 @@ class VAEDecoderWrapper:
 
     # ------------------------------------------------------------------ arena / cache views
     def _new_arena(self, h, w):
-        lib = _lib.load()
-        lib.rtv_vae_arena_bytes_rows.restype = ctypes.c_size_t
-        lib.rtv_vae_arena_bytes_rows.argtypes = [ctypes.c_int] * 4
-        n = lib.rtv_vae_arena_bytes_rows(h, w, *self.row_range(h))
+        n = _lib.load().rtv_vae_arena_bytes_rows(h, w, *self.row_range(h))
         if n == 0:
             raise ValueError("VAE decoder: bad latent size / row range")
         return torch.zeros(n + 256, dtype=torch.uint8, device=self.device)

@@ -15,23 +15,13 @@ import math
 import torch
 
 from . import _lib
-from .vae_decoder import MEAN, STD, CacheArenas, _Attn, _Conv, _Res, pack_conv_weight
+from .vae_decoder import MEAN, STD, CacheArenas, pack_conv_weight
 
 c_vp = ctypes.c_void_p
 c_int = ctypes.c_int
 
 
-class _VaeEncWeights(ctypes.Structure):
-    _fields_ = [("conv1", _Conv), ("down", _Res * 8), ("resample", _Conv * 3), ("time_conv", _Conv * 2),
-                ("mid0", _Res), ("mid2", _Res), ("attn", _Attn), ("head_gamma", c_vp), ("head", _Conv),
-                ("conv1x1_w", c_vp), ("conv1x1_b", c_vp), ("mean", c_vp), ("std", c_vp)]
-
-
-_lib.EXTRA_SIGNATURES.update({
-    "rtv_vae_set_fresh_tap_skip": [c_int],      # include/rtv_hip_lab.h (A/B switch for the tests)
-    "rtv_vae_encode": [ctypes.POINTER(_VaeEncWeights), c_vp] + [c_int] * 6 + [c_vp, ctypes.c_size_t, c_vp, c_int, c_int, c_vp],
-    "rtv_vae_enc_cache_slot": [c_int, c_int, c_int, ctypes.POINTER(ctypes.c_size_t)] + [ctypes.POINTER(c_int)] * 4,
-})
+_VaeEncWeights = _lib.STRUCTS["rtv_vae_enc_weights"]
 
 ENC_DIMS = (96, 96, 192, 384, 384)       # _video_vae: dim 96, dim_mult [1,2,4,4] (wan/modules/vae.py:591-598)
 RES_LAYERS = (0, 1, 3, 4, 6, 7, 9, 10)   # encoder.downsamples.N that are ResidualBlocks
@@ -177,10 +167,7 @@ class VAEEncoderWrapper:
 
     # ------------------------------------------------------------------ arena / cache views
     def _new_arena(self, H, W):
-        lib = _lib.load()
-        lib.rtv_vae_enc_arena_bytes.restype = ctypes.c_size_t
-        lib.rtv_vae_enc_arena_bytes.argtypes = [c_int, c_int]
-        n = lib.rtv_vae_enc_arena_bytes(H, W)
+        n = _lib.load().rtv_vae_enc_arena_bytes(H, W)
         if n == 0:
             raise ValueError(f"VAE encoder: frame size {H}x{W} not supported (multiples of 8, (H/8)(W/8) % 8 == 0)")
         return torch.zeros(n + 256, dtype=torch.uint8, device=self.device)

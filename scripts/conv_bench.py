@@ -17,7 +17,6 @@ from realtime_video_amd.vae_decoder import pack_conv_weight  # noqa: E402
 
 DEV = "cuda"
 lib = _lib.load()
-lib.rtv_conv_set_halo.argtypes = [ctypes.c_int]
 rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 5
 
 

@@ -11,7 +11,6 @@
                                                                # `rocprofv3 --kernel-trace --stats -- python ...`
 """
 import argparse
-import ctypes
 import json
 import os
 import sys
@@ -91,10 +90,7 @@ def main():
     res["taehv_fresh1_ms_runs"], res["wan_fresh1_ms_runs"] = f_taehv, f_wan
     res["fresh1_note"] = "the TAEHV fresh stream presents the frame four times (one full 4-frame group); the Wan encoder runs one frame"
     res["taehv_arena_bytes"] = enc_arena_bytes(H, W, TAEHVEncoder.GROUP)
-    lib = _lib.load()
-    lib.rtv_vae_enc_arena_bytes.restype = ctypes.c_size_t
-    lib.rtv_vae_enc_arena_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
-    res["wan_arena_bytes"] = int(lib.rtv_vae_enc_arena_bytes(H, W))
+    res["wan_arena_bytes"] = int(_lib.load().rtv_vae_enc_arena_bytes(H, W))
     flop = 2.0 * 12 * H * W * 27 * 64                                             # first conv
     flop += 2.0 * 6 * (H // 2) * (W // 2) * 18 * 64 * 64                          # TPool(64, 2) + stride-2 conv, folded
     flop += 2.0 * 3 * (H // 4) * (W // 4) * 18 * 64 * 64 + 2.0 * 3 * (H // 8) * (W // 8) * 9 * 64 * 64

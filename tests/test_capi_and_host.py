@@ -25,15 +25,10 @@ def test_library_exports_every_declared_symbol():
     assert "rtv_attn_set_waves" in syms and "rtv_attn_set_waves" not in boundary
     if not os.environ.get("RTV_LIB_PATH"):
         assert lib.rtv_lab_build() == 0
-    lib.rtv_dit_workspace_bytes.restype = ctypes.c_size_t
-    lib.rtv_vae_arena_bytes.restype = ctypes.c_size_t
-    lib.rtv_vae_arena_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
     # sized for 288 GB HBM: 14.6 GB per decode stream since r06 (concat buffers hold three frames' worth of new slices so that the
     # [cache | new] window slides instead of being copied back per frame; 7.4 GB before)
     assert 5e9 < lib.rtv_vae_arena_bytes(60, 104) < 16e9
     assert "rtv_vae_encode" in syms and "rtv_vae_enc_cache_slot" in syms
-    lib.rtv_vae_enc_arena_bytes.restype = ctypes.c_size_t
-    lib.rtv_vae_enc_arena_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
     assert 3e9 < lib.rtv_vae_enc_arena_bytes(480, 832) < 8e9 and lib.rtv_vae_enc_arena_bytes(481, 832) == 0
 
 

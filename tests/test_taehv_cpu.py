@@ -117,8 +117,6 @@ def test_library_exports_taehv_symbols():
     lib = _lib.load()
     for s in ("rtv_taehv_arena_bytes", "rtv_taehv_state_slot", "rtv_taehv_decode", "rtv_taehv_conv"):
         assert s in _lib.declared_symbols(lab=False) and hasattr(lib, s), s
-    lib.rtv_taehv_arena_bytes.restype = ctypes.c_size_t
-    lib.rtv_taehv_arena_bytes.argtypes = [ctypes.c_int] * 3
     n = lib.rtv_taehv_arena_bytes(60, 104, 3)
     assert 0 < n < 1.5e9, n
     assert lib.rtv_taehv_arena_bytes(60, 104, 0) == 0 and lib.rtv_taehv_arena_bytes(0, 104, 3) == 0

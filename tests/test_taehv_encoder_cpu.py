@@ -127,10 +127,6 @@ def test_library_exports_taehv_encoder_symbols():
     lib = _lib.load()
     for s in ("rtv_taehv_enc_arena_bytes", "rtv_taehv_enc_state_slot", "rtv_taehv_encode", "rtv_taehv_enc_conv"):
         assert s in _lib.declared_symbols(lab=False) and hasattr(lib, s), s
-    lib.rtv_taehv_enc_arena_bytes.restype = ctypes.c_size_t
-    lib.rtv_taehv_enc_arena_bytes.argtypes = [ctypes.c_int] * 3
-    lib.rtv_vae_enc_arena_bytes.restype = ctypes.c_size_t
-    lib.rtv_vae_enc_arena_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
     n = lib.rtv_taehv_enc_arena_bytes(480, 832, 12)
     print(f"TAEHV encoder arena at 480x832, 12 frames per call: {n / 1e9:.3f} GB (Wan encoder: "
           f"{lib.rtv_vae_enc_arena_bytes(480, 832) / 1e9:.3f} GB)")

@@ -137,7 +137,6 @@ def test_halo_conv_kernel_forms_are_bit_identical():
         def fused():
             out = torch.full((T, H, W, 96), float("nan"), dtype=torch.float16, device=DEV)
             fn = lib.rtv_conv3_norm_silu_cl
-            fn.argtypes = _lib.EXTRA_SIGNATURES["rtv_conv3_norm_silu_cl"]
             assert fn(_p(x), _p(wp), _p(b), _p(gamma), _p(out), 96, T, H, W, Cin, 96, 0, _p(zeros), _stream()) == 0
             return out
         both(fused)
@@ -201,7 +200,6 @@ def test_conv_with_fused_rmsnorm_silu_epilogue(Cin, T, H, W):
     def fused(flags=0, cout=Cout, weight=wp):
         out = torch.full((T, H, W, cout), float("nan"), dtype=torch.float16, device=DEV)
         fn = lib.rtv_conv3_norm_silu_cl
-        fn.argtypes = _lib.EXTRA_SIGNATURES["rtv_conv3_norm_silu_cl"]
         st = fn(_p(x), _p(weight), _p(b), _p(gamma), _p(out), cout, T, H, W, Cin, cout, flags, _p(zeros), _stream())
         return st, out
 
@@ -304,7 +302,6 @@ def _mid_attention(x, N, h, w, poison):
     from realtime_video_amd import _lib
     from realtime_video_amd.vae_decoder import _Attn
     lib = _lib.load()
-    lib.rtv_vae_attn_arena_bytes.restype, lib.rtv_vae_attn_arena_bytes.argtypes = ctypes.c_size_t, [ctypes.c_int] * 2
     nbytes = lib.rtv_vae_attn_arena_bytes(h, w)
     assert nbytes > 0
     arena = torch.full((nbytes // 2 + 128,), poison, dtype=torch.float16, device=DEV)

@@ -671,14 +671,11 @@ def test_taehv_prep_restatement_and_slips():
 
 # ------------------------------------------------------------------------------------------------------ the library
 def test_library_exports_vae_unit_symbols():
-    import realtime_video_amd.taehv       # noqa: F401  (register the signatures)
-    import realtime_video_amd.vae_decoder  # noqa: F401
     lib = _lib.load()
     for s in NEW_SYMBOLS:
         assert s in _lib.declared_symbols(lab=False) and hasattr(lib, s), s
-        assert s == "rtv_vae_attn_arena_bytes" or s in _lib.EXTRA_SIGNATURES, s
-    lib.rtv_vae_attn_arena_bytes.restype = ctypes.c_size_t
-    lib.rtv_vae_attn_arena_bytes.argtypes = [ctypes.c_int] * 2
+        restype, argtypes = _lib.PROTOTYPES[s]
+        assert getattr(lib, s).restype is restype and list(getattr(lib, s).argtypes) == argtypes, s
     P, ldp = 60 * 104, 6272
     need = 2 * (P * P + P * ldp + 4 * P * 384 + 384 * ldp)
     assert need <= lib.rtv_vae_attn_arena_bytes(60, 104) <= need + 16 * 256
@@ -687,12 +684,8 @@ def test_library_exports_vae_unit_symbols():
 
 def test_unit_entries_refuse_bad_arguments_on_the_host():
     """Null pointers and out-of-range sizes are refused before anything is launched (no GPU is touched)."""
-    import realtime_video_amd.taehv       # noqa: F401
     import realtime_video_amd.vae_decoder as vd
     lib = _lib.load()
-    for s in NEW_SYMBOLS[1:]:
-        fn = getattr(lib, s)
-        fn.argtypes, fn.restype = _lib.EXTRA_SIGNATURES[s], ctypes.c_int
     p = ctypes.c_void_p(4096)      # never dereferenced: every call below fails its argument check
     null = ctypes.c_void_p(0)
     attn = vd._Attn()
