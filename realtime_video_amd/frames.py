@@ -1,4 +1,4 @@
-"""Output side of the hot path: decoded pixels -> the bytes the serving loop JPEG-encodes.
+"""Output and input side of the hot path.  Output: decoded pixels -> the bytes the serving loop JPEG-encodes.
 
 The reference's frame callback (release_server.py:978-991) copies the decoder's float32 pixels [1, T, 3, H, W] to a
 pinned host tensor on a download stream (after waiting on the event recorded behind the decode), normalises them on
@@ -7,6 +7,12 @@ float path is `mul(255).byte()` in H x W x C order.  `FrameDownloader` is that c
 of the copy (`rtv_pixels_to_rgb8`): the device-to-host transfer carries 1 byte per sample instead of 4 (14.4 MB instead of
 57.5 MB per 12-frame block), the CPU does no arithmetic, and the result is bit-identical
 (`oracle/vae_oracle.frames_to_rgb8`).  JPEG encoding / the WebSocket stay with the caller (control plane, out of scope).
+
+Input: the reference's push_frame (release_server.py:470-487) turns every decoded camera image into a float16 tensor on the
+CPU (`TF.to_tensor(image).to(float16).pin_memory()`), uploads 2 bytes per sample on an upload stream and maps it to [-1, 1]
+there (`sub_(0.5).mul_(2.0)`); frames of another size than the session's are resized per block (v2v.py:153).  `FrameUploader`
+is the mirror image of the downloader: the bytes go up as they are, 1 byte per sample, into a device ring of frame slots, and
+one launch per block (`rtv_frames_from_rgb8`) decodes, resizes and lays out the block's frames for the encoder.
 """
 import torch
 
@@ -67,3 +73,79 @@ class FrameDownloader:
 
     def frame_ids(self, ticket):
         return self._frame_ids[ticket % self.slots]
+
+
+class FrameUploader:
+    """`push(frame)` copies one uint8 [H, W, 3] frame (CPU torch / numpy, or a CUDA tensor) into a pinned ring slot and on into
+    the device ring slot of the same number on the upload stream, and returns a ticket; `gather(tickets, size)` makes the current
+    stream wait for those uploads and returns the frames as float16 [3, T, h, w] in [-1, 1] from one kernel launch.  A ticket is
+    valid until its slot is reused `slots` pushes later, or until a frame of another size reallocates the rings."""
+
+    def __init__(self, device="cuda", slots=32):
+        if slots < 1:
+            raise ValueError("slots must be >= 1")
+        self.device = torch.device(device)
+        self.stream = torch.cuda.Stream(device=self.device)     # release_server.py:88-90 upload_stream
+        self.slots = slots
+        self._host = self._dev = None                           # uint8 [slots, H, W, 3]: pinned ring, device ring
+        self._done = [None] * slots                             # upload of the slot has landed (upload stream)
+        self._read = [None] * slots                             # last gather that reads the slot (its stream)
+        self._n = 0
+        self._first = 0                                         # oldest ticket of the present rings
+
+    def _held(self, ticket):
+        return max(self._first, self._n - self.slots) <= ticket < self._n
+
+    def push(self, frame):
+        if not torch.is_tensor(frame):
+            frame = torch.from_numpy(frame)
+        if frame.dtype != torch.uint8 or frame.dim() != 3 or frame.shape[2] != 3:
+            raise ValueError("FrameUploader.push expects a uint8 [H, W, 3] frame")
+        if self._dev is None or tuple(frame.shape) != tuple(self._dev.shape[1:]):
+            # first frame, or the camera changed resolution: new rings, the old tickets are gone.  Copies in flight keep the old
+            # rings alive (pinned memory and record_stream defer the reuse of their memory), so nothing waits here.
+            self._host = torch.empty((self.slots,) + tuple(frame.shape), dtype=torch.uint8, pin_memory=True)
+            self._dev = torch.empty((self.slots,) + tuple(frame.shape), dtype=torch.uint8, device=self.device)
+            self._dev.record_stream(self.stream)
+            self._done, self._read = [None] * self.slots, [None] * self.slots
+            self._first = self._n
+        slot = self._n % self.slots
+        if self._read[slot] is not None:
+            self.stream.wait_event(self._read[slot])            # a gather may still read the slot the upload overwrites
+        if frame.is_cuda:
+            produced = torch.cuda.Event()
+            produced.record(torch.cuda.current_stream(self.device))
+            self.stream.wait_event(produced)
+            with torch.cuda.stream(self.stream):
+                self._dev[slot].copy_(frame, non_blocking=True)
+                frame.record_stream(self.stream)
+        else:
+            if self._done[slot] is not None:
+                self._done[slot].synchronize()                  # the pinned slot's previous upload must have landed before reuse
+            self._host[slot].copy_(frame)
+            with torch.cuda.stream(self.stream):
+                self._dev[slot].copy_(self._host[slot], non_blocking=True)
+        done = torch.cuda.Event()
+        done.record(self.stream)
+        self._done[slot] = done
+        self._n += 1
+        return self._n - 1
+
+    def gather(self, tickets, size):
+        tickets = [int(t) for t in tickets]
+        for t in tickets:
+            if not self._held(t):
+                raise KeyError(f"ticket {t} is no longer (or not yet) held; {self.slots} slots")
+        if not tickets:
+            raise ValueError("FrameUploader.gather needs at least one ticket")
+        slots = [t % self.slots for t in tickets]
+        current = torch.cuda.current_stream(self.device)
+        for slot in set(slots):
+            current.wait_event(self._done[slot])
+        self._dev.record_stream(current)
+        out = ops.frames_from_rgb8(self._dev, size, slots=slots)
+        read = torch.cuda.Event()
+        read.record(current)
+        for slot in set(slots):
+            self._read[slot] = read
+        return out

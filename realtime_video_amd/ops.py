@@ -454,3 +454,28 @@ def pixels_to_rgb8(pixels, out=None):
         raise ValueError("pixels_to_rgb8: out must be contiguous uint8 [..., H, W, 3]")
     _lib.call("rtv_pixels_to_rgb8", _ptr(pixels), _ptr(out), T, H, W, _stream())
     return out
+
+
+def frames_from_rgb8(rgb8, size, out=None, slots=None):
+    """Camera / decoder bytes uint8 [N, Hin, Win, 3] -> the VAE encoder's input, float16 [3, T, h, w] in [-1, 1]
+    (rtv_frames_from_rgb8): the reference's push_frame arithmetic (release_server.py:479-481) and, when (Hin, Win) != size,
+    the bicubic resize of encode_video_latent (v2v.py:153), one launch per 16 frames.  `slots`: the T frames to take, as indices
+    into N (a ring of frame slots; default all N in order)."""
+    _gpu(rgb8)
+    if rgb8.dtype != torch.uint8 or rgb8.dim() != 4 or rgb8.shape[-1] != 3 or not rgb8.is_contiguous():
+        raise ValueError("frames_from_rgb8 expects contiguous uint8 [T, Hin, Win, 3]")
+    N, Hin, Win = rgb8.shape[:3]
+    h, w = int(size[0]), int(size[1])
+    slots = list(range(N)) if slots is None else [int(i) for i in slots]
+    if any(not 0 <= i < N for i in slots):
+        raise IndexError(f"frames_from_rgb8: slot outside the {N} frames")
+    T = len(slots)
+    if out is None:
+        out = torch.empty((3, T, h, w), dtype=torch.float16, device=rgb8.device)
+    elif out.shape != (3, T, h, w) or out.dtype != torch.float16 or not out.is_contiguous() or out.device != rgb8.device:
+        raise ValueError("frames_from_rgb8: out must be contiguous float16 [3, T, h, w] on the frames' device")
+    for t0 in range(0, T, _lib.FRAMES_MAX):
+        part = slots[t0:t0 + _lib.FRAMES_MAX]
+        _lib.call("rtv_frames_from_rgb8", _ptr(rgb8), (ctypes.c_int * len(part))(*part), Hin * Win * 3, len(part), Hin, Win,
+                  _ptr(out), T, t0, h, w, _stream())
+    return out

@@ -16,7 +16,7 @@ from typing import Callable, Optional
 import torch
 
 from .scheduler import FlowMatchScheduler, get_denoising_schedule
-from .vae_encoder import encode_video_latent
+from .vae_encoder import encode_planar, encode_video_latent
 
 
 @dataclass
@@ -31,7 +31,8 @@ class GenerateParams:
     keep_first_frame: bool = False
     webcam_mode: bool = False          # streaming video-to-video: incoming frames are VAE-encoded every block
     input_frames: object = None        # offline video-to-video: the decoded input video [T, 3, H, W] in [-1, 1] (the reference's
-                                       # `input_video` path / URL after load_video_as_rgb, v2v.py:33-131; file decoding is out of scope)
+                                       # `input_video` path / URL after load_video_as_rgb, v2v.py:33-131; file decoding is out of scope),
+                                       # or the decoder's bytes, uint8 [T, H, W, 3] of any size (the native input path)
     start_frame: object = None         # image-to-video start: PIL image or [3, H, W] tensor in [0, 1] (release_server.py:578-586)
     interp_blocks: int = -1
     kv_cache_num_frames: int = 3
@@ -66,6 +67,8 @@ def resample_array(array, target_length):
 
 
 class GenerationSession:
+    UPLOAD_SLOTS = 64                                 # uint8 frames the upload ring holds (a block takes 12 of those queued)
+
     def __init__(self, params: GenerateParams, models, frame_callback: Optional[Callable] = None, device="cuda",
                  use_taehv=False):
         """use_taehv (the reference's config.use_taehv, release_server.py:350): decode blocks with models.taehv_decoder
@@ -85,7 +88,9 @@ class GenerationSession:
         self.frame_context_cache = deque(maxlen=1 + (params.kv_cache_num_frames - 1) * 4)
         self.decode_vae_cache = [None] * 55
         self.encode_vae_cache = [None] * 55
-        self.frame_queue = deque()                    # webcam / v2v input frames, [3, H, W] in [-1, 1] (release_server.py:470-487)
+        self.frame_queue = deque()                    # webcam / v2v input frames, [3, H, W] in [-1, 1] (release_server.py:470-487),
+        self._queue_is_u8 = False                     # or the upload tickets of uint8 [H, W, 3] frames (push_frame)
+        self.uploader = None                          # frames.FrameUploader, created by the first uint8 frame
         self.interpolated_prompt_embeds = []
         self.num_frame_per_block = 3
         self.rnd = torch.Generator(self.gpu).manual_seed(params.seed if params.seed is not None else 0)
@@ -114,9 +119,12 @@ class GenerationSession:
     # release_server.py:417-428 (+ :529-540 encode_v2v)
     def setup_input_video(self, frames, models):
         """Offline video-to-video: the video's latents, noised to the first step's level with the session generator, replace
-        the noise; the block count follows the video (latent frames / 3 - 1, capped by params.num_blocks)."""
+        the noise; the block count follows the video (latent frames / 3 - 1, capped by params.num_blocks).  `frames`: float
+        [T, 3, H, W] in [-1, 1], or uint8 [T, H, W, 3], which encode_video_latent takes through the native input path."""
         if self._encoder(models) is None:
             raise RuntimeError("input_frames needs a VAE encoder")
+        if isinstance(frames, np.ndarray):
+            frames = torch.from_numpy(frames)
         s0 = self.denoising_step_list[0] / 1000
         latents, _ = encode_video_latent(self._encoder(models), [None] * 55, frames=frames.to(self.gpu), height=self.params.height,
                                          width=self.params.width, stream=False, max_frames=None, resample_to=None)
@@ -181,8 +189,25 @@ class GenerationSession:
 
     # release_server.py:470-487 (queue side) and :489-527
     def push_frame(self, frame):
-        """Queue one input frame [3, H, W] in [-1, 1] (webcam / video-to-video mode)."""
-        self.frame_queue.append(frame)
+        """Queue one input frame (webcam / video-to-video mode): either a float [3, H, W] tensor in [-1, 1], or what a camera or
+        a JPEG decoder delivers, uint8 [H, W, 3] of any size (CPU torch / numpy, or a CUDA tensor).  A uint8 frame goes up as
+        bytes on the session's upload stream (frames.FrameUploader, the reference's upload_stream) and the queue holds its
+        ticket; the block's frames are decoded, resized to the session's size and laid out for the encoder by one kernel launch
+        in process_webcam_frames.  One block's frames are all of one kind."""
+        is_u8 = (frame.dtype == torch.uint8) if torch.is_tensor(frame) else (isinstance(frame, np.ndarray) and frame.dtype == np.uint8)
+        if not self.frame_queue:
+            self._queue_is_u8 = is_u8
+        elif is_u8 != self._queue_is_u8:
+            raise ValueError("push_frame: the queued frames of one block are all uint8 [H, W, 3] or all float [3, H, W]")
+        if not is_u8:
+            self.frame_queue.append(frame)
+            return
+        if self.uploader is None:
+            from .frames import FrameUploader
+            self.uploader = FrameUploader(self.gpu, slots=self.UPLOAD_SLOTS)
+        if len(self.frame_queue) == self.UPLOAD_SLOTS:
+            self.frame_queue.popleft()                # the ring holds this many frames: the oldest queued one gives its slot up
+        self.frame_queue.append(self.uploader.push(frame))
 
     def process_webcam_frames(self, models, idx):
         """Encode the queued input frames of this block with the streaming VAE encoder: 9 frames for block 0 (fresh
@@ -193,6 +218,10 @@ class GenerationSession:
             return None
         frame_list = list(self.frame_queue)
         self.frame_queue.clear()
+        if self._queue_is_u8:                         # tickets of uploaded uint8 frames: one launch makes the encoder's input
+            planar = self.uploader.gather(resample_array(frame_list, n), (self.height, self.width))
+            latents, self.encode_vae_cache = encode_planar(self._encoder(models), self.encode_vae_cache, planar, stream=idx > 0)
+            return latents
         frames = torch.stack(resample_array(frame_list, n)).to(self.gpu)
         latents, self.encode_vae_cache = encode_video_latent(self._encoder(models), self.encode_vae_cache, frames=frames,
                                                              height=self.params.height, width=self.params.width,

@@ -14,7 +14,7 @@ import math
 
 import torch
 
-from . import _lib
+from . import _lib, ops
 from .vae_decoder import MEAN, STD, CacheArenas, pack_conv_weight
 
 c_vp = ctypes.c_void_p
@@ -243,14 +243,35 @@ class VAEEncoderWrapper:
     __call__ = forward
 
 
+def encode_planar(vae, encode_vae_cache, planar, stream=False, dtype=torch.float16):
+    """The tail of encode_video_latent for frames that already are the encoder's input, float16 [3, T, h, w] in [-1, 1]
+    (ops.frames_from_rgb8 / frames.FrameUploader.gather).  Returns (latents [16, T', h/8, w/8], cache)."""
+    latents, encode_vae_cache = vae(planar.to(dtype).unsqueeze(0), encode_vae_cache, stream=stream)
+    return latents.squeeze(0).to(dtype), encode_vae_cache
+
+
 def encode_video_latent(vae, encode_vae_cache, resample_to=16, max_frames=81, video_path_or_url=None, frames=None,
                         height=None, width=None, stream=False, dtype=torch.float16):
     """Mirror of v2v.py:138-158 for in-memory frames [T, 3, H, W] in [-1, 1] (file / URL decoding is outside the hot
-    path).  Returns (latents [16, T', h, w], cache)."""
+    path).  Returns (latents [16, T', h, w], cache).
+
+    uint8 frames [T, Hin, Win, 3], as a camera or a JPEG decoder delivers them, take the native input path instead: the
+    reference's push_frame arithmetic (release_server.py:479-481) and the bicubic resize below in one kernel launch
+    (ops.frames_from_rgb8), straight into the encoder's layout."""
     if frames is None:
         raise NotImplementedError("encode_video_latent: pass decoded frames (video file / URL loading is out of scope)")
     if not frames.is_cuda:
         raise RuntimeError("encode_video_latent needs GPU frames (no CPU fallback)")
+    if frames.dtype == torch.uint8:
+        if frames.dim() != 4 or frames.shape[-1] != 3:
+            raise ValueError("encode_video_latent: uint8 frames are [T, Hin, Win, 3]")
+        h, w = (frames.shape[1:3]) if (height is None and width is None) else (height, width)
+        if max_frames is None:
+            max_frames = 1 + ((frames.shape[0] - 1) // 4) * 4
+        if max_frames:
+            frames = frames[:max_frames]
+        planar = ops.frames_from_rgb8(frames.contiguous(), (h // 8 * 8, w // 8 * 8))
+        return encode_planar(vae, encode_vae_cache, planar, stream=stream, dtype=dtype)
     h, w = (frames.shape[2:]) if (height is None and width is None) else (height, width)
     if max_frames is None:
         max_frames = 1 + ((frames.shape[0] - 1) // 4) * 4
