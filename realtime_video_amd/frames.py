@@ -6,7 +6,10 @@ the CPU (`add_(1.0).mul_(0.5).clamp_(0.0, 1.0)`) and hands every frame to `TF.to
 float path is `mul(255).byte()` in H x W x C order.  `FrameDownloader` is that callback with the arithmetic moved in front
 of the copy (`rtv_pixels_to_rgb8`): the device-to-host transfer carries 1 byte per sample instead of 4 (14.4 MB instead of
 57.5 MB per 12-frame block), the CPU does no arithmetic, and the result is bit-identical
-(`oracle/vae_oracle.frames_to_rgb8`).  JPEG encoding / the WebSocket stay with the caller (control plane, out of scope).
+(`oracle/vae_oracle.frames_to_rgb8`).  JPEG encoding / the WebSocket stay with the caller (control plane, out of scope) -
+unless the caller opts into `JpegFrameDownloader`: the same call protocol, but the block is JPEG-encoded on the device
+(`rtv_jpeg_encode`, csrc/jpeg_encode.hip: baseline 4:2:0 JFIF at the reference's quality 90, one restart interval per MCU row)
+and only the files cross to the host, so the caller needs no CPU encode pool and `fetch` returns bytes ready to send.
 
 Input: the reference's push_frame (release_server.py:470-487) turns every decoded camera image into a float16 tensor on the
 CPU (`TF.to_tensor(image).to(float16).pin_memory()`), uploads 2 bytes per sample on an upload stream and maps it to [-1, 1]
@@ -70,6 +73,104 @@ class FrameDownloader:
         self._done[slot].synchronize()
         T, H, W, C = self._shape[slot]
         return self._host[slot][:T * H * W * C].view(T, H, W, C)
+
+    def frame_ids(self, ticket):
+        return self._frame_ids[ticket % self.slots]
+
+
+class JpegFrameDownloader:
+    """`FrameDownloader`'s call protocol with the JPEG encode in front of the copy: every call enqueues, on the download stream,
+    one `rtv_jpeg_encode` of the block's float pixels, an async copy of the frame offsets and an async copy of the files into
+    one of `slots` pinned buffers, and returns a ticket; `fetch(ticket)` waits for that slot only and returns a list of T
+    memoryviews over the pinned buffer, each a complete JPEG file, valid until the slot is reused `slots` calls later.
+
+    How many bytes a block's files take is known on the device only, so the payload copy is sized by a running estimate:
+    H * W * T / 2 bytes at first, then 1.25 x the largest total seen.  `fetch` reads the true total from the offsets and copies
+    the rest when the estimate fell short (one more copy and wait; the estimate grows).  The device buffer of a slot has
+    `rtv_jpeg_out_bound` bytes, which the files cannot exceed, so nothing is ever encoded twice; it and the arena are cached per
+    slot, and the header travels by value with the launch (nothing is uploaded)."""
+
+    def __init__(self, device="cuda", slots=2, quality=90):
+        if slots < 1:
+            raise ValueError("slots must be >= 1")
+        if not 1 <= int(quality) <= 100:
+            raise ValueError("quality must be in 1..100")
+        self.device = torch.device(device)
+        self.stream = torch.cuda.Stream(device=self.device)     # release_server.py:88-90 download_stream
+        self.slots, self.quality = slots, int(quality)
+        self._key = [None] * slots                              # (T, H, W) the slot's device buffers are sized for
+        self._arena = [None] * slots
+        self._dev = [None] * slots                              # uint8 [rtv_jpeg_out_bound]
+        self._offs = [None] * slots                             # int64 [T + 1] on the device
+        self._host = [None] * slots                             # pinned uint8, grows with the estimate
+        self._host_offs = [None] * slots                        # pinned int64 [T + 1]
+        self._copied = [0] * slots
+        self._done = [None] * slots
+        self._frame_ids = [None] * slots
+        self._largest = 0                                       # largest total of one block seen so far
+        self.topups = 0                                         # fetches whose estimate fell short (each cost one more copy and wait)
+        self._n = 0
+
+    def _estimate(self, T, H, W):
+        return (self._largest * 5 + 3) // 4 if self._largest else T * H * W // 2
+
+    def __call__(self, pixels, frame_ids=(), event=None):
+        if pixels.dim() != 5 or pixels.shape[0] != 1 or pixels.shape[2] != 3:
+            raise ValueError("expected decoder pixels [1, T, 3, H, W]")
+        T, _, H, W = pixels.shape[1:]
+        slot = self._n % self.slots
+        if self._done[slot] is not None:
+            self._done[slot].synchronize()                      # the slot's previous copy must have landed before reuse
+        if self._key[slot] != (T, H, W):
+            bound = ops.jpeg_out_bound(T, H, W)
+            if bound == 0:
+                raise ValueError(f"JpegFrameDownloader: cannot encode {T} frames of {H} x {W} (H and W multiples of 8, "
+                                 "at most RTV_FRAMES_MAX frames per block)")
+            self._arena[slot] = torch.empty(ops.jpeg_arena_bytes(T, H, W), dtype=torch.uint8, device=self.device)
+            self._dev[slot] = torch.empty(bound, dtype=torch.uint8, device=self.device)
+            self._offs[slot] = torch.zeros(T + 1, dtype=torch.int64, device=self.device)
+            self._host_offs[slot] = torch.zeros(T + 1, dtype=torch.int64).pin_memory()
+            self._key[slot] = (T, H, W)
+        n = min(self._estimate(T, H, W), self._dev[slot].numel())
+        if self._host[slot] is None or self._host[slot].numel() < n:
+            self._host[slot] = torch.empty(n, dtype=torch.uint8, pin_memory=True)
+        if event is None:
+            event = torch.cuda.Event()
+            event.record(torch.cuda.current_stream(self.device))
+        self.stream.wait_event(event)                           # :981 download_stream.wait_event(event)
+        with torch.cuda.stream(self.stream):
+            src = pixels[0].float().contiguous()
+            src.record_stream(self.stream)
+            ops.jpeg_encode(src, self.quality, out=self._dev[slot], offsets=self._offs[slot], arena=self._arena[slot])
+            self._host_offs[slot].copy_(self._offs[slot], non_blocking=True)
+            self._host[slot][:n].copy_(self._dev[slot][:n], non_blocking=True)
+            done = torch.cuda.Event()
+            done.record(self.stream)
+        self._done[slot], self._copied[slot], self._frame_ids[slot] = done, n, list(frame_ids)
+        self._n += 1
+        return self._n - 1
+
+    def fetch(self, ticket):
+        if not (self._n - self.slots <= ticket < self._n) or ticket < 0:
+            raise KeyError(f"ticket {ticket} is no longer (or not yet) held; {self.slots} slots")
+        slot = ticket % self.slots
+        self._done[slot].synchronize()
+        offs = self._host_offs[slot].tolist()
+        total, have = offs[-1], self._copied[slot]
+        self._largest = max(self._largest, total)
+        if total > have:                                        # the estimate fell short: the rest, into a buffer that holds it all
+            if self._host[slot].numel() < total:
+                grown = torch.empty((total * 5 + 3) // 4, dtype=torch.uint8, pin_memory=True)
+                grown[:have].copy_(self._host[slot][:have])
+                self._host[slot] = grown
+            with torch.cuda.stream(self.stream):
+                self._host[slot][have:total].copy_(self._dev[slot][have:total], non_blocking=True)
+                self._done[slot].record(self.stream)
+            self._done[slot].synchronize()
+            self._copied[slot] = total
+            self.topups += 1
+        files = memoryview(self._host[slot].numpy())
+        return [files[a:b] for a, b in zip(offs[:-1], offs[1:])]
 
     def frame_ids(self, ticket):
         return self._frame_ids[ticket % self.slots]

@@ -479,3 +479,88 @@ def frames_from_rgb8(rgb8, size, out=None, slots=None):
         _lib.call("rtv_frames_from_rgb8", _ptr(rgb8), (ctypes.c_int * len(part))(*part), Hin * Win * 3, len(part), Hin, Win,
                   _ptr(out), T, t0, h, w, _stream())
     return out
+
+
+# ------------------------------------------------------------------------------------ JPEG frame encoder (include/rtv_hip_jpeg.h)
+def jpeg_header(quality, H, W):
+    """Everything of the JPEG file in front of the entropy-coded data, SOI .. SOS (rtv_jpeg_header; host only, no GPU call)."""
+    buf = ctypes.create_string_buffer(1024)
+    n = _lib.load().rtv_jpeg_header(int(quality), int(H), int(W), buf, len(buf))
+    if n == 0:
+        _lib.check(-1, "rtv_jpeg_header")
+    return buf.raw[:n]
+
+
+def _jpeg_input(x, what):
+    """-> (contiguous tensor, pixels_are_rgb8, T, H, W) for float32 [..., 3, H, W] or uint8 [..., H, W, 3]."""
+    _gpu(x)
+    if x.dtype == torch.float32 and x.dim() >= 3 and x.shape[-3] == 3 and x.is_contiguous():
+        H, W = x.shape[-2:]
+        return x, 0, x.numel() // (3 * H * W), H, W
+    if x.dtype == torch.uint8 and x.dim() >= 3 and x.shape[-1] == 3 and x.is_contiguous():
+        H, W = x.shape[-3:-1]
+        return x, 1, x.numel() // (3 * H * W), H, W
+    raise ValueError(f"{what} expects contiguous float32 [..., 3, H, W] in [-1, 1] or uint8 [..., H, W, 3]")
+
+
+def _jpeg_arena(T, H, W, device, arena):
+    need = jpeg_arena_bytes(T, H, W)
+    if arena is None:
+        # sizes the entry point refuses give 0: it is called all the same, for its message
+        arena = torch.empty(max(need, 16), dtype=torch.uint8, device=device)
+    elif arena.dtype != torch.uint8 or not arena.is_contiguous() or arena.device != device:
+        raise ValueError("arena must be a contiguous uint8 tensor on the pixels' device")
+    return arena
+
+
+def jpeg_arena_bytes(T, H, W):
+    """Bytes of device scratch one jpeg_encode / jpeg_coefficients call of T frames needs (rtv_jpeg_arena_bytes); 0 = refused."""
+    return _lib.load().rtv_jpeg_arena_bytes(int(T), int(H), int(W))
+
+
+def jpeg_out_bound(T, H, W):
+    """Bytes an `out` buffer of T frames can never exceed (rtv_jpeg_out_bound); real frames take a few percent of it."""
+    return _lib.load().rtv_jpeg_out_bound(int(T), int(H), int(W))
+
+
+def jpeg_encode(pixels, quality=90, out=None, offsets=None, arena=None):
+    """Decoder pixels float32 [T, 3, H, W] in [-1, 1], or rgb8 uint8 [T, H, W, 3] -> (uint8 device buffer, int64 device
+    offsets [T + 1]): T complete baseline JPEG files back to back, file t = buffer[offsets[t]:offsets[t + 1]]
+    (rtv_jpeg_encode; three launches on the current stream).
+
+    With `out` (uint8, its numel is the capacity) nothing synchronises: nothing is written beyond it, the offsets hold the true
+    sizes, and offsets[T] > out.numel() means the files are truncated.  Without it the call reads the total back (one
+    synchronisation), encodes again if one byte per pixel did not suffice, and returns a buffer of exactly the total."""
+    pixels, rgb8, T, H, W = _jpeg_input(pixels, "jpeg_encode")
+    dev = pixels.device
+    arena = _jpeg_arena(T, H, W, dev, arena)
+    if offsets is None:
+        offsets = torch.zeros(T + 1, dtype=torch.int64, device=dev)
+    elif offsets.dtype != torch.int64 or offsets.numel() != T + 1 or not offsets.is_contiguous() or offsets.device != dev:
+        raise ValueError("jpeg_encode: offsets must be contiguous int64 [T + 1] on the pixels' device")
+    if out is not None and (out.dtype != torch.uint8 or not out.is_contiguous() or out.device != dev):
+        raise ValueError("jpeg_encode: out must be a contiguous uint8 tensor on the pixels' device")
+
+    def run(buf):
+        _lib.call("rtv_jpeg_encode", _ptr(pixels), rgb8, T, H, W, int(quality), _ptr(arena), arena.numel(), _ptr(buf), buf.numel(),
+                  _ptr(offsets), _stream())
+    if out is not None:
+        run(out)
+        return out, offsets
+    out = torch.empty(T * (H * W + 1024), dtype=torch.uint8, device=dev)
+    run(out)
+    total = int(offsets[-1]) if T else 0
+    if total > out.numel():
+        out = torch.empty(total, dtype=torch.uint8, device=dev)
+        run(out)
+    return out[:total], offsets
+
+
+def jpeg_coefficients(pixels, quality=90, arena=None):
+    """The encoder's first stage alone (rtv_jpeg_coefficients, a unit-test hook): quantised DCT coefficients int16
+    [T, mcu_rows, mcus, 6, 64] - the six blocks of an MCU as Y00 Y01 Y10 Y11 Cb Cr, each in zigzag order."""
+    pixels, rgb8, T, H, W = _jpeg_input(pixels, "jpeg_coefficients")
+    arena = _jpeg_arena(T, H, W, pixels.device, arena)
+    out = torch.empty((T, (H + 15) // 16, (W + 15) // 16, 6, 64), dtype=torch.int16, device=pixels.device)
+    _lib.call("rtv_jpeg_coefficients", _ptr(pixels), rgb8, T, H, W, int(quality), _ptr(arena), arena.numel(), _ptr(out), _stream())
+    return out
