@@ -2,7 +2,8 @@
 STRUCTS (the ABI structs as ctypes.Structure classes), PROTOTYPES (restype / argtypes of every declared function, which load()
 puts on the library) and ABI_VERSION are parsed from the headers at import; nothing restates them by hand.  The pixel input side,
 include/rtv_hip_io.h, is parsed the same way into tables of its own (IO_STRUCTS / IO_PROTOTYPES) until it is folded into rtv_hip.h,
-and so is the frame delivery side, include/rtv_hip_jpeg.h (JPEG_STRUCTS / JPEG_PROTOTYPES).
+and so are the frame delivery side, include/rtv_hip_jpeg.h (JPEG_STRUCTS / JPEG_PROTOTYPES), and the JPEG frame decoder,
+include/rtv_hip_jpeg_decode.h (JPEGDEC_STRUCTS / JPEGDEC_PROTOTYPES).
 
 The product path has no CPU / eager fallback: if the library is missing or a kernel reports an
 error, a RuntimeError is raised (the reference's attention()/pipeline API reports errors as Python
@@ -107,6 +108,10 @@ JPEG_HEADER = "rtv_hip_jpeg.h"   # frame delivery side (JPEG encoder), kept apar
 JPEG_STRUCTS = dict(STRUCTS)
 JPEG_PROTOTYPES = parse_header(_read(JPEG_HEADER), JPEG_STRUCTS)
 JPEG_STRUCTS = {k: v for k, v in JPEG_STRUCTS.items() if k not in STRUCTS}
+JPEGDEC_HEADER = "rtv_hip_jpeg_decode.h"   # frame input side, second half (JPEG decoder): its descriptor struct stays out of STRUCTS
+JPEGDEC_STRUCTS = dict(STRUCTS)
+JPEGDEC_PROTOTYPES = parse_header(_read(JPEGDEC_HEADER), JPEGDEC_STRUCTS)
+JPEGDEC_STRUCTS = {k: v for k, v in JPEGDEC_STRUCTS.items() if k not in STRUCTS}
 FRAMES_MAX = int(re.search(r"^#define\s+RTV_FRAMES_MAX\s+(\d+)", _read(IO_HEADER), flags=re.M).group(1))
 ABI_VERSION = int(re.search(r"^#define\s+RTV_ABI_VERSION\s+(\d+)", _read(HEADERS[0]), flags=re.M).group(1))
 
@@ -145,7 +150,7 @@ def load():
             f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C realtime_video_amd/csrc`). There is no CPU fallback for the HIP path.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(IO_PROTOTYPES.items()) + list(JPEG_PROTOTYPES.items()):
+    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(IO_PROTOTYPES.items()) + list(JPEG_PROTOTYPES.items()) + list(JPEGDEC_PROTOTYPES.items()):
         fn = getattr(lib, name, None)
         if fn is None:
             # RTV_LIB_PATH = an older build of the same C ABI (A/B measurements): entry points added since are simply absent

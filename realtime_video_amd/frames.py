@@ -15,7 +15,9 @@ Input: the reference's push_frame (release_server.py:470-487) turns every decode
 CPU (`TF.to_tensor(image).to(float16).pin_memory()`), uploads 2 bytes per sample on an upload stream and maps it to [-1, 1]
 there (`sub_(0.5).mul_(2.0)`); frames of another size than the session's are resized per block (v2v.py:153).  `FrameUploader`
 is the mirror image of the downloader: the bytes go up as they are, 1 byte per sample, into a device ring of frame slots, and
-one launch per block (`rtv_frames_from_rgb8`) decodes, resizes and lays out the block's frames for the encoder.
+one launch per block (`rtv_frames_from_rgb8`) decodes, resizes and lays out the block's frames for the encoder.  `push_jpeg` takes
+what the reference's push_frame takes, the camera's JPEG file: the file goes up as it arrived (about a tenth of its pixels' bytes)
+and is decoded on the device (`rtv_jpeg_decode`, csrc/jpeg_decode.hip) into the ring slot a raw frame would have landed in.
 """
 import torch
 
@@ -180,7 +182,14 @@ class FrameUploader:
     """`push(frame)` copies one uint8 [H, W, 3] frame (CPU torch / numpy, or a CUDA tensor) into a pinned ring slot and on into
     the device ring slot of the same number on the upload stream, and returns a ticket; `gather(tickets, size)` makes the current
     stream wait for those uploads and returns the frames as float16 [3, T, h, w] in [-1, 1] from one kernel launch.  A ticket is
-    valid until its slot is reused `slots` pushes later, or until a frame of another size reallocates the rings."""
+    valid until its slot is reused `slots` pushes later, or until a frame of another size reallocates the rings.
+
+    `push_jpeg(file)` is `push` for a JPEG file (bytes / bytearray / memoryview): the host parses the marker segments (ValueError
+    for a file the decoder refuses, before anything is queued), descriptor and file go into a pinned slot of a second ring, and
+    the upload stream copies them up and decodes them straight into the rgb8 ring slot (one rtv_jpeg_decode call).  The ticket
+    is of the same kind, raw and JPEG pushes may alternate, `gather` is the same.  `status(ticket)` waits for that upload only and
+    returns the frame's status word (0 = clean; a raw frame's is 0).  A file slot holds the frame's raw size plus 1 KiB: a file
+    larger than its own pixels is refused."""
 
     def __init__(self, device="cuda", slots=32):
         if slots < 1:
@@ -193,24 +202,34 @@ class FrameUploader:
         self._read = [None] * slots                             # last gather that reads the slot (its stream)
         self._n = 0
         self._first = 0                                         # oldest ticket of the present rings
+        self._jhost = self._jdev = None                         # uint8 [slots, cap]: descriptor plus file, pinned ring / device ring
+        self._jshape = None                                     # the frame size the file rings are sized for
+        self._jarena = None                                     # the decoder's scratch: calls are serial on the upload stream
+        self._jstatus = self._jstatus_host = None               # int32 [slots]: device, pinned
+        self._is_jpeg = [False] * slots
 
     def _held(self, ticket):
         return max(self._first, self._n - self.slots) <= ticket < self._n
+
+    def _rings(self, shape):
+        if self._dev is None or tuple(shape) != tuple(self._dev.shape[1:]):
+            # first frame, or the camera changed resolution: new rings, the old tickets are gone.  Copies in flight keep the old
+            # rings alive (pinned memory and record_stream defer the reuse of their memory), so nothing waits here.
+            self._host = torch.empty((self.slots,) + tuple(shape), dtype=torch.uint8, pin_memory=True)
+            self._dev = torch.empty((self.slots,) + tuple(shape), dtype=torch.uint8, device=self.device)
+            self._dev.record_stream(self.stream)
+            self._done, self._read = [None] * self.slots, [None] * self.slots
+            self._first = self._n
+            self._jshape = None                                 # the file rings go with them: their slots' events are gone too
 
     def push(self, frame):
         if not torch.is_tensor(frame):
             frame = torch.from_numpy(frame)
         if frame.dtype != torch.uint8 or frame.dim() != 3 or frame.shape[2] != 3:
             raise ValueError("FrameUploader.push expects a uint8 [H, W, 3] frame")
-        if self._dev is None or tuple(frame.shape) != tuple(self._dev.shape[1:]):
-            # first frame, or the camera changed resolution: new rings, the old tickets are gone.  Copies in flight keep the old
-            # rings alive (pinned memory and record_stream defer the reuse of their memory), so nothing waits here.
-            self._host = torch.empty((self.slots,) + tuple(frame.shape), dtype=torch.uint8, pin_memory=True)
-            self._dev = torch.empty((self.slots,) + tuple(frame.shape), dtype=torch.uint8, device=self.device)
-            self._dev.record_stream(self.stream)
-            self._done, self._read = [None] * self.slots, [None] * self.slots
-            self._first = self._n
+        self._rings(frame.shape)
         slot = self._n % self.slots
+        self._is_jpeg[slot] = False
         if self._read[slot] is not None:
             self.stream.wait_event(self._read[slot])            # a gather may still read the slot the upload overwrites
         if frame.is_cuda:
@@ -231,6 +250,60 @@ class FrameUploader:
         self._done[slot] = done
         self._n += 1
         return self._n - 1
+
+    def push_jpeg(self, data):
+        import ctypes
+        if isinstance(data, (bytearray, memoryview)):
+            data = bytes(data)
+        if not isinstance(data, bytes):
+            raise TypeError("FrameUploader.push_jpeg expects a JPEG file as bytes, bytearray or memoryview")
+        info = ops.jpeg_parse(data)                             # ValueError for a refusal: nothing has been queued
+        shape = (info.H, info.W, 3)
+        cap = (ops.JPEG_DESC_BYTES + info.H * info.W * 3 + 1024 + 15) // 16 * 16
+        n = ops.JPEG_DESC_BYTES + len(data)
+        if n > cap:
+            raise ValueError(f"FrameUploader.push_jpeg: a file of {len(data)} bytes for {info.H} x {info.W} pixels is larger than "
+                             "its own raw pixels; decode it on the host and push the pixels")
+        self._rings(shape)
+        if self._jshape != shape:
+            self._jhost = torch.empty((self.slots, cap), dtype=torch.uint8, pin_memory=True)
+            self._jdev = torch.empty((self.slots, cap), dtype=torch.uint8, device=self.device)
+            self._jdev.record_stream(self.stream)
+            self._jshape = shape
+        if self._jstatus is None:
+            self._jstatus = torch.zeros(self.slots, dtype=torch.int32, device=self.device)
+            self._jstatus.record_stream(self.stream)
+            self._jstatus_host = torch.zeros(self.slots, dtype=torch.int32).pin_memory()
+        need = ops.jpeg_decode_arena_bytes([info])
+        if self._jarena is None or self._jarena.numel() < need:
+            self._jarena = torch.empty(need, dtype=torch.uint8, device=self.device)
+            self._jarena.record_stream(self.stream)
+        slot = self._n % self.slots
+        if self._read[slot] is not None:
+            self.stream.wait_event(self._read[slot])            # a gather may still read the slot the decode overwrites
+        if self._done[slot] is not None:
+            self._done[slot].synchronize()                      # the pinned slot's previous upload must have landed before reuse
+        at = self._jhost[slot].data_ptr()
+        ctypes.memmove(at, ctypes.byref(info.desc), ops.JPEG_DESC_BYTES)
+        ctypes.memmove(at + ops.JPEG_DESC_BYTES, data, len(data))
+        with torch.cuda.stream(self.stream):
+            self._jdev[slot, :n].copy_(self._jhost[slot, :n], non_blocking=True)
+            ops.jpeg_decode_frames([info], [self._jdev[slot]], [self._dev[slot]], self._jstatus[slot:slot + 1], self._jarena)
+            self._jstatus_host[slot:slot + 1].copy_(self._jstatus[slot:slot + 1], non_blocking=True)
+        done = torch.cuda.Event()
+        done.record(self.stream)
+        self._done[slot], self._is_jpeg[slot] = done, True
+        self._n += 1
+        return self._n - 1
+
+    def status(self, ticket):
+        if not self._held(int(ticket)):
+            raise KeyError(f"ticket {ticket} is no longer (or not yet) held; {self.slots} slots")
+        slot = int(ticket) % self.slots
+        if not self._is_jpeg[slot]:
+            return 0
+        self._done[slot].synchronize()
+        return int(self._jstatus_host[slot])
 
     def gather(self, tickets, size):
         tickets = [int(t) for t in tickets]

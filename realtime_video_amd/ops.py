@@ -564,3 +564,126 @@ def jpeg_coefficients(pixels, quality=90, arena=None):
     out = torch.empty((T, (H + 15) // 16, (W + 15) // 16, 6, 64), dtype=torch.int16, device=pixels.device)
     _lib.call("rtv_jpeg_coefficients", _ptr(pixels), rgb8, T, H, W, int(quality), _ptr(arena), arena.numel(), _ptr(out), _stream())
     return out
+
+
+# ----------------------------------------------------------------------------- JPEG frame decoder (include/rtv_hip_jpeg_decode.h)
+JPEG_DESC_BYTES = ctypes.sizeof(_lib.JPEGDEC_STRUCTS["rtv_jpeg_desc"])
+
+
+class JpegInfo:
+    """What jpeg_parse makes of a file's marker segments: H, W, components (1 or 3), sampling (luma blocks per MCU, horizontal x
+    vertical), restart_interval (MCUs, 0 = none), file_bytes, and `desc`, the rtv_jpeg_desc the decode calls take; `packed()` is
+    its bytes, which go in front of the file's bytes on the device."""
+
+    def __init__(self, desc):
+        self.desc = desc
+        self.H, self.W, self.components = desc.height, desc.width, desc.components
+        self.sampling = (desc.hsamp, desc.vsamp)
+        self.restart_interval, self.file_bytes = desc.restart_interval, desc.file_bytes
+
+    def packed(self):
+        return ctypes.string_at(ctypes.byref(self.desc), JPEG_DESC_BYTES)
+
+
+def _jpeg_bytes(data, what):
+    if isinstance(data, (bytearray, memoryview)):
+        data = bytes(data)
+    if not isinstance(data, bytes):
+        raise TypeError(f"{what} expects a JPEG file as bytes, bytearray or memoryview, not {type(data).__name__}")
+    return data
+
+
+def jpeg_parse(data):
+    """A JPEG file (bytes-like) -> JpegInfo (rtv_jpeg_parse; host only, no GPU call).  ValueError with the reason for a file
+    outside what the decoder accepts - progressive, CMYK, 12 bit, other sampling, a missing table, a cut header, above the caps:
+    a server can hand that one frame to PIL and push its pixels instead."""
+    data = _jpeg_bytes(data, "jpeg_parse")
+    lib = _lib.load()
+    desc = _lib.JPEGDEC_STRUCTS["rtv_jpeg_desc"]()
+    if lib.rtv_jpeg_parse(data, len(data), ctypes.byref(desc)) != 0:
+        raise ValueError(lib.rtv_last_error().decode("utf-8", "replace"))
+    return JpegInfo(desc)
+
+
+def jpeg_decode_arena_bytes(infos):
+    """Bytes of device scratch one jpeg_decode call of these frames needs (rtv_jpeg_decode_arena_bytes); 0 = refused."""
+    descs = (_lib.JPEGDEC_STRUCTS["rtv_jpeg_desc"] * max(len(infos), 1))(*[i.desc for i in infos])
+    return _lib.load().rtv_jpeg_decode_arena_bytes(descs, len(infos))
+
+
+def jpeg_decode_frames(infos, frames, outs, status, arena, rounds=None, subseq_bits=0):
+    """The call itself (rtv_jpeg_decode, two launches on the current stream): infos [T] JpegInfo; frames [T] uint8 CUDA tensors,
+    each a frame's descriptor plus file (16-byte aligned); outs [T] uint8 [H, W, 3] CUDA tensors; status int32 [T]; arena uint8;
+    rounds int32 [T] or None.  Nothing is allocated and nothing synchronises."""
+    T = len(infos)
+    if not (len(frames) == len(outs) == T) or T > _lib.FRAMES_MAX:
+        raise ValueError(f"jpeg_decode: as many frames as outputs, at most {_lib.FRAMES_MAX} per call")
+    _gpu(status, arena, rounds, *frames, *outs)
+    for info, f, o in zip(infos, frames, outs):
+        if f.dtype != torch.uint8 or not f.is_contiguous() or f.numel() < JPEG_DESC_BYTES + info.file_bytes:
+            raise ValueError("jpeg_decode: a frame must be a contiguous uint8 tensor of descriptor plus file")
+        if o.dtype != torch.uint8 or tuple(o.shape) != (info.H, info.W, 3) or not o.is_contiguous():
+            raise ValueError("jpeg_decode: an output must be contiguous uint8 [H, W, 3] of the file's size")
+    if status.dtype != torch.int32 or status.numel() < T or not status.is_contiguous():
+        raise ValueError("jpeg_decode: status must be contiguous int32 [T]")
+    if rounds is not None and (rounds.dtype != torch.int32 or rounds.numel() < T or not rounds.is_contiguous()):
+        raise ValueError("jpeg_decode: rounds must be contiguous int32 [T]")
+    if arena.dtype != torch.uint8 or not arena.is_contiguous():
+        raise ValueError("jpeg_decode: arena must be a contiguous uint8 tensor")
+    descs = (_lib.JPEGDEC_STRUCTS["rtv_jpeg_desc"] * T)(*[i.desc for i in infos])
+    fp = (ctypes.c_void_p * T)(*[f.data_ptr() for f in frames])
+    op = (ctypes.c_void_p * T)(*[o.data_ptr() for o in outs])
+    _lib.call("rtv_jpeg_decode", descs, fp, op, T, int(subseq_bits), _ptr(arena), arena.numel(), _ptr(status), _ptr(rounds), _stream())
+
+
+def _jpeg_upload(file, device, what):
+    """bytes-like -> (JpegInfo, uint8 CUDA tensor of descriptor plus file)."""
+    if torch.is_tensor(file):
+        _gpu(file)
+        raise TypeError(f"{what} expects JPEG files as bytes-like objects")
+    data = _jpeg_bytes(file, what)
+    info = jpeg_parse(data)
+    host = torch.frombuffer(bytearray(info.packed() + data), dtype=torch.uint8)
+    return info, host.to(device)
+
+
+def jpeg_decode(files, out=None, status=None, arena=None, subseq_bits=0, device="cuda"):
+    """JPEG files (a list of bytes-like objects, which may differ in size and sampling) -> (list of uint8 [H, W, 3] CUDA tensors,
+    int32 status tensor [T], 0 = clean, else RTV_JPEG_STATUS_* bits): PIL's `Image.open(...).convert("RGB")` pixels, decoded on
+    the device (rtv_jpeg_decode).  ValueError for a file the parser refuses.  `out`: a list of output tensors to fill."""
+    files = list(files)
+    pairs = [_jpeg_upload(f, device, "jpeg_decode") for f in files]
+    infos, frames = [p[0] for p in pairs], [p[1] for p in pairs]
+    dev = frames[0].device if frames else torch.device(device)
+    if out is None:
+        out = [torch.empty((i.H, i.W, 3), dtype=torch.uint8, device=dev) for i in infos]
+    if status is None:
+        status = torch.zeros(len(files), dtype=torch.int32, device=dev)
+    for t0 in range(0, len(files), _lib.FRAMES_MAX):
+        part = slice(t0, t0 + _lib.FRAMES_MAX)
+        need = jpeg_decode_arena_bytes(infos[part])
+        a = arena if arena is not None else torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+        jpeg_decode_frames(infos[part], frames[part], out[part], status[part], a, subseq_bits=subseq_bits)
+    return out, status
+
+
+def jpeg_decode_coefficients(file, subseq_bits=0, device="cuda"):
+    """The decoder's entropy stage alone (rtv_jpeg_decode_coefficients, a unit-test hook) -> (one int16 tensor [block_rows,
+    block_cols, 64] per component: the quantised coefficients in natural order over the padded block grid; status int32 [1];
+    rounds int32 [1], the synchronisation rounds taken).  subseq_bits: bits of the scan per thread, 0 = the default."""
+    info, frame = _jpeg_upload(file, device, "jpeg_decode_coefficients")
+    need = jpeg_decode_arena_bytes([info])
+    d = info.desc
+    shapes = [(d.mcu_rows * (d.vsamp if c == 0 else 1), d.mcu_cols * (d.hsamp if c == 0 else 1), 64) for c in range(d.components)]
+    n = sum(s[0] * s[1] * 64 for s in shapes)
+    arena = torch.empty(max(need, 16), dtype=torch.uint8, device=frame.device)
+    flat = torch.empty(n, dtype=torch.int16, device=frame.device)
+    status = torch.zeros(1, dtype=torch.int32, device=frame.device)
+    rounds = torch.zeros(1, dtype=torch.int32, device=frame.device)
+    _lib.call("rtv_jpeg_decode_coefficients", ctypes.byref(d), _ptr(frame), int(subseq_bits), _ptr(arena), arena.numel(), _ptr(flat),
+              _ptr(status), _ptr(rounds), _stream())
+    out, at = [], 0
+    for s in shapes:
+        out.append(flat[at:at + s[0] * s[1] * 64].view(s))
+        at += s[0] * s[1] * 64
+    return out, status, rounds

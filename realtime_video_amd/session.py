@@ -6,6 +6,7 @@ the server's WebSocket queue) and `interpolate_prompt_embeds` (:459-468).  Host 
 on PyTorch-ROCm exactly as in the reference; every forward it issues is the native `rtv_dit_forward` / VAE
 kernel path.  The web layer (FastAPI / WebSocket / JPEG encoding) is outside the hot-path scope.
 """
+import base64
 import types
 from collections import deque
 
@@ -193,8 +194,19 @@ class GenerationSession:
         a JPEG decoder delivers, uint8 [H, W, 3] of any size (CPU torch / numpy, or a CUDA tensor).  A uint8 frame goes up as
         bytes on the session's upload stream (frames.FrameUploader, the reference's upload_stream) and the queue holds its
         ticket; the block's frames are decoded, resized to the session's size and laid out for the encoder by one kernel launch
-        in process_webcam_frames.  One block's frames are all of one kind."""
-        is_u8 = (frame.dtype == torch.uint8) if torch.is_tensor(frame) else (isinstance(frame, np.ndarray) and frame.dtype == np.uint8)
+        in process_webcam_frames.  One block's frames are all of one kind.
+
+        The reference's own input kinds (release_server.py:470-487) are taken too: a bytes-like object is a JPEG file, a str is
+        its base64 text with an optional `data:...,` prefix.  The file goes up as it arrived and is decoded on the device into the
+        slot a uint8 frame would have landed in (FrameUploader.push_jpeg), so it counts as a uint8 frame; ValueError for a file
+        the decoder refuses (progressive, CMYK, ...): decode that one with PIL and push its pixels."""
+        if isinstance(frame, str):                    # :474-477
+            if frame.startswith("data:"):
+                frame = frame[frame.index(",") + 1:]
+            frame = base64.b64decode(frame)
+        is_jpeg = isinstance(frame, (bytes, bytearray, memoryview))
+        is_u8 = is_jpeg or ((frame.dtype == torch.uint8) if torch.is_tensor(frame)
+                            else (isinstance(frame, np.ndarray) and frame.dtype == np.uint8))
         if not self.frame_queue:
             self._queue_is_u8 = is_u8
         elif is_u8 != self._queue_is_u8:
@@ -205,9 +217,10 @@ class GenerationSession:
         if self.uploader is None:
             from .frames import FrameUploader
             self.uploader = FrameUploader(self.gpu, slots=self.UPLOAD_SLOTS)
+        ticket = self.uploader.push_jpeg(frame) if is_jpeg else self.uploader.push(frame)   # a refused file raises: nothing queued
         if len(self.frame_queue) == self.UPLOAD_SLOTS:
             self.frame_queue.popleft()                # the ring holds this many frames: the oldest queued one gives its slot up
-        self.frame_queue.append(self.uploader.push(frame))
+        self.frame_queue.append(ticket)
 
     def process_webcam_frames(self, models, idx):
         """Encode the queued input frames of this block with the streaming VAE encoder: 9 frames for block 0 (fresh
