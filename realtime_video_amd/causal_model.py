@@ -16,7 +16,7 @@ import types
 
 import torch
 
-from . import _lib, ops
+from . import _lib, lora, ops
 from .rope import rope_cos_sin_table
 
 c_vp = ctypes.c_void_p
@@ -118,6 +118,9 @@ class CausalWanModel:
         self._graphs = {}
         self._weights_version = 0     # part of the graph key: a captured graph embeds weight pointers and the launch sequence
         self._cfg = _Cfg(dim, ffn_dim, num_heads, num_layers, freq_dim, text_dim, text_len, in_dim, out_dim, eps, 0, 0)
+        self._lora = {}               # name -> {"scale": float, "targets": {target: lora.Target with A / B on the device}}, in load order
+        self._lora_base = {}          # _tensors key -> bf16 copy of the matrix as loaded; kept outside _tensors / parameters()
+        self.lora_version = 0         # bumps when a merge changes ck_w / cv_w: crossattn_cache entries carry the one they were made with
 
     # ------------------------------------------------------------------ nn.Module-ish conveniences
     def eval(self):
@@ -257,6 +260,9 @@ class CausalWanModel:
         self._layers_arr = layers
         self._tensors, self._w = t, w
         self._cfg.use_fp8 = 0           # (a reload replaces quantised weights; enable_fp8() again to re-quantise)
+        if self._lora or self._lora_base:
+            self._lora, self._lora_base = {}, {}      # adapters belong to the weights they were merged into
+            self.lora_version += 1
         self._graphs.clear()            # captured graphs point at the previous weights
         self._weights_version += 1
         return _IncompatibleKeys([], [] if strict else unexpected)
@@ -279,11 +285,9 @@ class CausalWanModel:
         scales = (ctypes.c_float * (len(_FP8_TOP) + len(_FP8_LAYER) * self.num_layers))()
 
         def quant(key):
-            w = self._tensors[key]
-            s = w.float().abs().max().clamp(min=1e-12) / 448.0      # on the GPU, like torchao's choose-scale
-            q = (w.float() / s).clamp(-448.0, 448.0).to(torch.float8_e4m3fn).contiguous()
+            q, s = self._quantize_fp8(self._tensors[key])
             self._tensors[key] = q
-            return q, float(s)
+            return q, s
 
         for i, name in enumerate(_FP8_TOP):
             q, scales[i] = quant(name)
@@ -300,6 +304,99 @@ class CausalWanModel:
         self._ws.clear()                  # the workspace grows by the fp8 activation buffer
         ops.ensure_gemm_workspace(self.device)
         return self
+
+    @staticmethod
+    def _quantize_fp8(w):
+        """bf16 matrix -> (e4m3 matrix, scale): the per-tensor quantisation of enable_fp8 (and of a LoRA re-merge under fp8)."""
+        s = w.float().abs().max().clamp(min=1e-12) / 448.0      # on the GPU, like torchao's choose-scale
+        q = (w.float() / s).clamp(-448.0, 448.0).to(torch.float8_e4m3fn).contiguous()
+        return q, float(s)
+
+    # ------------------------------------------------------------------ LoRA adapters (lora.py, include/rtv_hip_lora.h)
+    def lora_adapters(self):
+        """{name: scale} of the loaded adapters, in load order."""
+        return {name: ad["scale"] for name, ad in self._lora.items()}
+
+    def load_lora(self, sd, scale=1.0, name=None, strict=True):
+        """Merge a LoRA state dict (lora.parse_lora_state_dict names the accepted keys) into the weights IN PLACE, at strength
+        `scale`; returns the adapter's name.  The first adapter that touches a matrix keeps a bf16 copy of it (the base); every
+        change re-merges each touched matrix from its base with all adapters on it, so results never depend on history.  Weight
+        pointers do not move: captured hipGraphs stay valid.  Load adapters BEFORE enable_fp8(): afterwards the bf16 weights are gone.
+        (A device bf16 tensor that load_state_dict kept without a copy is shared with the caller's state dict and changes with it.)"""
+        targets, _ = lora.parse_lora_state_dict(sd, self.state_dict_shapes(), strict=strict)
+        scale = float(scale)
+        if scale != scale or scale in (float("inf"), float("-inf")):
+            raise ValueError("load_lora: scale must be finite")
+        if name is None:
+            n = len(self._lora)
+            while f"lora{n}" in self._lora:
+                n += 1
+            name = f"lora{n}"
+        if name in self._lora:
+            raise ValueError(f"load_lora: an adapter named {name!r} is loaded already")
+        if len(self._lora) >= lora.MAX_ADAPTERS:
+            raise RuntimeError(f"load_lora: at most {lora.MAX_ADAPTERS} adapters are loaded at once (RTV_LORA_MAX_ADAPTERS)")
+        if self.device.type != "cuda":
+            raise RuntimeError("load_lora: the merge is a HIP kernel and this model lives on the CPU (no CPU fallback)")
+        if self._w is None:
+            raise RuntimeError("load weights before load_lora()")
+        if self._cfg.use_fp8:
+            raise RuntimeError("load_lora after enable_fp8(): the bf16 weights are gone - load adapters first, then enable_fp8()")
+        dev, bf = self.device, torch.bfloat16
+        on_dev = {t: tg._replace(A=tg.A.detach().to(device=dev, dtype=bf).contiguous(),
+                                 B=tg.B.detach().to(device=dev, dtype=bf).contiguous()) for t, tg in targets.items()}
+        for tg in on_dev.values():
+            if tg.tensor not in self._lora_base:
+                self._lora_base[tg.tensor] = self._tensors[tg.tensor].clone()
+        self._lora[name] = {"scale": scale, "targets": on_dev}
+        self._remerge({tg.tensor for tg in on_dev.values()})
+        return name
+
+    def set_lora_scale(self, name, scale):
+        """Strength of a loaded adapter; the touched matrices are re-merged from their bases (tens of milliseconds at 14B)."""
+        if name not in self._lora:
+            raise KeyError(f"no LoRA adapter named {name!r} (loaded: {list(self._lora)})")
+        scale = float(scale)
+        if scale != scale or scale in (float("inf"), float("-inf")):
+            raise ValueError("set_lora_scale: scale must be finite")
+        self._lora[name]["scale"] = scale
+        self._remerge({tg.tensor for tg in self._lora[name]["targets"].values()})
+
+    def unload_lora(self, name=None):
+        """Drop one adapter (None: all of them).  A matrix no adapter targets any more is restored bit for bit and its base freed."""
+        if name is not None and name not in self._lora:
+            raise KeyError(f"no LoRA adapter named {name!r} (loaded: {list(self._lora)})")
+        touched = set()
+        for n in [name] if name is not None else list(self._lora):
+            touched |= {tg.tensor for tg in self._lora.pop(n)["targets"].values()}
+        self._remerge(touched)
+
+    def _remerge(self, keys):
+        """Rebuild the matrices `keys` from their bases with every adapter on them: one rtv_lora_merge per matrix, per q / k / v
+        row block of a fused qkv_w.  bf16: into the live weight, in place.  fp8: into a temporary bf16 matrix, re-quantised with
+        enable_fp8's routine into the existing e4m3 buffer; its scale is replaced and the graphs, which may hold it by value, go."""
+        fp8, cross = bool(self._cfg.use_fp8), False
+        for key in sorted(keys):
+            base = self._lora_base[key]
+            live = [(ad["scale"], tg) for ad in self._lora.values() for tg in ad["targets"].values() if tg.tensor == key]
+            out = torch.empty_like(base) if fp8 else self._tensors[key]
+            blocks = ((0, base.shape[0]),) if not key.endswith(".qkv_w") else tuple((j * self.dim, self.dim) for j in range(3))
+            for row0, rows in blocks:
+                lora.merge(base[row0:row0 + rows], out[row0:row0 + rows],
+                           [(tg.A, tg.B, s * tg.factor) for s, tg in live if (tg.row0, tg.rows) == (row0, rows)])
+            if fp8:
+                q, s = self._quantize_fp8(out)
+                self._tensors[key].copy_(q)
+                layer, field = key[1:].split(".")
+                self._fp8_scales[len(_FP8_TOP) + len(_FP8_LAYER) * int(layer) + _FP8_LAYER.index(field)] = s
+            if not live:
+                del self._lora_base[key]
+            cross = cross or key.endswith((".ck_w", ".cv_w"))
+        if fp8 and keys:
+            self._graphs.clear()
+            self._weights_version += 1
+        if cross:
+            self.lora_version += 1        # text K / V rows in a crossattn_cache were made with the old ck_w / cv_w
 
     def init_random_weights(self, seed=0, std=0.02):
         """Synthetic weights of the right architecture generated directly on the GPU (bench.py: there is no
@@ -471,7 +568,8 @@ class CausalWanModel:
         tt = t.reshape(-1).to(device=u.device, dtype=torch.float32).contiguous()
         if tt.numel() != F:
             raise ValueError("t must hold one timestep per latent frame")
-        need_cross = not all(bool(c["is_init"]) for c in crossattn_cache)
+        # (a cache filled under other LoRA weights is not initialised: its text K / V rows came from the old ck_w / cv_w)
+        need_cross = not all(bool(c["is_init"]) and int(c.get("lora_version", 0)) == self.lora_version for c in crossattn_cache)
         ctx = None
         if need_cross:
             cu = context[0] if not torch.is_tensor(context) else context[0]
@@ -691,6 +789,7 @@ class CausalWanModel:
         if need_cross:
             for c in crossattn_cache:
                 c["is_init"] = True
+                c["lora_version"] = self.lora_version
         return out.unsqueeze(0)
 
     def forward(self, *args, **kwargs):

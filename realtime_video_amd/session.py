@@ -362,6 +362,11 @@ class GenerationSession:
         self.resume_latents = None
         return pixels if pixels is not None else denoised_pred
 
+    def set_lora_scale(self, name, scale):
+        """Strength of a loaded LoRA adapter, between two blocks of a running session: the model re-merges the touched weights
+        in place and the next block runs with them (its KV recompute pass refreshes the self-attention state)."""
+        self.models.transformer.set_lora_scale(name, scale)
+
     def generate_block(self, models=None):
         out = self.generate_block_internal(models or self.models)
         if out is None:

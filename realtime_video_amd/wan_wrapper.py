@@ -83,6 +83,19 @@ class WanDiffusionWrapper:
     def eval(self):
         return self
 
+    # ---- LoRA adapters: the model's methods (causal_model.py)
+    def load_lora(self, sd, scale=1.0, name=None, strict=True):
+        return self.model.load_lora(sd, scale=scale, name=name, strict=strict)
+
+    def set_lora_scale(self, name, scale):
+        return self.model.set_lora_scale(name, scale)
+
+    def unload_lora(self, name=None):
+        return self.model.unload_lora(name)
+
+    def lora_adapters(self):
+        return self.model.lora_adapters()
+
     def get_scheduler(self):
         return self.scheduler
 
