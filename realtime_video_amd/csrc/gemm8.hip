@@ -3,7 +3,8 @@
 //
 // One workgroup = 8 waves on one CU, two waves per SIMD.  Waves 0-3 ("group 0", output rows 0-127) and waves 4-7
 // ("group 1", rows 128-255) run the SAME phase program staggered by one s_barrier, so on every SIMD one wave is in its
-// MFMA segment while its partner is in its LDS segment.  A K-tile (64 deep) is TWO phases of 16 MFMA 32x32x16 each:
+// MFMA segment while its partner is in its LDS segment.  A K-tile (64 deep) is TWO phases of 32 MFMA 16x16x32 each (16 of 32x32x16
+// in the RTV_G8_MFMA16=0 build; the MFMA time of a phase is the same):
 //
 //   interval 4t+0:  g0  LDS  X(t): W[n0], W[n1], A[m0]  (16 ds_read_b128)        g1  MFMA Y(t-1)
 //   interval 4t+1:  g0  MFMA X(t): (m0; n0, n1) + stage A0, A1 of tile t+2       g1  LDS  X(t)
@@ -38,6 +39,21 @@
 #include "gemm_core.h"
 #include "gemm_split.h"
 #include "rtv_internal.h"
+
+// The matrix instruction is v_mfma_f32_16x16x32_bf16 (RTV_G8_MFMA16, the default).  Lane l reads row l & 15 of a 16-row block,
+// 16-byte chunk 4 ks + (l >> 4) for the two 32-deep steps ks of a K-tile (conflict-free under the same swizzle: in every
+// ds_read_b128 lane group rows 2i and 2i + 1 share a chunk position in opposite bank halves and the group's eight i take eight
+// positions); a phase is 32 MFMAs on af[4][2] / bfr[4][2] (16 reads, 64 registers) and `f32x4 acc[8][4]` (128 registers), a DMA
+// piece behind every eighth.  Under the power cap the chip holds a higher clock on this shape than on 32x32x16 at equal cycles
+// per flop: 6-7 % less time on the four M = 4680 layer shapes (profiles/mfma_shape_microbench.txt, mfma_shape_gemm8_ab.txt),
+// and the results are bit-identical with the 32x32x16 form (one 32-deep step leaves the same fp32 bits as two 16-deep ones on
+// this hardware; the GEMM identity tests tie this kernel to gemm5.hip and gemm.hip, which stay on 32x32x16).
+// A/B: make EXTRA=-DRTV_G8_MFMA16=0 BUILD=build_m32 OUT=../librtv_hip_m32.so is the same kernel on 32x32x16 (tile, waves, LDS
+// image, DMA pieces, counted waits, idle-wave loop, tail forms and supertile map are shared; only fragments and accumulators
+// differ).  One body per build: a second instantiation in this translation unit cost ffn-in 3.8 % in r05.
+#ifndef RTV_G8_MFMA16
+#define RTV_G8_MFMA16 1
+#endif
 
 namespace rtv {
 
@@ -134,16 +150,17 @@ __global__ __launch_bounds__(g8::THREADS, 2) void gemm8_kernel(GemmParams p, Spl
   }
 #ifdef RTV_GEMM_TIMELINE
   const unsigned long long tl_t0 = __builtin_amdgcn_s_memrealtime();
+  const unsigned long long tl_c0 = __builtin_amdgcn_s_memtime();   // shader cycles: with tl_t0 / tl_t1 the in-kernel clock
   unsigned long long tl_t1 = 0;
 #endif
-  typedef TileCfg<256, 256, 64, 2, 4> Cfg;  // epilogue geometry: 4 x 2 blocks of 32x32 per wave
+  [[maybe_unused]] typedef TileCfg<256, 256, 64, 2, 4> Cfg;  // epilogue geometry: 4 x 2 blocks of 32x32 per wave
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave >> 2, wc = wave & 3;
-  const int l31 = lane & 31, g = lane >> 5;
+  [[maybe_unused]] const int l31 = lane & 31, g = lane >> 5;
 
   // ---- workgroup -> (tile, K segment)
   const int nk_total = p.K / BK;
@@ -186,6 +203,37 @@ __global__ __launch_bounds__(g8::THREADS, 2) void gemm8_kernel(GemmParams p, Spl
 
   // ---- fragment addressing: A rows of this wave live in half `wr`, W rows in half wc >> 1
   const int b_row0 = (wc & 1) * 64;
+#if RTV_G8_MFMA16
+  const int l15 = lane & 15, q4 = lane >> 4;
+  u32x4 af[4][2];   // current 64-row A half: [16-row block][32-deep step]
+  u32x4 bfr[4][2];  // the four 16-column W blocks of the K-tile: [n-block][32-deep step]
+  auto read_a = [&](int a3, int mq) {
+    const char* s = smem + A_OFF + (a3 * 2 + wr) * HALF_BYTES;
+#pragma unroll
+    for (int mb = 0; mb < 4; ++mb) {
+      const int row = mq * 64 + mb * 16 + l15;
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) af[mb][ks] = *(const u32x4*)(s + row * 128 + (swz(row, ks * 4 + q4) << 4));
+    }
+  };
+  auto read_w = [&](int wb) {
+    const char* s = smem + W_OFF + (wb * 2 + (wc >> 1)) * HALF_BYTES;
+#pragma unroll
+    for (int nb = 0; nb < 4; ++nb) {
+      const int row = b_row0 + nb * 16 + l15;
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) bfr[nb][ks] = *(const u32x4*)(s + row * 128 + (swz(row, ks * 4 + q4) << 4));
+    }
+  };
+
+  f32x4 acc[8][4];
+#pragma unroll
+  for (int mi = 0; mi < 8; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < 4; ++ni)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) acc[mi][ni][r] = 0.f;
+#else
   u32x4 af[2][4];   // current 64-row A half: [m-block][k-step]
   u32x4 bfr[2][4];  // both 32-column W blocks of the K-tile: [n-block][k-step]
   auto read_a = [&](int a3, int mq) {
@@ -214,8 +262,16 @@ __global__ __launch_bounds__(g8::THREADS, 2) void gemm8_kernel(GemmParams p, Spl
     for (int ni = 0; ni < 2; ++ni)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
+#endif
 
 #define G8_FENCE() __builtin_amdgcn_sched_barrier(0)
+#if RTV_G8_MFMA16   // the epilogues of the accumulator layout in use (gemm_core.h); the block counts are deduced from `acc`
+#define G8_STORE_LDS(...) store_tile_lds16<F16>(__VA_ARGS__)
+#define G8_STORE_DIRECT(CFG, ...) store_tile16<F16>(__VA_ARGS__)
+#else
+#define G8_STORE_LDS(...) store_tile_lds<F16>(__VA_ARGS__)
+#define G8_STORE_DIRECT(CFG, ...) store_tile<F16, CFG>(__VA_ARGS__)
+#endif
 #define G8_BARRIER()                  \
   do {                                \
     G8_FENCE();                       \
@@ -228,7 +284,8 @@ __global__ __launch_bounds__(g8::THREADS, 2) void gemm8_kernel(GemmParams p, Spl
     G8_FENCE();                                         \
   } while (0)
 
-  // MFMA segment: 16 MFMA on the 64 x 64 half (mq; n0, n1) with 4 DMA pieces between them (halves h0, h0 + 1 of K-tile
+  // MFMA segment: 32 MFMA 16x16x32 (16 of 32x32x16 in the RTV_G8_MFMA16=0 build) on the 64 x 64 half (mq; n0, n1) with 4 DMA pieces
+  // between them, one behind every eighth (fourth) MFMA (halves h0, h0 + 1 of K-tile
   // st_kt): an LDS-DMA costs 60-180 issue cycles inside an LDS segment but ~10 behind an MFMA.
   // A wave whose 128 rows all lie beyond M (M = 4680: waves 4-7 of the last row of tiles) has nothing to multiply: it keeps
   // its barriers and its DMA duty (the pieces it stages are other waves' operands) and skips fragment reads and MFMAs.
@@ -236,6 +293,22 @@ __global__ __launch_bounds__(g8::THREADS, 2) void gemm8_kernel(GemmParams p, Spl
   auto mma_half = [&](int mq, int st_kt, int st_a3, int h0, auto chk) {
     __builtin_amdgcn_s_setprio(1);
     int n = 0;
+#if RTV_G8_MFMA16
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+      for (int nb = 0; nb < 4; ++nb)
+#pragma unroll
+        for (int mb = 0; mb < 4; ++mb) {
+          acc[mq * 4 + mb][nb] = Mfma16<F16>::run(bfr[nb][ks], af[mb][ks], acc[mq * 4 + mb][nb]);
+          ++n;
+          if ((n & 7) == 4) {   // the same four pieces, behind every eighth MFMA
+            G8_FENCE();
+            stage_piece(st_kt, st_a3, h0 + (n >> 4), (n >> 3) & 1, chk);
+            G8_FENCE();
+          }
+        }
+#else
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
@@ -250,6 +323,7 @@ __global__ __launch_bounds__(g8::THREADS, 2) void gemm8_kernel(GemmParams p, Spl
             G8_FENCE();
           }
         }
+#endif
     __builtin_amdgcn_s_setprio(0);
   };
 
@@ -320,8 +394,9 @@ __global__ __launch_bounds__(g8::THREADS, 2) void gemm8_kernel(GemmParams p, Spl
   //      release/acquire; the slab is a per-lane register image, so the reduce is a plain elementwise add)
 #ifdef RTV_GEMM_TIMELINE
   tl_t1 = __builtin_amdgcn_s_memrealtime();
+  const unsigned long long tl_c1 = __builtin_amdgcn_s_memtime();
   bool reducer = true;
-  if (is_split) reducer = split_k_reduce<4>(acc, sp, unit, seg, tile_id, smem, tid, wave, lane);
+  if (is_split) reducer = split_k_reduce(acc, sp, unit, seg, tile_id, smem, tid, wave, lane);
   if (!reducer) {
     if (g_timeline && tid == 0) {
       unsigned long long* t = g_timeline + (size_t)blockIdx.x * 4;
@@ -333,7 +408,7 @@ __global__ __launch_bounds__(g8::THREADS, 2) void gemm8_kernel(GemmParams p, Spl
     return;
   }
 #else
-  if (is_split && !split_k_reduce<4>(acc, sp, unit, seg, tile_id, smem, tid, wave, lane)) return;
+  if (is_split && !split_k_reduce(acc, sp, unit, seg, tile_id, smem, tid, wave, lane)) return;
 #endif
 
   // ---- epilogue through LDS when the output / residual rows allow 16-byte accesses (always on the DiT path)
@@ -342,7 +417,7 @@ __global__ __launch_bounds__(g8::THREADS, 2) void gemm8_kernel(GemmParams p, Spl
     if (is_split) __syncthreads();   // the reducer's flag word lives in smem[0..4)
 #ifdef RTV_GEMM_TIMELINE
     unsigned long long tl_mid = 0;
-    store_tile_lds<F16, 4>(p, m0 + wr * 128, n0 + wc * 64, lane, smem + wave * (128 * 128), acc, &tl_mid);
+    G8_STORE_LDS(p, m0 + wr * 128, n0 + wc * 64, lane, smem + wave * (128 * 128), acc, &tl_mid);
     if (g_timeline && tid == 0) g_timeline[(size_t)blockIdx.x * 4 + 1] = tl_mid | (1ull << 63);   // replaces the K-loop stamp
     tl_t1 = tl_t1 ? tl_t1 : 0;
     if (g_timeline && tid == 0) {
@@ -351,13 +426,14 @@ __global__ __launch_bounds__(g8::THREADS, 2) void gemm8_kernel(GemmParams p, Spl
       t[2] = __builtin_amdgcn_s_memrealtime();
       t[3] = ((unsigned long long)(is_split ? seg + 1 : 0) << 32) | (unsigned)tile_id;
       g_timeline[(size_t)(gridDim.x + blockIdx.x) * 4] = tl_t1;    // K-loop end in the second half of the buffer
+      g_timeline[(size_t)(gridDim.x + blockIdx.x) * 4 + 1] = tl_c1 - tl_c0;   // ... and its shader cycles (start of kernel -> K-loop end)
     }
     return;
 #else
-    store_tile_lds<F16, 4>(p, m0 + wr * 128, n0 + wc * 64, lane, smem + wave * (128 * 128), acc);
+    G8_STORE_LDS(p, m0 + wr * 128, n0 + wc * 64, lane, smem + wave * (128 * 128), acc, nullptr);
 #endif
   } else {
-    store_tile<F16, Cfg>(p, m0 + wr * 128, n0 + wc * 64, lane, acc);
+    G8_STORE_DIRECT(Cfg, p, m0 + wr * 128, n0 + wc * 64, lane, acc);
   }
 #ifdef RTV_GEMM_TIMELINE
   if (g_timeline && tid == 0) {
@@ -398,7 +474,7 @@ __device__ __forceinline__ void gemm8m_body(const GemmParams& p, const SplitArgs
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave >> 2, wc = wave & 3;
-  const int l31 = lane & 31, g = lane >> 5;
+  [[maybe_unused]] const int l31 = lane & 31, g = lane >> 5;
 
   uint32_t src_off[3][2];  // [A, W0, W1][piece]: byte offsets at k = 0
   {
@@ -421,6 +497,34 @@ __device__ __forceinline__ void gemm8m_body(const GemmParams& p, const SplitArgs
                                              src_off[h][j], (unsigned)kt * (BK * 2), 0, 0);
   };
 
+#if RTV_G8_MFMA16
+  const int l15 = lane & 15, q4 = lane >> 4;
+  u32x4 af[4][2], bfr[4][2];
+  auto read_frags = [&](int b3) {
+    const char* sa = smem + (b3 * 3) * HALF_BYTES;
+    const char* sw = smem + (b3 * 3 + 1 + (wc >> 1)) * HALF_BYTES;
+#pragma unroll
+    for (int nb = 0; nb < 4; ++nb) {
+      const int row = (wc & 1) * 64 + nb * 16 + l15;
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) bfr[nb][ks] = *(const u32x4*)(sw + row * 128 + (g8::swz(row, ks * 4 + q4) << 4));
+    }
+#pragma unroll
+    for (int mb = 0; mb < 4; ++mb) {
+      const int row = wr * 64 + mb * 16 + l15;
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) af[mb][ks] = *(const u32x4*)(sa + row * 128 + (g8::swz(row, ks * 4 + q4) << 4));
+    }
+  };
+
+  f32x4 acc[4][4];
+#pragma unroll
+  for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < 4; ++ni)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) acc[mi][ni][r] = 0.f;
+#else
   u32x4 af[2][4], bfr[2][4];
   auto read_frags = [&](int b3) {
     const char* sa = smem + (b3 * 3) * HALF_BYTES;
@@ -446,6 +550,7 @@ __device__ __forceinline__ void gemm8m_body(const GemmParams& p, const SplitArgs
     for (int ni = 0; ni < 2; ++ni)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
+#endif
 
   // ---- prologue: K-tiles 0 and 1 by everybody, K-tile 2 by group 1 (what its MFMA(-1) would have staged)
 #pragma unroll
@@ -482,11 +587,29 @@ __device__ __forceinline__ void gemm8m_body(const GemmParams& p, const SplitArgs
     read_frags(b3);
     G8_LDS_DONE();
     G8_BARRIER();
-    // ---------------- MFMA segment: 16 MFMA + the 6 pieces of K-tile kt + 2 + group, then the counted wait
+    // ---------------- MFMA segment: 32 MFMA 16x16x32 (16 of 32x32x16 with RTV_G8_MFMA16=0) + the 6 pieces of K-tile kt + 2 + group,
+    //                  then the counted wait
     const int st_kt = kt + 2 + wr;
     const int st_b = wr ? b3 : (b3 == 0 ? 2 : b3 - 1);   // (kt + 3) % 3 = b3 for group 1, (kt + 2) % 3 for group 0
     __builtin_amdgcn_s_setprio(1);
     int n = 0;
+#if RTV_G8_MFMA16
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+      for (int nb = 0; nb < 4; ++nb)
+#pragma unroll
+        for (int mb = 0; mb < 4; ++mb) {
+          acc[mb][nb] = Mfma16<F16>::run(bfr[nb][ks], af[mb][ks], acc[mb][nb]);
+          ++n;
+          if (n == 4 || n == 8 || n == 14 || n == 20 || n == 24 || n == 30) {   // the same six pieces at twice the MFMA count
+            const int pc = n == 4 ? 0 : n == 8 ? 1 : n == 14 ? 2 : n == 20 ? 3 : n == 24 ? 4 : 5;
+            G8_FENCE();
+            stage_piece(st_kt, st_b, pc >> 1, pc & 1, chk);
+            G8_FENCE();
+          }
+        }
+#else
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
@@ -502,6 +625,7 @@ __device__ __forceinline__ void gemm8m_body(const GemmParams& p, const SplitArgs
             G8_FENCE();
           }
         }
+#endif
     __builtin_amdgcn_s_setprio(0);
     G8_FENCE();
     // retire everything but the pieces just issued: K-tile kt + 1 (+ group) becomes readable after the next barrier
@@ -515,15 +639,15 @@ __device__ __forceinline__ void gemm8m_body(const GemmParams& p, const SplitArgs
   for (; kt < kt_end; ++kt) k_tile(kt, std::true_type{});
   if (wr == 0) G8_BARRIER();  // group 0 closes the stagger
 
-  if (is_split && !split_k_reduce<2>(acc, sp, unit, seg, tile_id, smem, tid, wave, lane)) return;
+  if (is_split && !split_k_reduce(acc, sp, unit, seg, tile_id, smem, tid, wave, lane)) return;
 
   const bool wide = !((p.ldc | (p.residual ? p.ldr : 0)) & 7) && !(((uintptr_t)p.C | (uintptr_t)p.residual) & 15);
   if (wide) {
     if (is_split) __syncthreads();
-    store_tile_lds<F16, 2>(p, m0 + wr * 64, n0 + wc * 64, lane, smem + wave * (64 * 128), acc);
+    G8_STORE_LDS(p, m0 + wr * 64, n0 + wc * 64, lane, smem + wave * (64 * 128), acc, nullptr);
   } else {
-    typedef TileCfg<128, 256, 64, 2, 4> CfgM;
-    store_tile<F16, CfgM>(p, m0 + wr * 64, n0 + wc * 64, lane, acc);
+    [[maybe_unused]] typedef TileCfg<128, 256, 64, 2, 4> CfgM;
+    G8_STORE_DIRECT(CfgM, p, m0 + wr * 64, n0 + wc * 64, lane, acc);
   }
 }
 

@@ -62,6 +62,17 @@ struct Mfma32<true> {
   static __device__ __forceinline__ float hi_f32(uint32_t u) { return f16_to_f32((uint16_t)(u >> 16)); }
 };
 
+// The 16x16x32 form of the same product (4 f32 per lane per 16 x 16 block; swapped operands as above: lane l owns output row
+// m = l & 15 and the 4 consecutive columns n = 4 (l >> 4) + r).  Under the power cap the chip holds a higher clock on this shape
+// (scripts/micro/mfma_shape.hip, profiles/mfma_shape_microbench.txt); conversions and packing are Mfma32's.
+template <bool F16>
+struct Mfma16 : Mfma32<F16> {
+  static __device__ __forceinline__ f32x4 run(const u32x4& a, const u32x4& b, const f32x4& c) {
+    if constexpr (F16) return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+    else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+  }
+};
+
 // LDS tile geometry shared by the GEMM and the implicit-GEMM conv kernels.
 template <int BM, int BN, int BK, int WM, int WN>
 struct TileCfg {
@@ -293,6 +304,123 @@ __device__ __forceinline__ void store_tile_lds(const GemmParams& p, int m_base, 
     if (p.act == 0) store_tile_lds_impl<F16, TM, 0, false>(p, m_base, n_base, lane, img, acc, mid_stamp);
     else if (p.act == 1) store_tile_lds_impl<F16, TM, 1, false>(p, m_base, n_base, lane, img, acc, mid_stamp);
     else store_tile_lds_impl<F16, TM, 2, false>(p, m_base, n_base, lane, img, acc, mid_stamp);
+  }
+}
+
+// ---------------------------------------------------------------- the same two epilogues for 16x16x32 accumulators
+// acc[mb][nb]: lane l holds row 16 mb + (l & 15), columns 16 nb + 4 (l >> 4) + r of the wave's TMB*16 x 64 block.
+template <bool F16, int TMB>
+__device__ __forceinline__ void store_tile16(const GemmParams& p, int m_base, int n_base, int lane, f32x4 (&acc)[TMB][4]) {
+  const int l15 = lane & 15, q = lane >> 4;
+#pragma unroll
+  for (int mb = 0; mb < TMB; ++mb) {
+    const int m = m_base + mb * 16 + l15;
+    if (m >= p.M) continue;
+#pragma unroll
+    for (int nb = 0; nb < 4; ++nb) {
+      const int n = n_base + nb * 16 + q * 4;
+      if (n < p.N) {
+        float v4[4] = {acc[mb][nb][0], acc[mb][nb][1], acc[mb][nb][2], acc[mb][nb][3]};
+        epilogue_quad<F16>(p, m, n, v4);
+      }
+    }
+  }
+}
+
+// store_tile_lds for that layout: same rounding points, same batched bias / gate loads, same row-contiguous 16-byte global accesses;
+// only the register -> LDS-image writes differ.  A lane writes 8 bytes at row r = 16 mb + (l & 15), 8-byte slot s = 4 nb + (l >> 4)
+// of the row's 16; it goes to slot s ^ (r & 15).  ds_write_b64 is serviced in groups of 16 consecutive lanes = the 16 rows of a block
+// at one s: 16 distinct slots -> conflict-free.  In 16-byte chunks that is chunk c of row r at c ^ ((r >> 1) & 7) with its halves
+// swapped when r & 1: a ds_read_b128 lane group holds, per 128-byte bank half (r & 1), the chunks {0-3} of one row pair and {4-7}
+// of another ({0-3} ^ i and {4-7} ^ i stay disjoint for i < 8, and neighbouring pairs differ in bit 0 of i only): conflict-free.
+template <bool F16, int TMB, int ACT, bool GATE>
+__device__ __forceinline__ void store_tile_lds16_impl(const GemmParams& p, int m_base, int n_base, int lane, char* img,
+                                                      f32x4 (&acc)[TMB][4], unsigned long long* mid_stamp) {
+  typedef Mfma32<F16> T;
+  const int l15 = lane & 15, q = lane >> 4;
+  int ncol[4];
+  u32x2 bq[4];
+#pragma unroll
+  for (int nb = 0; nb < 4; ++nb) {
+    ncol[nb] = min(n_base + nb * 16 + q * 4, p.N - 4);
+    bq[nb] = p.bias ? *(const u32x2*)(p.bias + ncol[nb]) : u32x2{0u, 0u};
+  }
+#pragma unroll
+  for (int mb = 0; mb < TMB; ++mb) {
+    const int row = mb * 16 + l15;
+    u32x2 gq[4];
+    if (GATE) {
+      const uint16_t* gp = p.gate + (size_t)((p.row_offset + min(m_base + row, p.M - 1)) / p.rows_per_frame) * p.gate_stride;
+#pragma unroll
+      for (int nb = 0; nb < 4; ++nb) gq[nb] = *(const u32x2*)(gp + ncol[nb]);
+    }
+#pragma unroll
+    for (int nb = 0; nb < 4; ++nb) {
+      float v[4] = {acc[mb][nb][0], acc[mb][nb][1], acc[mb][nb][2], acc[mb][nb][3]};
+      v[0] += T::lo_f32(bq[nb][0]);   // (zero quads without a bias: + 0 is exact)
+      v[1] += T::hi_f32(bq[nb][0]);
+      v[2] += T::lo_f32(bq[nb][1]);
+      v[3] += T::hi_f32(bq[nb][1]);
+      if (ACT == 1) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = gelu_tanh(T::round(v[i]));
+      } else if (ACT == 2) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = silu(T::round(v[i]));
+      }
+      if (GATE) {
+        v[0] = T::round(v[0]) * T::lo_f32(gq[nb][0]);
+        v[1] = T::round(v[1]) * T::hi_f32(gq[nb][0]);
+        v[2] = T::round(v[2]) * T::lo_f32(gq[nb][1]);
+        v[3] = T::round(v[3]) * T::hi_f32(gq[nb][1]);
+      }
+      u32x2 o;
+      o[0] = T::pack2(v[0], v[1]);
+      o[1] = T::pack2(v[2], v[3]);
+      *(u32x2*)(img + row * 128 + (((nb * 4 + q) ^ l15) << 3)) = o;
+    }
+  }
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
+  if (mid_stamp) *mid_stamp = __builtin_amdgcn_s_memrealtime();   // lab builds: end of the register -> LDS pass
+  const int rsub = lane >> 3, c = lane & 7;
+  const int n = n_base + c * 8;
+  const bool n_ok = n < p.N;
+  constexpr int PASSES = TMB * 2;   // 8 rows per pass
+  u32x4 res[PASSES];
+  if (p.residual) {
+#pragma unroll
+    for (int ps = 0; ps < PASSES; ++ps) {
+      const int m = min(m_base + ps * 8 + rsub, p.M - 1);
+      res[ps] = *(const u32x4*)(p.residual + (size_t)m * p.ldr + min(n, p.N - 8));
+    }
+  }
+#pragma unroll
+  for (int ps = 0; ps < PASSES; ++ps) {
+    const int row = ps * 8 + rsub;
+    const int m = m_base + row;
+    u32x4 t = *(const u32x4*)(img + row * 128 + ((c ^ ((row >> 1) & 7)) << 4));
+    if (row & 1) t = u32x4{t[2], t[3], t[0], t[1]};
+    if (p.residual) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        t[i] = T::pack2(T::lo_f32(t[i]) + T::lo_f32(res[ps][i]), T::hi_f32(t[i]) + T::hi_f32(res[ps][i]));
+    }
+    if (m < p.M && n_ok) *(u32x4*)(p.C + (size_t)m * p.ldc + n) = t;
+  }
+}
+
+template <bool F16, int TMB>
+__device__ __forceinline__ void store_tile_lds16(const GemmParams& p, int m_base, int n_base, int lane, char* img,
+                                                 f32x4 (&acc)[TMB][4], unsigned long long* mid_stamp = nullptr) {
+  if (p.gate) {
+    if (p.act == 0) store_tile_lds16_impl<F16, TMB, 0, true>(p, m_base, n_base, lane, img, acc, mid_stamp);
+    else if (p.act == 1) store_tile_lds16_impl<F16, TMB, 1, true>(p, m_base, n_base, lane, img, acc, mid_stamp);
+    else store_tile_lds16_impl<F16, TMB, 2, true>(p, m_base, n_base, lane, img, acc, mid_stamp);
+  } else {
+    if (p.act == 0) store_tile_lds16_impl<F16, TMB, 0, false>(p, m_base, n_base, lane, img, acc, mid_stamp);
+    else if (p.act == 1) store_tile_lds16_impl<F16, TMB, 1, false>(p, m_base, n_base, lane, img, acc, mid_stamp);
+    else store_tile_lds16_impl<F16, TMB, 2, false>(p, m_base, n_base, lane, img, acc, mid_stamp);
   }
 }
 

@@ -70,11 +70,12 @@ __device__ __forceinline__ bool split_unit_of_block(const SplitArgs& sp, int bid
 
 // device: publish this unit's partial 128x64-per-wave accumulators; the last arriver of the tile returns true with
 // the full sum in `acc` (placement-independent: the slab is a per-lane register image, the reduce is elementwise).
-// `smem` needs 4 free bytes at offset 0 (the K loop is over).  8 waves, acc = [4][2] blocks of 32x32 per wave.
-template <int TM>   // 32x32 blocks per wave: TM x 2 (the 256-row kernel: 4, the 128-row kernel: 2)
-__device__ __forceinline__ bool split_k_reduce(f32x16 (&acc)[TM][2], const SplitArgs& sp, int unit, int seg, int tile_id,
-                                               char* smem, int tid, int wave, int lane) {
-  constexpr int NB = TM * 2;
+// `smem` needs 4 free bytes at offset 0 (the K loop is over).  8 waves; the wrappers below pass 32x32 blocks (f32x16 acc[TM][2]) or
+// 16x16 blocks (f32x4 acc[TMB][4]).  The slab is a per-lane register image: NQ quads of 4 floats per lane, whatever their grouping into MFMA blocks (`get(qi)` /
+// `set(qi, v)`: quad qi of the caller's accumulators, compile-time foldable under full unrolling).
+template <int NQ, class Get, class Set>
+__device__ __forceinline__ bool split_k_reduce_quads(Get get, Set set, const SplitArgs& sp, int unit, int seg, int tile_id,
+                                                     char* smem, int tid, int wave, int lane) {
   // Publish with WRITE-THROUGH (sc1) 16-byte stores + a per-wave drain, then ONE relaxed agent-scope ticket: no release
   // fence.  A release fence is `buffer_wbl2`, which writes back every dirty line of the XCD's L2 - at the end of a GEMM that
   // is megabytes of other workgroups' freshly written output tiles (measured: the 16 split units of the FFN-in GEMM cost
@@ -82,14 +83,10 @@ __device__ __forceinline__ bool split_k_reduce(f32x16 (&acc)[TM][2], const Split
   __amdgpu_buffer_rsrc_t slab =
       __builtin_amdgcn_make_buffer_rsrc((void*)(sp.slabs + (size_t)unit * SPLIT_SLAB_FLOATS), 0, SPLIT_SLAB_FLOATS * 4, 0x00020000);
 #pragma unroll
-  for (int blk = 0; blk < NB; ++blk)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const f32x16& a = acc[blk >> 1][blk & 1];
-      const f32x4 v = {a[4 * q], a[4 * q + 1], a[4 * q + 2], a[4 * q + 3]};
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), slab, (((wave * NB + blk) * 4 + q) * 64 + lane) * 16, 0,
-                                             /*aux: sc1*/ 16);
-    }
+  for (int qi = 0; qi < NQ; ++qi) {
+    const f32x4 v = get(qi);
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), slab, ((wave * NQ + qi) * 64 + lane) * 16, 0, /*aux: sc1*/ 16);
+  }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // every storing wave drains its write-through stores
   __syncthreads();
   int* flag = (int*)smem;
@@ -112,26 +109,48 @@ __device__ __forceinline__ bool split_k_reduce(f32x16 (&acc)[TM][2], const Split
   // zero and adds all S slabs in index order.
   if (sp.S > 2) {
 #pragma unroll
-    for (int blk = 0; blk < NB; ++blk)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[blk >> 1][blk & 1][r] = 0.f;
+    for (int qi = 0; qi < NQ; ++qi) set(qi, f32x4{0.f, 0.f, 0.f, 0.f});
   }
   for (int s = 0; s < sp.S; ++s) {
     if (s == seg && sp.S == 2) continue;
     const float4* other = (const float4*)(sp.slabs + (size_t)(unit0 + s) * SPLIT_SLAB_FLOATS);
 #pragma unroll
-    for (int blk = 0; blk < NB; ++blk)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const float4 v = other[((wave * NB + blk) * 4 + q) * 64 + lane];
-        f32x16& a = acc[blk >> 1][blk & 1];
-        a[4 * q] += v.x;
-        a[4 * q + 1] += v.y;
-        a[4 * q + 2] += v.z;
-        a[4 * q + 3] += v.w;
-      }
+    for (int qi = 0; qi < NQ; ++qi) {
+      const float4 v = other[(wave * NQ + qi) * 64 + lane];
+      f32x4 a = get(qi);
+      a[0] += v.x;
+      a[1] += v.y;
+      a[2] += v.z;
+      a[3] += v.w;
+      set(qi, a);
+    }
   }
   return true;
+}
+
+template <int TM>   // 32x32 blocks per wave: TM x 2 (the 256-row kernel: 4, the 128-row kernel: 2); quad = registers 4q .. 4q + 3 of a block
+__device__ __forceinline__ bool split_k_reduce(f32x16 (&acc)[TM][2], const SplitArgs& sp, int unit, int seg, int tile_id,
+                                               char* smem, int tid, int wave, int lane) {
+  return split_k_reduce_quads<TM * 8>(
+      [&](int qi) __attribute__((always_inline)) {
+        const f32x16& a = acc[qi >> 3][(qi >> 2) & 1];
+        const int q = qi & 3;
+        return f32x4{a[4 * q], a[4 * q + 1], a[4 * q + 2], a[4 * q + 3]};
+      },
+      [&](int qi, f32x4 v) __attribute__((always_inline)) {
+        f32x16& a = acc[qi >> 3][(qi >> 2) & 1];
+        const int q = qi & 3;
+        a[4 * q] = v[0], a[4 * q + 1] = v[1], a[4 * q + 2] = v[2], a[4 * q + 3] = v[3];
+      },
+      sp, unit, seg, tile_id, smem, tid, wave, lane);
+}
+
+template <int TMB>   // 16x16 blocks per wave: TMB x 4 (the 256-row kernel: 8, the 128-row kernel: 4); quad = one block's 4 registers
+__device__ __forceinline__ bool split_k_reduce(f32x4 (&acc)[TMB][4], const SplitArgs& sp, int unit, int seg, int tile_id,
+                                               char* smem, int tid, int wave, int lane) {
+  return split_k_reduce_quads<TMB * 4>([&](int qi) __attribute__((always_inline)) { return acc[qi >> 2][qi & 3]; },
+                                       [&](int qi, f32x4 v) __attribute__((always_inline)) { acc[qi >> 2][qi & 3] = v; }, sp, unit, seg,
+                                       tile_id, smem, tid, wave, lane);
 }
 
 }  // namespace rtv

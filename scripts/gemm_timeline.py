@@ -8,7 +8,7 @@ import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-lib = ctypes.CDLL(os.path.join(ROOT, "scripts", "micro", "libgemm_tl.so"))
+lib = ctypes.CDLL(os.environ.get("GEMM_TL_LIB") or os.path.join(ROOT, "scripts", "micro", "libgemm_tl.so"))
 vp, ci, c64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
 lib.rtv_gemm.argtypes = [vp, ci, vp, ci, vp, ci, ci, ci, ci, vp, ci, vp, ci, ci, ci, vp, ci, ci, ci, vp]
 lib.rtv_gemm_workspace_bytes.restype = ctypes.c_size_t
@@ -59,6 +59,12 @@ def run(M, N, K, cfg):
         ok = raw[:ng, 2] != 0
         print(f"   epilogue split (us): K loop end -> LDS image written: median {np.median((mid - kend_rt)[ok]) / 100.0:.2f}, "
               f"image -> all stores issued: median {np.median((raw[:ng, 2] - mid)[ok]) / 100.0:.2f}")
+        # shader cycles from kernel start to the end of the K loop (full-K workgroups only): cycles per K-tile and the in-kernel clock
+        cyc, span = raw[ng:2 * ng, 1].astype(np.float64), (kend_rt - t0g).astype(np.float64)
+        full = ok & ((raw[:ng, 3] >> 32) == 0) & (cyc > 0) & (span > 0)
+        if full.any():
+            print(f"   K loop (prologue included), {int(full.sum())} unsplit workgroups: median {np.median(cyc[full]) / (K // 64):.0f} wave cycles per "
+                  f"K-tile, in-kernel clock median {np.median(cyc[full] / span[full]) * 100.0:.0f} MHz")
         raw = raw[:ng].copy()
         raw[:, 1] = kend_rt
     t = raw[raw[:, 0] != 0]

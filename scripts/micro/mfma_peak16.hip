@@ -1,5 +1,8 @@
 // As mfma_peak.hip but with v_mfma_f32_16x16x32_bf16 (4 passes, f32x4 accumulators): same FLOPs per cycle on paper;
 // does it sustain a different clock / rate than 32x32x16 on random operands?
+// NOT A VALID COMPARISON: hipcc shuffles the sixteen f32x4 accumulators through accumulation registers, so the timed loop holds 96
+// v_accvgpr moves beside its 32 MFMAs and is VALU-issue-bound (r04's "1530 TF/s").  Kept for the record; use mfma_shape.hip, whose
+// loops hold matrix instructions only (scripts/micro/mfma_shape_audit.sh).
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
