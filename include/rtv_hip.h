@@ -32,9 +32,9 @@ typedef void* rtv_stream_t; /* hipStream_t */
 
 /* ---- library ---------------------------------------------------------------------------- */
 /* ABI revision of this header: bumped whenever a struct layout or a signature below changes (101: rtv_dit_config gained the
- * trailing max_attn_kv_splits; 102: rtv_attn_set_waves value 3, r05; 103: rtv_dispatch_* added, r06).  A binding compares rtv_version() with the
+ * trailing max_attn_kv_splits; 102: rtv_attn_set_waves value 3, r05; 103: rtv_dispatch_* added, r06; 104: rtv_dit_step gained the trailing ca_vo_ld, in its former tail padding - the entry points that go with it are in rtv_hip_cross_fold.h).  A binding compares rtv_version() with the
  * RTV_ABI_VERSION it was written against and refuses a mismatch (realtime_video_amd/_lib.py does). */
-#define RTV_ABI_VERSION 103
+#define RTV_ABI_VERSION 104
 int rtv_version(void);
 const char* rtv_last_error(void);
 
@@ -292,6 +292,17 @@ typedef struct rtv_dit_step {
                                rtv_dit_layer_rest with row_count < M) cut their key window into this many ranges
                                (rtv_attn_fwd_split); 0 / 1: one launch.  Not bit-identical with the unsplit forward.  Must not
                                exceed rtv_dit_config.max_attn_kv_splits (the workspace holds the partials): an error otherwise. */
+  int ca_vo_ld;             /* > 0: cross-attention V folded into the output projection (bf16 path, short prompts).  The host
+                               array `ca_v` then holds 2 * num_layers pointers: ca_v[num_layers + l] = ca_vo[l], a device buffer
+                               [dim][ca_vo_ld] bf16 (ca_vo_ld >= k_fold, a multiple of 8) with
+                                 ca_vo[l][n, h*kh + t] = bf16(sum_d' co_w[n, h*128 + d'] * ca_v[l][t, h*128 + d'])   t <= text_rows
+                               kh / k_fold from rtv_cross_fold_dims (include/rtv_hip_cross_fold.h), zeros in every other column of
+                               [0, k_fold).  Filled by the call that fills ca_k / ca_v (compute_cross_kv), read by every later
+                               one: the cross-attention then writes its probabilities [rows][k_fold] (rtv_attn_probs_dup) and the
+                               output projection multiplies them by ca_vo[l] - K = k_fold instead of dim.  Used only where the
+                               fold applies (bf16 weights, text_rows > 0, text_rows + 1 < text_len, rtv_cross_fold_dims says
+                               yes); everything else, and 0, runs the unfolded path.  (One int in what was the struct's tail
+                               padding: sizeof(rtv_dit_step) and every earlier offset are those of revision 103.) */
 } rtv_dit_step;
 
 size_t rtv_dit_workspace_bytes(const rtv_dit_config* cfg, int F, int gh, int gw);

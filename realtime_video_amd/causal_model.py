@@ -12,6 +12,7 @@ Surface used by the reference's callers and reproduced here:
 """
 import collections
 import ctypes
+import os
 import types
 
 import torch
@@ -36,6 +37,16 @@ _FP8_TOP = ("text0_w", "text2_w", "time0_w", "time2_w", "tproj_w", "head_w")
 _FP8_LAYER = ("qkv_w", "o_w", "cq_w", "ck_w", "cv_w", "co_w", "ffn0_w", "ffn2_w")
 
 PROJ_LN, PROJ_Q, PROJ_KV = 1, 2, 4
+
+
+def _cross_fold_max_cols(num_heads):
+    """Columns of the widest folded cross-attention weight (rtv_cross_fold_dims at the longest prompt the fold takes)."""
+    lib, kh, kf = _lib.load(), ctypes.c_int(0), ctypes.c_int(0)
+    rows = 1
+    while lib.rtv_cross_fold_dims(int(num_heads), rows + 8, ctypes.byref(kh), ctypes.byref(kf)):
+        rows += 8
+    lib.rtv_cross_fold_dims(int(num_heads), rows, ctypes.byref(kh), ctypes.byref(kf))
+    return kf.value
 
 
 class BlockCausalMask:
@@ -114,13 +125,17 @@ class CausalWanModel:
         # cross-attention over the real prompt rows + ONE of the (identical) zero-padding rows weighted by their count instead of
         # all 512 text rows (rtv_attn_fwd_dup: mathematically identical, 8x less cross-attention work for a 64-token prompt)
         self.fold_text_padding = True
+        # short prompts (bf16 weights): V is folded into the cross-attention output projection when the caches are filled
+        # (rtv_dit_step.ca_vo_ld: V_h . Wo_h^T per head, once per prompt / LoRA change), the cross-attention writes probabilities and
+        # the projection runs with K = k_fold instead of dim.  Needs fold_text_padding; RTV_FOLD_CROSS_V=0 turns it off (A/B runs).
+        self.fold_cross_v = os.environ.get("RTV_FOLD_CROSS_V", "1") != "0"
         self.use_hip_graphs = False   # replay each distinct forward (recompute / denoise step) from a captured hipGraph
         self._graphs = {}
         self._weights_version = 0     # part of the graph key: a captured graph embeds weight pointers and the launch sequence
         self._cfg = _Cfg(dim, ffn_dim, num_heads, num_layers, freq_dim, text_dim, text_len, in_dim, out_dim, eps, 0, 0)
         self._lora = {}               # name -> {"scale": float, "targets": {target: lora.Target with A / B on the device}}, in load order
         self._lora_base = {}          # _tensors key -> bf16 copy of the matrix as loaded; kept outside _tensors / parameters()
-        self.lora_version = 0         # bumps when a merge changes ck_w / cv_w: crossattn_cache entries carry the one they were made with
+        self.lora_version = 0         # bumps when a merge changes ck_w / cv_w / co_w: crossattn_cache entries carry the one they were made with
 
     # ------------------------------------------------------------------ nn.Module-ish conveniences
     def eval(self):
@@ -391,7 +406,7 @@ class CausalWanModel:
                 self._fp8_scales[len(_FP8_TOP) + len(_FP8_LAYER) * int(layer) + _FP8_LAYER.index(field)] = s
             if not live:
                 del self._lora_base[key]
-            cross = cross or key.endswith((".ck_w", ".cv_w"))
+            cross = cross or key.endswith((".ck_w", ".cv_w", ".co_w"))      # (co_w: the folded V . Wo^T lives with the caches)
         if fp8 and keys:
             self._graphs.clear()
             self._weights_version += 1
@@ -593,6 +608,22 @@ class CausalWanModel:
         text_rows = int(crossattn_cache[0].get("text_rows", 0)) if getattr(self, "fold_text_padding", True) else 0
         if text_rows <= 0 or any(int(c.get("text_rows", 0)) != text_rows for c in crossattn_cache):
             text_rows = 0        # unknown (caches filled elsewhere) or inconsistent: attend all text_len rows
+        # V folded into the cross-attention output projection (rtv_dit_step.ca_vo_ld).  Decided HERE, once, for the whole forward, the
+        # phase API and every shard; the native side takes the same decision from the same fields.  The folded weights are made by
+        # the call that fills the caches, so caches filled with the fold off (or for another prompt length / LoRA state) stay on
+        # the unfolded path until they are refilled.
+        fold_k = 0
+        if 0 < text_rows < self.text_len - 1 and getattr(self, "fold_cross_v", True) and not self._cfg.use_fp8:
+            kh_, kf_ = ctypes.c_int(0), ctypes.c_int(0)
+            if _lib.load().rtv_cross_fold_dims(self.num_heads, text_rows, ctypes.byref(kh_), ctypes.byref(kf_)):
+                fold_k = kf_.value
+            if fold_k and not need_cross and any(c.get("vo_for") != (text_rows, self.lora_version) for c in crossattn_cache):
+                fold_k = 0
+        if fold_k:
+            # one buffer per cache, at the largest fold width, never reallocated: captured graphs embed the addresses
+            for c in crossattn_cache:
+                if "vo" not in c:
+                    c["vo"] = torch.zeros(self.dim * _cross_fold_max_cols(self.num_heads), dtype=torch.bfloat16, device=u.device)
         row0, lo, hi, start_frame, causal_block, (ring_lo, ring_size, ring_shift), commit = \
             self._cache_window(kv_cache, M, current_start, fs, ring=not use_cp)
         L = self.num_layers
@@ -610,7 +641,9 @@ class CausalWanModel:
         kk_keep, kk = ptr_array([c["k"] for c in kv_cache])
         kv_keep, kv = ptr_array([c["v"] for c in kv_cache])
         ck_keep, ck = ptr_array([c["k"] for c in crossattn_cache])
-        cv_keep, cv = ptr_array([c["v"] for c in crossattn_cache])
+        cv_list = [c["v"] for c in crossattn_cache] + ([c["vo"] for c in crossattn_cache] if fold_k else [])
+        cv_keep = (c_vp * len(cv_list))(*[t_.data_ptr() for t_ in cv_list])      # folded: ca_v[L + l] = the folded weight of layer l
+        cv = ctypes.cast(cv_keep, ctypes.POINTER(c_vp))
         out = (torch.zeros if kv_only else torch.empty)((self.out_dim, F, Hh, Ww), dtype=torch.bfloat16, device=u.device)
         stream = c_vp(torch.cuda.current_stream().cuda_stream)
         cfg_p, w_p = ctypes.byref(self._cfg), ctypes.byref(self._w)
@@ -622,7 +655,7 @@ class CausalWanModel:
                        F, gh, gw, kk, kv, rs, ck, cv, int(need_cross), row0, lo, hi,
                        start_frame, causal_block, int(self.gemm_tile_cfg), rank_rows[0], rank_rows[1],
                        ring_lo, ring_size, ring_shift, int(text_rows), int(kv_only),
-                       int(getattr(cp, "attn_kv_splits", 1)) if use_cp else 1)
+                       int(getattr(cp, "attn_kv_splits", 1)) if use_cp else 1, fold_k)
             return st, (c_vp(ws_ptr), ctypes.c_size_t(ws.numel() - (ws_ptr - ws.data_ptr())), stream)
 
         splits = int(getattr(cp, "attn_kv_splits", 1)) if use_cp else 1
@@ -641,7 +674,7 @@ class CausalWanModel:
                 # the ~530 launches of one forward replayed as ONE hipGraph.  Everything the launch sequence
                 # depends on is part of the key (steady state has two entries: the recompute pass and the denoise step);
                 # the latent / timestep / output live in static buffers.  The first sighting of a key runs eagerly.
-                graph_key = (F, gh, gw, row0, lo, hi, start_frame, causal_block, ring_lo, ring_size, ring_shift, kv_only, text_rows,
+                graph_key = (F, gh, gw, row0, lo, hi, start_frame, causal_block, ring_lo, ring_size, ring_shift, kv_only, text_rows, fold_k,
                              int(self.gemm_tile_cfg), rs, self._weights_version,
                              kv_cache[0]["k"].data_ptr(), kv_cache[-1]["v"].data_ptr(), crossattn_cache[0]["k"].data_ptr())
                 ent = self._graphs.get(graph_key)
@@ -685,7 +718,7 @@ class CausalWanModel:
             # object and its overlap mode: a captured graph embeds that object's process group and stream fences.)
             if self.use_hip_graphs and not need_cross and not getattr(cp, "_gloo", False):
                 graph_key = ("cp", id(cp), bool(getattr(cp, "overlap", True)), cp.world, cp.head_exchange(self.num_heads), F, gh, gw, row0, lo, hi, start_frame, causal_block, kv_only,
-                             text_rows, int(self.gemm_tile_cfg), rs, self._weights_version, splits,
+                             text_rows, fold_k, int(self.gemm_tile_cfg), rs, self._weights_version, splits,
                              kv_cache[0]["k"].data_ptr(), kv_cache[-1]["v"].data_ptr(), crossattn_cache[0]["k"].data_ptr())
                 ent = self._graphs.get(graph_key)
                 if isinstance(ent, dict):
@@ -790,6 +823,7 @@ class CausalWanModel:
             for c in crossattn_cache:
                 c["is_init"] = True
                 c["lora_version"] = self.lora_version
+                c["vo_for"] = (text_rows, self.lora_version) if fold_k else None      # what c["vo"] now holds
         return out.unsqueeze(0)
 
     def forward(self, *args, **kwargs):

@@ -731,6 +731,138 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_pp_kernel(AttnParams p) {
   }
 }
 
+// =====================================================================================================================
+// Probabilities of a short key window (rtv_attn_probs_dup): the text cross-attention whose V is folded into the output
+// projection.  The whole window (<= NKB * 32 <= 128 keys) stays in registers, so this is a plain softmax: S^T = K . Q^T as in the
+// kernels above (a lane owns ONE query column, the row reductions are in-lane plus one exchange with lane ^ 32), m = max,
+// e = 2^(x - m), P = e / sum e in fp32, rounded once.
+// Workgroup = 4 waves x 32 query rows of one head.  The head's K rows are staged into LDS once (XOR-swizzled as above, rows
+// beyond Lkv as zeros) and the workgroup walks `tiles_per_wg` row tiles.  A wave's P rows go through its own LDS slab and leave
+// as whole 16-byte pieces of the [kh] column block of the head; the workgroups of the last head also zero the tail columns
+// [H * kh, p_cols).
+struct ProbsParams {
+  const uint16_t* q;
+  const uint16_t* k;
+  uint16_t* p;
+  int Lq, Lkv, H;
+  int64_t q_rs, k_rs, p_rs;
+  int kh, p_cols;
+  float scale_log2e;
+  int dup_key;        // -1: none
+  float dup_log2;     // log2(dup_count), added to the key's score in the exp2 domain
+  int tiles_per_wg;
+};
+constexpr int PROBS_NW = 4;                       // waves per workgroup
+constexpr int PROBS_ROWS = PROBS_NW * ATT_QW;     // query rows per tile (128)
+
+template <int NKB>
+__global__ __launch_bounds__(PROBS_NW * 64) void attn_probs_kernel(ProbsParams p) {
+  constexpr int KEYS = NKB * 32;
+  constexpr int SLAB_LD = KEYS * 2 + 16;          // bytes per P row of a wave's slab (+16: the rows do not all start in one bank)
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* const sK = smem;                                   // [KEYS][256 B]
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int l31 = lane & 31, g = lane >> 5;
+  char* const slab = smem + KEYS * 256 + wave * (ATT_QW * SLAB_LD);
+  const int h = blockIdx.y;
+  const uint16_t* qb = p.q + (size_t)h * ATT_D;
+  const uint16_t* kb = p.k + (size_t)h * ATT_D;
+  uint16_t* pb = p.p + (size_t)h * p.kh;
+
+  // ---- K rows of the head -> LDS, chunk index XOR (row & 15); rows >= Lkv are zeros
+  for (int id = tid; id < KEYS * 16; id += PROBS_NW * 64) {
+    const int r = id >> 4, c = id & 15;
+    u32x4 v = {0u, 0u, 0u, 0u};
+    if (r < p.Lkv) v = *(const u32x4*)(kb + (int64_t)r * p.k_rs + c * 8);
+    *(u32x4*)(sK + r * 256 + ((c ^ (r & 15)) << 4)) = v;
+  }
+  __syncthreads();
+  const char* k_rd[8];
+#pragma unroll
+  for (int dc = 0; dc < 8; ++dc) k_rd[dc] = sK + l31 * 256 + (((dc * 2 + g) ^ (l31 & 15)) << 4);
+
+  const float c = p.scale_log2e;
+  const int ppr = p.kh >> 3;                                // 16-byte pieces per P row of this head
+  const int tail0 = p.H * p.kh, tail_pieces = h == p.H - 1 ? (p.p_cols - tail0) >> 3 : 0;
+  const int tile0 = blockIdx.x * p.tiles_per_wg;
+  for (int ti = 0; ti < p.tiles_per_wg; ++ti) {
+    const int row0 = (tile0 + ti) * PROBS_ROWS + wave * ATT_QW;   // first row of this wave (wave-uniform)
+    if (row0 >= p.Lq) break;
+    const int q_row_c = min(row0 + l31, p.Lq - 1);
+    // ---- Q^T fragments (MFMA B operand): lane holds Q[q][dc*16 + g*8 .. +8]
+    u32x4 qf[8];
+    {
+      const uint16_t* qp = qb + (size_t)q_row_c * p.q_rs + g * 8;
+#pragma unroll
+      for (int dc = 0; dc < 8; ++dc) qf[dc] = *(const u32x4*)(qp + dc * 16);
+    }
+    f32x16 s[NKB];
+#pragma unroll
+    for (int kbk = 0; kbk < NKB; ++kbk)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) s[kbk][r] = 0.f;
+#pragma unroll
+    for (int dc = 0; dc < 8; ++dc)
+#pragma unroll
+      for (int kbk = 0; kbk < NKB; ++kbk) {
+        const u32x4 kf = *(const u32x4*)(k_rd[dc] + kbk * 32 * 256);
+        s[kbk] = mfma32<false>(kf, qf[dc], s[kbk]);
+      }
+    // ---- scores in the exp2 domain; the counted key's bias; keys beyond the window masked
+    float mx = -INFINITY;
+#pragma unroll
+    for (int kbk = 0; kbk < NKB; ++kbk)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int key = kbk * 32 + (r & 3) + 8 * (r >> 2) + 4 * g;
+        float x = s[kbk][r] * c;
+        if (key == p.dup_key) x += p.dup_log2;
+        if (key >= p.Lkv) x = -INFINITY;
+        s[kbk][r] = x;
+        mx = fmaxf(mx, x);
+      }
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));      // key 0 is always inside the window: mx is finite
+    float l = 0.f;
+#pragma unroll
+    for (int kbk = 0; kbk < NKB; ++kbk)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float e = __builtin_amdgcn_exp2f(s[kbk][r] - mx);
+        s[kbk][r] = e;
+        l += e;
+      }
+    l += __shfl_xor(l, 32, 64);
+    const float inv = 1.0f / l;
+    // ---- P row l31 of the wave -> slab: 4 consecutive keys (r = 4i .. 4i+3) are keys kbk*32 + 8i + 4g + {0..3}
+#pragma unroll
+    for (int kbk = 0; kbk < NKB; ++kbk)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        u32x2 w;
+        w[0] = pack2<false>(s[kbk][4 * i + 0] * inv, s[kbk][4 * i + 1] * inv);
+        w[1] = pack2<false>(s[kbk][4 * i + 2] * inv, s[kbk][4 * i + 3] * inv);
+        *(u32x2*)(slab + l31 * SLAB_LD + (kbk * 32 + 8 * i + 4 * g) * 2) = w;
+      }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");   // the slab is this wave's own: its writes have landed
+    __builtin_amdgcn_wave_barrier();
+    // ---- slab -> global, 16-byte pieces: columns [h * kh, (h + 1) * kh) of rows row0 .. row0 + 31
+    const int rows_here = min(ATT_QW, p.Lq - row0);
+    for (int id = lane; id < rows_here * ppr; id += 64) {
+      const int r = id / ppr, pc = id - r * ppr;
+      const u32x4 v = *(const u32x4*)(slab + r * SLAB_LD + pc * 16);
+      *(u32x4*)(pb + (int64_t)(row0 + r) * p.p_rs + pc * 8) = v;
+    }
+    for (int id = lane; id < rows_here * tail_pieces; id += 64) {
+      const int r = id / tail_pieces, pc = id - r * tail_pieces;
+      *(u32x4*)(p.p + (int64_t)(row0 + r) * p.p_rs + tail0 + pc * 8) = u32x4{0u, 0u, 0u, 0u};
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");   // the reads are done before the next tile overwrites the slab
+    __builtin_amdgcn_wave_barrier();
+  }
+}
+
 }  // namespace rtv
 
 using namespace rtv;
@@ -804,6 +936,61 @@ extern "C" int rtv_attn_fwd_dup(const void* q, const void* k, const void* v, voi
   return attn_fwd_impl(q, k, v, o, B, Lq, Lkv, 0, 0, H, D, q_batch_stride, q_row_stride, k_batch_stride, k_row_stride,
                        v_batch_stride, v_row_stride, o_batch_stride, o_row_stride, scale, 0, 0, dtype, stream,
                        dup_count > 1 ? dup_key : -1, dup_count);
+}
+
+template <int NKB>
+static int launch_attn_probs(const ProbsParams& p, dim3 grid, hipStream_t stream) {
+  static LdsAttr lds_attr;   // per device
+  const int lds = NKB * 32 * 256 + PROBS_NW * ATT_QW * (NKB * 64 + 16);
+  if (int st = ensure_dynamic_lds((const void*)attn_probs_kernel<NKB>, lds, &lds_attr, "attn_probs")) return st;
+  hipLaunchKernelGGL((attn_probs_kernel<NKB>), grid, dim3(PROBS_NW * 64), lds, stream, p);
+  return check_launch("attn_probs");
+}
+
+extern "C" int rtv_attn_probs_dup(const void* q, const void* k, void* p, int Lq, int Lkv, int H, int D, int64_t q_row_stride,
+                                  int64_t k_row_stride, int64_t p_row_stride, int kh, int p_cols, float scale, int dup_key,
+                                  int dup_count, rtv_stream_t stream) {
+  if (D != ATT_D) return set_error(-1, "attn_probs: head_dim must be 128");
+  if (H <= 0 || Lq <= 0) return 0;
+  if (Lkv <= 0 || Lkv > 128) return set_error(-1, "attn_probs: the key window must hold 1..128 keys");
+  if (kh <= 0 || (kh & 7) || kh < Lkv || kh > 128) return set_error(-1, "attn_probs: kh must be a multiple of 8 in [Lkv, 128]");
+  if ((p_cols & 7) || (int64_t)H * kh > p_cols || p_cols > p_row_stride)
+    return set_error(-1, "attn_probs: need H * kh <= p_cols <= p_row_stride, p_cols a multiple of 8");
+  if ((q_row_stride | k_row_stride | p_row_stride) & 7 || q_row_stride < (int64_t)H * ATT_D || k_row_stride < (int64_t)H * ATT_D)
+    return set_error(-1, "attn_probs: strides must be multiples of 8 elements (16-byte rows) and hold H heads");
+  if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)p) & 15) return set_error(-1, "attn_probs: base pointers must be 16-byte aligned");
+  if (dup_key < 0 || dup_key >= Lkv || dup_count < 1) return set_error(-1, "attn_probs: dup_key must be a key of the window, dup_count >= 1");
+  ProbsParams pp;
+  pp.q = (const uint16_t*)q;
+  pp.k = (const uint16_t*)k;
+  pp.p = (uint16_t*)p;
+  pp.Lq = Lq;
+  pp.Lkv = Lkv;
+  pp.H = H;
+  pp.q_rs = q_row_stride;
+  pp.k_rs = k_row_stride;
+  pp.p_rs = p_row_stride;
+  pp.kh = kh;
+  pp.p_cols = p_cols;
+  pp.scale_log2e = scale * 1.4426950408889634f;
+  pp.dup_key = dup_count > 1 ? dup_key : -1;
+  pp.dup_log2 = dup_count > 1 ? log2f((float)dup_count) : 0.f;
+  // a workgroup stages its head's K rows once: let it walk enough row tiles that the grid is about two workgroups per CU
+  const int cus = device_num_cus() > 0 ? device_num_cus() : 256;
+  const int n_tiles = (Lq + PROBS_ROWS - 1) / PROBS_ROWS;
+  int tpw = (int)(((int64_t)n_tiles * H) / (2 * (int64_t)cus));
+  tpw = tpw < 1 ? 1 : (tpw > 8 ? 8 : tpw);
+  pp.tiles_per_wg = tpw;
+  const dim3 grid((n_tiles + tpw - 1) / tpw, H);
+  ProfScope prof(PROF_ATTN, (hipStream_t)stream, 2.0 * H * (double)Lq * Lkv * ATT_D);
+  note_kernel(DK_ATTN_PROBS);
+  const int nkb = (kh + 31) / 32;   // 32-key blocks that cover the kh columns of a head (keys >= Lkv come out as zeros)
+  switch (nkb) {
+    case 1: return launch_attn_probs<1>(pp, grid, (hipStream_t)stream);
+    case 2: return launch_attn_probs<2>(pp, grid, (hipStream_t)stream);
+    case 3: return launch_attn_probs<3>(pp, grid, (hipStream_t)stream);
+    default: return launch_attn_probs<4>(pp, grid, (hipStream_t)stream);
+  }
 }
 
 extern "C" size_t rtv_attn_split_workspace_bytes(int B, int Lq, int H, int kv_splits) {

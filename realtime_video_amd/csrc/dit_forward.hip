@@ -25,6 +25,59 @@ __global__ void silu_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ o
     out[i] = f32_to_bf16(silu(bf16_to_f32(x[i])));
 }
 
+// Folded cross-attention weight of one layer (rtv_cross_fold_weight): vo[n, h*kh + t] = sum_d' co_w[n, h*128 + d'] * v[t, h*128 + d'].
+// Once per prompt, 0.03 % of a block's multiply-adds: plain fp32 FMAs.  Workgroup = 64 rows n of one head; lane = key t (so the
+// 2-byte stores of a wave are one contiguous run), wave = 16 of the 64 rows.  LDS rows are 130 elements long: the per-lane reads
+// of V (65 words apart) touch 64 different banks, the reads of co_w are broadcasts.
+constexpr int FOLD_ROWS = 64, FOLD_LD = 130;
+__global__ __launch_bounds__(256) void cross_fold_weight_kernel(const bf16_t* __restrict__ w, int64_t ldw, const bf16_t* __restrict__ v,
+                                                               int64_t ldv, bf16_t* __restrict__ vo, int64_t ldvo, int H, int rows, int kh,
+                                                               int k_fold) {
+  __shared__ __attribute__((aligned(16))) bf16_t sW[FOLD_ROWS * FOLD_LD];
+  __shared__ __attribute__((aligned(16))) bf16_t sV[128 * FOLD_LD];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int n0 = blockIdx.x * FOLD_ROWS, h = blockIdx.y;
+  for (int id = tid; id < FOLD_ROWS * 64; id += 256) {      // 2 elements per step (the padded rows are only 4-byte aligned)
+    const int r = id >> 6, c = (id & 63) * 2;
+    *(uint32_t*)(sW + r * FOLD_LD + c) = *(const uint32_t*)(w + (int64_t)(n0 + r) * ldw + h * 128 + c);
+  }
+  for (int id = tid; id < rows * 64; id += 256) {
+    const int r = id >> 6, c = (id & 63) * 2;
+    *(uint32_t*)(sV + r * FOLD_LD + c) = *(const uint32_t*)(v + (int64_t)r * ldv + h * 128 + c);
+  }
+  __syncthreads();
+  for (int ts = 0; ts < kh; ts += 64) {
+    const int t = ts + lane;
+    float acc[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+    if (t < rows) {
+      const bf16_t* vr = sV + t * FOLD_LD;
+      const bf16_t* wr = sW + wave * 16 * FOLD_LD;
+      for (int dd = 0; dd < 128; dd += 2) {
+        const uint32_t v2 = *(const uint32_t*)(vr + dd);
+        const float v0 = __uint_as_float(v2 << 16), v1 = __uint_as_float(v2 & 0xffff0000u);
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          const uint32_t w2 = *(const uint32_t*)(wr + i * FOLD_LD + dd);
+          acc[i] = fmaf(__uint_as_float(w2 << 16), v0, acc[i]);
+          acc[i] = fmaf(__uint_as_float(w2 & 0xffff0000u), v1, acc[i]);
+        }
+      }
+    }
+    if (t < kh) {   // keys t >= rows of the head's kh columns: zeros
+#pragma unroll
+      for (int i = 0; i < 16; ++i) vo[(int64_t)(n0 + wave * 16 + i) * ldvo + h * kh + t] = f32_to_bf16(acc[i]);
+    }
+  }
+  if (h == H - 1) {   // the tail behind the last head's columns
+    const int tail0 = H * kh;
+    for (int t = tail0 + lane; t < k_fold; t += 64)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) vo[(int64_t)(n0 + wave * 16 + i) * ldvo + t] = 0;
+  }
+}
+
 struct Workspace {
   char* base;
   size_t off, cap;
@@ -95,6 +148,8 @@ struct Ctx {
   DitBuffers b;
   rtv_stream_t stream;
   int d, H, L, ffn, hd, F, gh, gw, fs, M, r0, rc, tc;
+  int fold_kh, fold_k;   // cross-attention V folded into the output projection: columns per head / in all; 0 = the unfolded path
+                         // (then st->ca_v[L + l] is layer l's folded weight, rtv_dit_step.ca_vo_ld)
 };
 
 static int make_ctx(const rtv_dit_config* cfg, const rtv_dit_weights* w, const rtv_dit_step* st, void* workspace,
@@ -132,6 +187,16 @@ static int make_ctx(const rtv_dit_config* cfg, const rtv_dit_weights* w, const r
   carve(cfg, c->F, c->gh, c->gw, (char*)workspace, workspace_bytes, &c->b, &ok);
   if (!ok) return set_error(-1, "dit: workspace too small (see rtv_dit_workspace_bytes)");
   c->tc = st->gemm_tile_cfg;
+  // One decision for every entry point (whole forward, phase API, every shard): a function of the configuration and the step alone.
+  c->fold_kh = c->fold_k = 0;
+  if (st->ca_vo_ld > 0 && st->ca_v && !cfg->use_fp8 && st->text_rows > 0 && st->text_rows + 1 < cfg->text_len) {
+    int kh = 0, kf = 0;
+    if (rtv_cross_fold_dims(c->H, st->text_rows, &kh, &kf) && kf <= c->d) {
+      if (st->ca_vo_ld < kf || (st->ca_vo_ld & 7)) return set_error(-1, "dit: ca_vo_ld must be a multiple of 8 and >= k_fold (rtv_cross_fold_dims)");
+      c->fold_kh = kh;
+      c->fold_k = kf;
+    }
+  }
   return 0;
 }
 
@@ -152,6 +217,28 @@ extern "C" int rtv_silu(const void* x, void* out, int64_t n, rtv_stream_t stream
   hipLaunchKernelGGL(silu_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
                      (bf16_t*)out, n);
   return check_launch("silu");
+}
+
+extern "C" int rtv_cross_fold_dims(int num_heads, int text_rows, int* kh, int* k_fold) {
+  const int khv = text_rows >= 0 ? (text_rows + 1 + 7) & ~7 : 0;
+  const int64_t kf = ((int64_t)num_heads * khv + 63) & ~(int64_t)63;
+  if (kh) *kh = khv;
+  if (k_fold) *k_fold = kf > 0x7fffffff ? 0 : (int)kf;
+  return num_heads > 0 && text_rows > 0 && khv <= RTV_CROSS_FOLD_KH_MAX && kf <= 0x7fffffff;
+}
+
+extern "C" int rtv_cross_fold_weight(const void* co_w, int64_t ldw, const void* v, int64_t ldv, void* vo, int64_t ldvo, int num_heads,
+                                     int rows, int kh, int k_fold, rtv_stream_t stream) {
+  if (!co_w || !v || !vo) return set_error(-1, "cross_fold_weight: null argument");
+  if (num_heads <= 0 || rows <= 0 || rows > kh || kh > 128 || (kh & 7)) return set_error(-1, "cross_fold_weight: need 0 < rows <= kh <= 128, kh % 8 == 0");
+  const int64_t d = (int64_t)num_heads * 128;
+  if ((int64_t)num_heads * kh > k_fold || k_fold > ldvo || ldw < d || ldv < d || ((ldw | ldv) & 1))
+    return set_error(-1, "cross_fold_weight: need num_heads * kh <= k_fold <= ldvo and rows of num_heads * 128 elements");
+  if (((uintptr_t)co_w | (uintptr_t)v) & 3) return set_error(-1, "cross_fold_weight: operands must be 4-byte aligned");
+  ProfScope prof(PROF_MISC, (hipStream_t)stream, 2.0 * d * (double)num_heads * rows * 128);
+  hipLaunchKernelGGL(cross_fold_weight_kernel, dim3((unsigned)(d / FOLD_ROWS), num_heads), dim3(256), 0, (hipStream_t)stream,
+                     (const bf16_t*)co_w, ldw, (const bf16_t*)v, ldv, (bf16_t*)vo, ldvo, num_heads, rows, kh, k_fold);
+  return check_launch("cross_fold_weight");
 }
 
 extern "C" size_t rtv_dit_workspace_bytes(const rtv_dit_config* cfg, int F, int gh, int gw) {
@@ -206,6 +293,9 @@ static int dit_begin(Ctx& c) {
       RTV_TRY(linear(c, S_LAYER0 + S_PER_LAYER * l + S_CK, b.ctx, d, lw.ck_w, lw.ck_b, b.ktmp, T, d, 0, nullptr, 0, 0, 0, nullptr, tc, stream));
       RTV_TRY(rtv_rmsnorm(b.ktmp, d, st->ca_k[l], d, T, d, cfg->eps, lw.cnorm_k_w, stream));
       RTV_TRY(linear(c, S_LAYER0 + S_PER_LAYER * l + S_CV, b.ctx, d, lw.cv_w, lw.cv_b, st->ca_v[l], T, d, 0, nullptr, 0, 0, 0, nullptr, tc, stream));
+      if (c.fold_k)   // the folded weight lives and dies with the caches: refreshed exactly when they are (new prompt, LoRA change)
+        RTV_TRY(rtv_cross_fold_weight(lw.co_w, d, st->ca_v[l], d, st->ca_v[c.L + l], st->ca_vo_ld, c.H, st->text_rows + 1, c.fold_kh, c.fold_k,
+                                      stream));
     }
   }
   return 0;
@@ -402,13 +492,22 @@ static int dit_after_attn(Ctx& c, int l) {
   RTV_TRY(rtv_layernorm_modulate(b.x, b.xn, rc, d, eps, nullptr, nullptr, 0, 0, 0, lw.norm3_w, lw.norm3_b, stream));
   RTV_TRY(linear(c, S_LAYER0 + S_PER_LAYER * l + S_CQ, b.xn, d, lw.cq_w, lw.cq_b, b.qkv, rc, d, 0, nullptr, 0, 0, 0, nullptr, tc, stream));
   RTV_TRY(rtv_rmsnorm(b.qkv, d, b.q, d, rc, d, eps, lw.cnorm_q_w, stream));
-  if (st->text_rows > 0 && st->text_rows + 1 < c.cfg->text_len)   // the padding rows share one K / V row: attend it once, weighted
-    RTV_TRY(rtv_attn_fwd_dup(b.q, st->ca_k[l], st->ca_v[l], b.ao, 1, rc, st->text_rows + 1, H, hd, 0, d, 0, d, 0, d, 0, d, scale,
-                             st->text_rows, c.cfg->text_len - st->text_rows, RTV_DTYPE_BF16, stream));
-  else
-    RTV_TRY(rtv_attn_fwd(b.q, st->ca_k[l], st->ca_v[l], b.ao, 1, rc, c.cfg->text_len, H, hd, 0, d, 0, d, 0, d, 0, d,
-                         scale, 0, 0, RTV_DTYPE_BF16, stream));
-  RTV_TRY(linear(c, S_LAYER0 + S_PER_LAYER * l + S_CO, b.ao, d, lw.co_w, lw.co_b, b.x, rc, d, 0, nullptr, 0, 0, 0, b.x, tc, stream));
+  if (c.fold_k) {
+    // short prompt: ao . Wo^T = sum_h P_h . (V_h . Wo_h^T) - the probabilities [rc][fold_k] go into b.ao, the projection multiplies
+    // them by the folded weight made with the caches (K = fold_k instead of d; same epilogue)
+    RTV_TRY(rtv_attn_probs_dup(b.q, st->ca_k[l], b.ao, rc, st->text_rows + 1, H, hd, d, d, c.fold_k, c.fold_kh, c.fold_k, scale,
+                               st->text_rows, c.cfg->text_len - st->text_rows, stream));
+    RTV_TRY(rtv_gemm(b.ao, c.fold_k, st->ca_v[c.L + l], st->ca_vo_ld, b.x, d, rc, d, c.fold_k, lw.co_b, 0, nullptr, 0, 0, 0, b.x, d,
+                     RTV_DTYPE_BF16, tc, stream));
+  } else {
+    if (st->text_rows > 0 && st->text_rows + 1 < c.cfg->text_len)   // the padding rows share one K / V row: attend it once, weighted
+      RTV_TRY(rtv_attn_fwd_dup(b.q, st->ca_k[l], st->ca_v[l], b.ao, 1, rc, st->text_rows + 1, H, hd, 0, d, 0, d, 0, d, 0, d, scale,
+                               st->text_rows, c.cfg->text_len - st->text_rows, RTV_DTYPE_BF16, stream));
+    else
+      RTV_TRY(rtv_attn_fwd(b.q, st->ca_k[l], st->ca_v[l], b.ao, 1, rc, c.cfg->text_len, H, hd, 0, d, 0, d, 0, d, 0, d,
+                           scale, 0, 0, RTV_DTYPE_BF16, stream));
+    RTV_TRY(linear(c, S_LAYER0 + S_PER_LAYER * l + S_CO, b.ao, d, lw.co_w, lw.co_b, b.x, rc, d, 0, nullptr, 0, 0, 0, b.x, tc, stream));
+  }
   // FFN (causal_model.py:482-488)
   RTV_TRY(rtv_layernorm_modulate(b.x, b.xn, rc, d, eps, em + 3 * d, em + 4 * d, 6 * d, fs, r0, nullptr, nullptr, stream));
   RTV_TRY(linear(c, S_LAYER0 + S_PER_LAYER * l + S_FFN0, b.xn, d, lw.ffn0_w, lw.ffn0_b, b.h, rc, c.ffn, RTV_ACT_GELU_TANH, nullptr, 0, 0, 0, nullptr, tc, stream));

@@ -140,6 +140,45 @@ def attn_fwd_dup(q, k, v, dup_key, dup_count, out=None, scale=None):
     return out
 
 
+def cross_fold_dims(num_heads, text_rows):
+    """-> (applies, kh, k_fold): the column layout of the folded cross-attention (rtv_cross_fold_dims)."""
+    kh, kf = ctypes.c_int(0), ctypes.c_int(0)
+    ok = _lib.load().rtv_cross_fold_dims(int(num_heads), int(text_rows), ctypes.byref(kh), ctypes.byref(kf))
+    return bool(ok), kh.value, kf.value
+
+
+def attn_probs_dup(q, k, dup_key, dup_count, kh, p_cols, out=None, scale=None):
+    """Softmax probabilities of a short key window with a counted key (rtv_attn_probs_dup).  q [Lq, H, 128], k [Lkv, H, 128]
+    -> [Lq, p_cols] bf16 with head h's keys in columns [h * kh, h * kh + Lkv) and zeros in every other column."""
+    _gpu(q, k)
+    Lq, H, D = q.shape
+    Lkv = k.shape[0]
+    if q.dtype != torch.bfloat16 or k.dtype != torch.bfloat16:
+        raise TypeError("attn_probs_dup is bf16 only")
+    for t in (q, k):
+        if t.stride(2) != 1 or t.stride(1) != D:
+            raise ValueError("attention operands need dense [H, D] inner dims")
+    if out is None:
+        out = torch.empty((Lq, p_cols), dtype=q.dtype, device=q.device)
+    if scale is None:
+        scale = 1.0 / math.sqrt(D)
+    _lib.call("rtv_attn_probs_dup", _ptr(q), _ptr(k), _ptr(out), Lq, Lkv, H, D, q.stride(0), k.stride(0), out.stride(0),
+              int(kh), int(p_cols), float(scale), int(dup_key), int(dup_count), _stream())
+    return out
+
+
+def cross_fold_weight(co_w, v, rows, kh, k_fold, out=None):
+    """vo[n, h * kh + t] = sum_d' co_w[n, h * 128 + d'] * v[t, h * 128 + d'] for t < rows, zeros elsewhere (rtv_cross_fold_weight).
+    co_w [d, d], v [>= rows, d] bf16 -> [d, k_fold] bf16."""
+    _gpu(co_w, v)
+    d = co_w.shape[0]
+    if out is None:
+        out = torch.empty((d, k_fold), dtype=torch.bfloat16, device=co_w.device)
+    _lib.call("rtv_cross_fold_weight", _ptr(co_w), co_w.stride(0), _ptr(v), v.stride(0), _ptr(out), out.stride(0), d // 128,
+              int(rows), int(kh), int(k_fold), _stream())
+    return out
+
+
 def attn_fwd_win(q, k_cache, v_cache, seg0, seg1=(0, 0), out=None, scale=None):
     """Attention over a key window made of two row ranges of a cache (rtv_attn_fwd_win): k_cache / v_cache [B, rows, H, 128],
     seg = (first_row, n_rows).  How a ring-indexed rolling KV cache is attended without the reference's shift copy."""
