@@ -32,9 +32,9 @@ typedef void* rtv_stream_t; /* hipStream_t */
 
 /* ---- library ---------------------------------------------------------------------------- */
 /* ABI revision of this header: bumped whenever a struct layout or a signature below changes (101: rtv_dit_config gained the
- * trailing max_attn_kv_splits; 102: rtv_attn_set_waves value 3, r05; 103: rtv_dispatch_* added, r06; 104: rtv_dit_step gained the trailing ca_vo_ld, in its former tail padding - the entry points that go with it are in rtv_hip_cross_fold.h).  A binding compares rtv_version() with the
+ * trailing max_attn_kv_splits; 102: rtv_attn_set_waves value 3, r05; 103: rtv_dispatch_* added, r06; 104: rtv_dit_step gained the trailing ca_vo_ld, in its former tail padding - the entry points that go with it are in rtv_hip_cross_fold.h; 105: rtv_dit_config.use_fp8 takes the value 2 and rtv_dit_weights gained the trailing fp8_row_scales - the entry points that go with them are in rtv_hip_fp8_rows.h).  A binding compares rtv_version() with the
  * RTV_ABI_VERSION it was written against and refuses a mismatch (realtime_video_amd/_lib.py does). */
-#define RTV_ABI_VERSION 104
+#define RTV_ABI_VERSION 105
 int rtv_version(void);
 const char* rtv_last_error(void);
 
@@ -231,7 +231,9 @@ typedef struct rtv_dit_config {
   int freq_dim, text_dim, text_len;
   int in_dim, out_dim;          /* latent channels (16, 16); patch size is (1,2,2) */
   float eps;
-  int use_fp8;                  /* 1: every nn.Linear runs the e4m3 path (weights below are e4m3, fp8_scales set) */
+  int use_fp8;                  /* 1: every nn.Linear runs the e4m3 path (weights below are e4m3, fp8_scales set);
+                                   2: the same with one scale per activation row and per weight row (fp8_row_scales set,
+                                   rtv_hip_fp8_rows.h) */
   int max_attn_kv_splits;       /* largest rtv_dit_step.attn_kv_splits this workspace must serve (0 / 1: none - the workspace then
                                    holds no split-attention partials: 97 MB at 14B, M = 4680); a step asking for more fails */
 } rtv_dit_config;
@@ -259,6 +261,9 @@ typedef struct rtv_dit_weights {
   const float* fp8_scales;            /* fp8 mode: host array of per-tensor weight scales: text0, text2, time0, time2, tproj,
                                          head, then per layer qkv, o, cq, ck, cv, co, ffn0, ffn2 (6 + 8 L entries); the *_w
                                          pointers of those linears then address e4m3 [N][K] data.  NULL otherwise */
+  const void* const* fp8_row_scales;  /* use_fp8 == 2: host array of device float pointers, one per Linear in the order of
+                                         fp8_scales; entry i addresses the N per-row (output channel) scales of that weight -
+                                         3d of them for the fused qkv weight.  NULL otherwise */
 } rtv_dit_weights;
 
 typedef struct rtv_dit_step {
@@ -359,7 +364,8 @@ int rtv_dit_layer_rest_hp(const rtv_dit_config* cfg, const rtv_dit_weights* w, c
  * rtv_quantize_fp8: x [M, d] bf16 (row stride ld) -> q [M, d] e4m3 (row stride ldq bytes) and *scale_out = s_x (device float);
  *   amax_scratch = 4 device bytes.  d % 16 == 0.
  * rtv_gemm_fp8: C[M,N] bf16 = epilogue((A . W^T) * a_scale[0] * w_scale): A [M,K], W [N,K] e4m3 (lda / ldw in bytes, K % 128 == 0);
- *   the epilogue arguments are rtv_gemm's.  Uses the split-K workspace of rtv_gemm_set_workspace when attached. */
+ *   the epilogue arguments are rtv_gemm's.  Uses the split-K workspace of rtv_gemm_set_workspace when attached.
+ * The same path with one scale per activation row and per weight row (use_fp8 == 2) is declared in rtv_hip_fp8_rows.h. */
 int rtv_quantize_fp8(const void* x, int64_t ld, int M, int d, void* q, int64_t ldq, float* scale_out, void* amax_scratch,
                      rtv_stream_t stream);
 int rtv_gemm_fp8(const void* A, int lda, const void* W, int ldw, const float* a_scale, float w_scale, void* C, int ldc,

@@ -282,21 +282,36 @@ class CausalWanModel:
         self._weights_version += 1
         return _IncompatibleKeys([], [] if strict else unexpected)
 
-    def enable_fp8(self):
+    def enable_fp8(self, granularity="tensor"):
         """The reference's `enable_fp8` switch (release_server.py:179-182: torchao quantize_ with
         Float8DynamicActivationFloat8WeightConfig(PerTensor) over every nn.Linear, after fuse_projections): weights become
         e4m3 with one scale per tensor (max|W| / 448), activations are quantised per call inside the forward
         (rtv_quantize_fp8), products accumulate in fp32 (rtv_gemm_fp8).  The Conv3d patch embedding is not an nn.Linear and
         stays bf16.  Call after load_state_dict / init_random_weights; the bf16 copies of the quantised weights are freed.
         Under context parallelism every rank quantises the token rows it holds with its own scale (a per-rank torchao
-        linear does exactly that), so the sharded fp8 forward equals the unsharded one up to quantisation noise only."""
+        linear does exactly that), so the sharded fp8 forward equals the unsharded one up to quantisation noise only.
+
+        granularity="row" (opt-in; "tensor" is the default and the reference's): torchao's other granularity, PerRow() - one scale
+        per activation row and one per weight row (output channel), kept as device tensors; the fused [3d, d] qkv weight carries
+        3d of them.  A row's quantisation needs that row alone: one pass over the activations, fused into the LayerNorm in front
+        of qkv / cross-q / ffn.0 (include/rtv_hip_fp8_rows.h), and a context-parallel rank takes exactly the decisions of the
+        unsharded forward.  Parity with torchao itself is unpinned for this granularity as for the other (restated from its
+        published source: tests/fp8_rows_oracle.py).  The granularity cannot be changed once fp8 is on: the bf16 weights are gone."""
+        if granularity not in ("tensor", "row"):
+            raise ValueError(f"enable_fp8: granularity must be 'tensor' or 'row', got {granularity!r}")
+        mode = 2 if granularity == "row" else 1
         if self._w is None:
             raise RuntimeError("load weights before enable_fp8()")
         if self._cfg.use_fp8:
+            if self._cfg.use_fp8 != mode:
+                raise RuntimeError(f"enable_fp8({granularity!r}): fp8 is on with the other granularity and the bf16 weights are gone - "
+                                   "reload the weights first")
             return self
         for k in (self.dim, self.ffn_dim, self.text_dim, self.freq_dim):
             if k % 128:
                 raise ValueError("enable_fp8: every Linear input width must be a multiple of 128")
+        if mode == 2:
+            return self._enable_fp8_rows()
         scales = (ctypes.c_float * (len(_FP8_TOP) + len(_FP8_LAYER) * self.num_layers))()
 
         def quant(key):
@@ -326,6 +341,38 @@ class CausalWanModel:
         s = w.float().abs().max().clamp(min=1e-12) / 448.0      # on the GPU, like torchao's choose-scale
         q = (w.float() / s).clamp(-448.0, 448.0).to(torch.float8_e4m3fn).contiguous()
         return q, float(s)
+
+    def _enable_fp8_rows(self):
+        """enable_fp8("row"): every Linear weight becomes e4m3 with one scale per row; the scales stay on the device, one fp32 [N]
+        tensor per weight, and rtv_dit_weights.fp8_row_scales is the host table of their addresses (order of fp8_scales)."""
+        keys = list(_FP8_TOP) + [f"L{l}.{name}" for l in range(self.num_layers) for name in _FP8_LAYER]
+        table = (c_vp * len(keys))()
+        self._fp8_row_scales = {}         # _tensors key -> its row scales; a LoRA re-merge refreshes them in place
+        for i, key in enumerate(keys):
+            q, rs = self._quantize_fp8_rows(self._tensors[key])
+            self._tensors[key], self._fp8_row_scales[key] = q, rs
+            table[i] = rs.data_ptr()
+            if i < len(_FP8_TOP):
+                setattr(self._w, key, q.data_ptr())
+            else:
+                layer, field = key[1:].split(".")
+                setattr(self._layers_arr[int(layer)], field, q.data_ptr())
+        self._fp8_row_table = table
+        self._w.fp8_row_scales = ctypes.cast(table, ctypes.POINTER(c_vp))
+        self._cfg.use_fp8 = 2
+        self._graphs.clear()
+        self._weights_version += 1
+        self._ws.clear()                  # the workspace grows by the fp8 activation buffer and its row scales
+        ops.ensure_gemm_workspace(self.device)
+        return self
+
+    @staticmethod
+    def _quantize_fp8_rows(w):
+        """bf16 matrix [N, K] -> (e4m3 matrix, fp32 [N] scales): the per-row quantisation of enable_fp8("row") (and of a LoRA
+        re-merge under it).  Once per weight, so torch does it; the arithmetic is the activation quantiser's."""
+        s = w.float().abs().amax(dim=1, keepdim=True).clamp(min=1e-12) / 448.0
+        q = (w.float() / s).clamp(-448.0, 448.0).to(torch.float8_e4m3fn).contiguous()
+        return q, s.reshape(-1).contiguous()
 
     # ------------------------------------------------------------------ LoRA adapters (lora.py, include/rtv_hip_lora.h)
     def lora_adapters(self):
@@ -389,7 +436,8 @@ class CausalWanModel:
     def _remerge(self, keys):
         """Rebuild the matrices `keys` from their bases with every adapter on them: one rtv_lora_merge per matrix, per q / k / v
         row block of a fused qkv_w.  bf16: into the live weight, in place.  fp8: into a temporary bf16 matrix, re-quantised with
-        enable_fp8's routine into the existing e4m3 buffer; its scale is replaced and the graphs, which may hold it by value, go."""
+        enable_fp8's routine into the existing e4m3 buffer; its scale is replaced (per-row scales: refreshed in their device tensor) and the
+        graphs, which may hold it by value, go."""
         fp8, cross = bool(self._cfg.use_fp8), False
         for key in sorted(keys):
             base = self._lora_base[key]
@@ -399,7 +447,11 @@ class CausalWanModel:
             for row0, rows in blocks:
                 lora.merge(base[row0:row0 + rows], out[row0:row0 + rows],
                            [(tg.A, tg.B, s * tg.factor) for s, tg in live if (tg.row0, tg.rows) == (row0, rows)])
-            if fp8:
+            if self._cfg.use_fp8 == 2:
+                q, rs = self._quantize_fp8_rows(out)
+                self._tensors[key].copy_(q)
+                self._fp8_row_scales[key].copy_(rs)      # in place: rtv_dit_weights.fp8_row_scales keeps pointing at it
+            elif fp8:
                 q, s = self._quantize_fp8(out)
                 self._tensors[key].copy_(q)
                 layer, field = key[1:].split(".")

@@ -94,6 +94,7 @@ struct DitBuffers {
   uint16_t *x, *xn, *qkv, *q, *ao, *h, *prow, *hrow;
   uint16_t *sinus, *te1, *e, *se, *e0, *emod, *ehead, *ctx1, *ctx, *ktmp;
   uint8_t* q8;      // fp8 path: the quantised activation of the linear being computed
+  float* frow;      // fp8 path with per-row scales (use_fp8 == 2): the row scales of the activation in q8
   float* fscale;    // fp8 path: its per-tensor scale (device), followed by the 4-byte absmax scratch
   float* attn_part; // KV-split self-attention of a sharded call: fp32 partial outputs + (m, l) of splits x heads x rows <= H x M
   size_t attn_part_bytes;
@@ -129,6 +130,7 @@ static size_t carve(const rtv_dit_config* c, int F, int gh, int gw, char* base, 
     if ((size_t)c->text_dim > k) k = c->text_dim;
     if ((size_t)c->freq_dim > k) k = c->freq_dim;
     t.q8 = (uint8_t*)ws.take(c->use_fp8 ? rows * k : 0);
+    t.frow = (float*)ws.take(c->use_fp8 == 2 ? rows * sizeof(float) : 0);   // (an empty take moves nothing: modes 0 / 1 keep their layout)
     t.fscale = (float*)ws.take(256);
   }
   // KV-split self-attention of sharded calls, only when the configuration asks for it (97 MB per workspace at 14B
@@ -247,8 +249,8 @@ extern "C" size_t rtv_dit_workspace_bytes(const rtv_dit_config* cfg, int F, int 
 }
 
 // nn.Linear on `M` rows with optional fused epilogue; `row_off` = global index of row 0 for the per-frame gate.
-// fp8 mode (cfg->use_fp8, release_server.py:179-182): every nn.Linear quantises its input per tensor (dynamic) and
-// multiplies e4m3 operands; `sidx` indexes the weight's per-tensor scale in rtv_dit_weights.fp8_scales (< 0: the op is
+// fp8 mode (cfg->use_fp8, release_server.py:179-182): every nn.Linear quantises its input per tensor (dynamic; use_fp8 == 2: per
+// row, rtv_hip_fp8_rows.h) and multiplies e4m3 operands; `sidx` indexes the weight's per-tensor scale in rtv_dit_weights.fp8_scales (< 0: the op is
 // not an nn.Linear - the Conv3d patch embedding - and stays bf16).
 enum { S_TEXT0 = 0, S_TEXT2, S_TIME0, S_TIME2, S_TPROJ, S_HEAD, S_LAYER0 };
 enum { S_QKV = 0, S_O, S_CQ, S_CK, S_CV, S_CO, S_FFN0, S_FFN2, S_PER_LAYER };
@@ -256,11 +258,34 @@ static int linear(Ctx& c, int sidx, const void* a, int K, const void* w, const v
                   const void* gate, int gate_stride, int rpf, int row_off, const void* res, int cfg, rtv_stream_t s) {
   if (!c.cfg->use_fp8 || sidx < 0)
     return rtv_gemm(a, K, w, K, out, N, M, N, K, bias, act, gate, gate_stride, rpf, row_off, res, N, RTV_DTYPE_BF16, cfg, s);
+  if (c.cfg->use_fp8 == 2) {
+    // per-row scales: the quantisation of a row needs that row alone, so a token shard takes the unsharded forward's decisions.
+    // a == nullptr: the input is in q8 / frow already (ln_input: the LayerNorm in front of this Linear quantised its own output)
+    if (!c.w->fp8_row_scales || !c.w->fp8_row_scales[sidx]) return set_error(-1, "dit: use_fp8 == 2 needs rtv_dit_weights.fp8_row_scales");
+    if (a) RTV_TRY(rtv_quantize_fp8_rows(a, K, M, K, c.b.q8, K, c.b.frow, s));
+    return rtv_gemm_fp8_rows(c.b.q8, K, w, K, c.b.frow, (const float*)c.w->fp8_row_scales[sidx], out, N, M, N, K, bias, act, gate,
+                             gate_stride, rpf, row_off, res, N, s);
+  }
   if (!c.w->fp8_scales) return set_error(-1, "dit: use_fp8 needs rtv_dit_weights.fp8_scales");
   // token-sharded calls quantise the rows this rank holds with their own scale - what a per-rank torchao linear does
   if (rtv_quantize_fp8(a, K, M, K, c.b.q8, K, c.b.fscale, c.b.fscale + 1, s)) return -1;
   return rtv_gemm_fp8(c.b.q8, K, w, K, c.b.fscale, c.w->fp8_scales[sidx], out, N, M, N, K, bias, act, gate, gate_stride, rpf,
                       row_off, res, N, s);
+}
+
+// LayerNorm of the local rows of b.x in front of a Linear: modulated by (shift, scale) per frame, or affine (weight, bias).
+// The result goes to b.xn - or, with per-row fp8 scales, straight to e4m3 codes and row scales in q8 / frow: one kernel in place
+// of LayerNorm + quantiser, same bits.  *a = what linear() takes as that Linear's input (null: already quantised).
+static int ln_input(Ctx& c, const void* shift, const void* scale, int frame_stride, const void* weight, const void* bias, const void** a) {
+  DitBuffers& b = c.b;
+  const int rpf = scale ? c.fs : 0, r0 = scale ? c.r0 : 0;
+  if (c.cfg->use_fp8 == 2) {
+    *a = nullptr;
+    return rtv_layernorm_modulate_fp8_rows(b.x, b.q8, c.d, b.frow, c.rc, c.d, c.cfg->eps, shift, scale, frame_stride, rpf, r0, weight, bias,
+                                           c.stream);
+  }
+  *a = b.xn;
+  return rtv_layernorm_modulate(b.x, b.xn, c.rc, c.d, c.cfg->eps, shift, scale, frame_stride, rpf, r0, weight, bias, c.stream);
 }
 
 // ---- embeddings, modulation tables, cross-attention K/V (causal_model.py:874-902)
@@ -315,8 +340,12 @@ static int dit_layer_proj(Ctx& c, int l, int parts, int world, void* q_send, voi
   const int d = c.d;
   if (!(parts & (RTV_PROJ_LN | RTV_PROJ_Q | RTV_PROJ_KV))) return set_error(-1, "dit: empty projection phase");
   const uint16_t* em = b.emod + (size_t)l * c.F * 6 * d;  // [F][6][d]: shift_sa, scale_sa, gate_sa, shift_ffn, scale_ffn, gate_ffn
-  if (parts & RTV_PROJ_LN)
-    RTV_TRY(rtv_layernorm_modulate(b.x, b.xn, c.rc, d, c.cfg->eps, em + 0 * d, em + 1 * d, 6 * d, c.fs, c.r0, nullptr, nullptr, c.stream));
+  // (per-row fp8 scales: the LN phase leaves codes and row scales in q8 / frow, and they stay there for the Q and KV phases of
+  // this layer, as b.xn does in the other modes - no other Linear runs between the projection phases of a layer)
+  if (parts & RTV_PROJ_LN) {
+    const void* ln_out;   // b.xn or q8 / frow: the projections below read them by name
+    RTV_TRY(ln_input(c, em + 0 * d, em + 1 * d, 6 * d, nullptr, nullptr, &ln_out));
+  }
   const bool q = parts & RTV_PROJ_Q, kv = parts & RTV_PROJ_KV;
   if (!q && !kv) return 0;
   // the fused weight is [3d, d] row-major: a column range of the output is a row range of the weight
@@ -376,6 +405,22 @@ static int dit_layer_proj(Ctx& c, int l, int parts, int world, void* q_send, voi
       } else {
         RTV_TRY(rtv_gemm(b.xn, d, wp, d, b.qkv + n0, 3 * d, c.rc, nn, d, bq + n0, 0, nullptr, 0, 0, 0, nullptr, 0, RTV_DTYPE_BF16, c.tc,
                          c.stream));
+      }
+    } else if (c.cfg->use_fp8 == 2) {
+      if (!c.w->fp8_row_scales || !c.w->fp8_row_scales[S_LAYER0 + S_PER_LAYER * l + S_QKV])
+        return set_error(-1, "dit: use_fp8 == 2 needs rtv_dit_weights.fp8_row_scales");
+      // the fused weight carries 3d row scales: a launch over a row range of it takes the matching slice
+      const float* wrs = (const float*)c.w->fp8_row_scales[S_LAYER0 + S_PER_LAYER * l + S_QKV];
+      if (v_dst) {
+        if (2 * d > n0)
+          RTV_TRY(rtv_gemm_fp8_rows(b.q8, d, wp, d, b.frow, wrs + n0, b.qkv + n0, 3 * d, c.rc, 2 * d - n0, d, bq + n0, 0, nullptr, 0, 0, 0,
+                                    nullptr, 0, c.stream));
+        RTV_TRY(rtv_gemm_fp8_rows(b.q8, d, wv, d, b.frow, wrs + 2 * d, v_dst, (int)st->kv_row_stride, c.rc, d, d, bq + 2 * d, 0, nullptr, 0, 0,
+                                  0, nullptr, 0, c.stream));
+        v_in_place = true;
+      } else {
+        RTV_TRY(rtv_gemm_fp8_rows(b.q8, d, wp, d, b.frow, wrs + n0, b.qkv + n0, 3 * d, c.rc, nn, d, bq + n0, 0, nullptr, 0, 0, 0, nullptr, 0,
+                                  c.stream));
       }
     } else {
       if (!c.w->fp8_scales) return set_error(-1, "dit: use_fp8 needs rtv_dit_weights.fp8_scales");
@@ -489,8 +534,9 @@ static int dit_after_attn(Ctx& c, int l) {
   const float scale = 1.0f / sqrtf((float)hd);
   RTV_TRY(linear(c, S_LAYER0 + S_PER_LAYER * l + S_O, b.ao, d, lw.o_w, lw.o_b, b.x, rc, d, 0, em + 2 * d, 6 * d, fs, r0, b.x, tc, stream));
   // cross attention (causal_model.py:480, model.py:171-228)
-  RTV_TRY(rtv_layernorm_modulate(b.x, b.xn, rc, d, eps, nullptr, nullptr, 0, 0, 0, lw.norm3_w, lw.norm3_b, stream));
-  RTV_TRY(linear(c, S_LAYER0 + S_PER_LAYER * l + S_CQ, b.xn, d, lw.cq_w, lw.cq_b, b.qkv, rc, d, 0, nullptr, 0, 0, 0, nullptr, tc, stream));
+  const void* ln_out = nullptr;
+  RTV_TRY(ln_input(c, nullptr, nullptr, 0, lw.norm3_w, lw.norm3_b, &ln_out));
+  RTV_TRY(linear(c, S_LAYER0 + S_PER_LAYER * l + S_CQ, ln_out, d, lw.cq_w, lw.cq_b, b.qkv, rc, d, 0, nullptr, 0, 0, 0, nullptr, tc, stream));
   RTV_TRY(rtv_rmsnorm(b.qkv, d, b.q, d, rc, d, eps, lw.cnorm_q_w, stream));
   if (c.fold_k) {
     // short prompt: ao . Wo^T = sum_h P_h . (V_h . Wo_h^T) - the probabilities [rc][fold_k] go into b.ao, the projection multiplies
@@ -509,8 +555,8 @@ static int dit_after_attn(Ctx& c, int l) {
     RTV_TRY(linear(c, S_LAYER0 + S_PER_LAYER * l + S_CO, b.ao, d, lw.co_w, lw.co_b, b.x, rc, d, 0, nullptr, 0, 0, 0, b.x, tc, stream));
   }
   // FFN (causal_model.py:482-488)
-  RTV_TRY(rtv_layernorm_modulate(b.x, b.xn, rc, d, eps, em + 3 * d, em + 4 * d, 6 * d, fs, r0, nullptr, nullptr, stream));
-  RTV_TRY(linear(c, S_LAYER0 + S_PER_LAYER * l + S_FFN0, b.xn, d, lw.ffn0_w, lw.ffn0_b, b.h, rc, c.ffn, RTV_ACT_GELU_TANH, nullptr, 0, 0, 0, nullptr, tc, stream));
+  RTV_TRY(ln_input(c, em + 3 * d, em + 4 * d, 6 * d, nullptr, nullptr, &ln_out));
+  RTV_TRY(linear(c, S_LAYER0 + S_PER_LAYER * l + S_FFN0, ln_out, d, lw.ffn0_w, lw.ffn0_b, b.h, rc, c.ffn, RTV_ACT_GELU_TANH, nullptr, 0, 0, 0, nullptr, tc, stream));
   RTV_TRY(linear(c, S_LAYER0 + S_PER_LAYER * l + S_FFN2, b.h, c.ffn, lw.ffn2_w, lw.ffn2_b, b.x, rc, d, 0, em + 5 * d, 6 * d, fs, r0, b.x, tc, stream));
   return 0;
 }

@@ -6,6 +6,7 @@
 
 #include "../../include/rtv_hip.h"
 #include "../../include/rtv_hip_cross_fold.h"
+#include "../../include/rtv_hip_fp8_rows.h"
 #include "../../include/rtv_hip_lab.h"
 
 namespace rtv {
@@ -57,6 +58,9 @@ int launch_quantize_fp8(const uint16_t* x, int64_t ld, int M, int d, uint8_t* q,
                         unsigned* amax_scratch, hipStream_t stream);
 int launch_gemm_fp8(GemmParams p, const uint8_t* A, int lda, const uint8_t* W, int ldw, const float* a_scale, float w_scale,
                     hipStream_t stream);
+// its per-row-scale variant (gemm_fp8_rows.hip; the row quantisers are fp8_rows.hip's C entry points)
+int launch_gemm_fp8_rows(GemmParams p, const uint8_t* A, int lda, const uint8_t* W, int ldw, const float* a_scales,
+                         const float* w_scales, hipStream_t stream);
 
 // elementwise.hip: rtv_qk_norm_rope_cache with the optional head-group scatter, and its inverse for the attention output
 int qk_norm_rope_check(int64_t cache_row_stride, int cache_row0, int M, int d, int num_heads, int F, int gh, int gw, int start_frame,

@@ -339,6 +339,58 @@ def gemm_fp8(a_q, a_scale, w_q, w_scale, bias=None, act=ACT_NONE, gate=None, gat
     return out
 
 
+# --------------------------------------------------------------------------------------- fp8 path, per-row scales
+def quantize_fp8_rows(x, out=None):
+    """Dynamic per-row e4m3 quantisation of a bf16 matrix (torchao PerRow semantics, include/rtv_hip_fp8_rows.h): returns
+    (q, scales) with q[m] = e4m3(clamp(x[m] / scales[m], +-448)) and scales[m] = max(max|x[m]|, 1e-12) / 448, an fp32 [M] tensor."""
+    _gpu(x, out)
+    if x.dtype != torch.bfloat16 or x.dim() != 2 or x.stride(1) != 1:
+        raise TypeError("quantize_fp8_rows expects a K-contiguous bf16 matrix")
+    M, d = x.shape
+    if out is None:
+        out = torch.empty((M, d), dtype=torch.float8_e4m3fn, device=x.device)
+    scales = torch.empty(M, dtype=torch.float32, device=x.device)
+    _lib.call("rtv_quantize_fp8_rows", _ptr(x), ctypes.c_int64(x.stride(0)), M, d, _ptr(out), ctypes.c_int64(out.stride(0)),
+              _ptr(scales), _stream())
+    return out, scales
+
+
+def layernorm_modulate_fp8_rows(x, eps=1e-6, shift=None, scale=None, frame_stride=0, rows_per_frame=0, weight=None, bias=None,
+                                row_offset=0):
+    """layernorm_modulate followed by quantize_fp8_rows on its bf16 result, in one kernel and bit for bit: returns (q, scales)."""
+    _gpu(x, shift, scale, weight, bias)
+    if x.dtype != torch.bfloat16 or x.dim() != 2 or not x.is_contiguous():
+        raise TypeError("layernorm_modulate_fp8_rows expects a contiguous bf16 matrix")
+    M, d = x.shape
+    out = torch.empty((M, d), dtype=torch.float8_e4m3fn, device=x.device)
+    scales = torch.empty(M, dtype=torch.float32, device=x.device)
+    _lib.call("rtv_layernorm_modulate_fp8_rows", _ptr(x), _ptr(out), ctypes.c_int64(out.stride(0)), _ptr(scales), M, d, float(eps),
+              _ptr(shift), _ptr(scale), int(frame_stride), int(rows_per_frame), int(row_offset), _ptr(weight), _ptr(bias), _stream())
+    return out, scales
+
+
+def gemm_fp8_rows(a_q, a_scales, w_q, w_scales, bias=None, act=ACT_NONE, gate=None, gate_stride=0, rows_per_frame=0,
+                  residual=None, out=None, row_offset=0):
+    """out[M,N] bf16 = epi((a_q @ w_q^T)[m, n] * a_scales[m] * w_scales[n]): gemm_fp8 with one fp32 scale per row of each operand."""
+    _gpu(a_q, w_q, a_scales, w_scales, bias, gate, residual, out)
+    if a_q.dtype != torch.float8_e4m3fn or w_q.dtype != torch.float8_e4m3fn:
+        raise TypeError("gemm_fp8_rows expects float8_e4m3fn operands")
+    M, K = a_q.shape
+    N = w_q.shape[0]
+    if w_q.shape[1] != K or a_q.stride(1) != 1 or w_q.stride(1) != 1:
+        raise ValueError("gemm_fp8_rows shape / stride mismatch")
+    for s, n in ((a_scales, M), (w_scales, N)):
+        if s.dtype != torch.float32 or s.dim() != 1 or s.shape[0] != n or not s.is_contiguous():
+            raise ValueError("gemm_fp8_rows expects contiguous fp32 scale vectors of M and N elements")
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.bfloat16, device=a_q.device)
+    ensure_gemm_workspace(a_q.device)
+    _lib.call("rtv_gemm_fp8_rows", _ptr(a_q), a_q.stride(0), _ptr(w_q), w_q.stride(0), _ptr(a_scales), _ptr(w_scales),
+              _ptr(out), out.stride(0), M, N, K, _ptr(bias), int(act), _ptr(gate), int(gate_stride), int(rows_per_frame),
+              int(row_offset), _ptr(residual), residual.stride(0) if residual is not None else 0, _stream())
+    return out
+
+
 # --------------------------------------------------------------------------------------- norms
 def layernorm_modulate(x, eps=1e-6, shift=None, scale=None, frame_stride=0, rows_per_frame=0,
                        weight=None, bias=None, out=None, row_offset=0):
