@@ -254,23 +254,44 @@ extern "C" size_t rtv_dit_workspace_bytes(const rtv_dit_config* cfg, int F, int 
 // not an nn.Linear - the Conv3d patch embedding - and stays bf16).
 enum { S_TEXT0 = 0, S_TEXT2, S_TIME0, S_TIME2, S_TPROJ, S_HEAD, S_LAYER0 };
 enum { S_QKV = 0, S_O, S_CQ, S_CK, S_CV, S_CO, S_FFN0, S_FFN2, S_PER_LAYER };
-static int linear(Ctx& c, int sidx, const void* a, int K, const void* w, const void* bias, void* out, int M, int N, int act,
-                  const void* gate, int gate_stride, int rpf, int row_off, const void* res, int cfg, rtv_stream_t s) {
-  if (!c.cfg->use_fp8 || sidx < 0)
-    return rtv_gemm(a, K, w, K, out, N, M, N, K, bias, act, gate, gate_stride, rpf, row_off, res, N, RTV_DTYPE_BF16, cfg, s);
+static bool is_fp8(const Ctx& c, int sidx) { return c.cfg->use_fp8 && sidx >= 0; }
+
+// Quantise half of a Linear: its input `a` [M][K] becomes e4m3 codes in q8 and the mode's scales in fscale / frow.  Nothing to do in
+// bf16, and nothing when a == nullptr: the input is in q8 / frow already (ln_input: the LayerNorm in front of this Linear quantised
+// its own output).  The weight's scales are asked for here, in front of the first launch of the Linear.
+static int quantize_input(Ctx& c, int sidx, const void* a, int M, int K, rtv_stream_t s) {
+  if (!is_fp8(c, sidx)) return 0;
   if (c.cfg->use_fp8 == 2) {
-    // per-row scales: the quantisation of a row needs that row alone, so a token shard takes the unsharded forward's decisions.
-    // a == nullptr: the input is in q8 / frow already (ln_input: the LayerNorm in front of this Linear quantised its own output)
+    // per-row scales: the quantisation of a row needs that row alone, so a token shard takes the unsharded forward's decisions
     if (!c.w->fp8_row_scales || !c.w->fp8_row_scales[sidx]) return set_error(-1, "dit: use_fp8 == 2 needs rtv_dit_weights.fp8_row_scales");
-    if (a) RTV_TRY(rtv_quantize_fp8_rows(a, K, M, K, c.b.q8, K, c.b.frow, s));
-    return rtv_gemm_fp8_rows(c.b.q8, K, w, K, c.b.frow, (const float*)c.w->fp8_row_scales[sidx], out, N, M, N, K, bias, act, gate,
-                             gate_stride, rpf, row_off, res, N, s);
+    return a ? rtv_quantize_fp8_rows(a, K, M, K, c.b.q8, K, c.b.frow, s) : 0;
   }
   if (!c.w->fp8_scales) return set_error(-1, "dit: use_fp8 needs rtv_dit_weights.fp8_scales");
   // token-sharded calls quantise the rows this rank holds with their own scale - what a per-rank torchao linear does
-  if (rtv_quantize_fp8(a, K, M, K, c.b.q8, K, c.b.fscale, c.b.fscale + 1, s)) return -1;
-  return rtv_gemm_fp8(c.b.q8, K, w, K, c.b.fscale, c.w->fp8_scales[sidx], out, N, M, N, K, bias, act, gate, gate_stride, rpf,
-                      row_off, res, N, s);
+  return rtv_quantize_fp8(a, K, M, K, c.b.q8, K, c.b.fscale, c.b.fscale + 1, s) ? -1 : 0;
+}
+
+// Project half: output columns [w_row0, w_row0 + N) of the Linear = that row range of its weight [..][K] and of its bias, into
+// out [M][ldc], from `a` (bf16) or from what quantize_input left.  A per-tensor scale holds for the weight whichever rows a launch
+// takes; of the row scales it takes the matching slice.
+static int project(Ctx& c, int sidx, const void* a, int K, const void* w, int w_row0, const void* bias, void* out, int ldc, int M, int N,
+                   int act, const void* gate, int gate_stride, int rpf, int row_off, const void* res, int cfg, rtv_stream_t s) {
+  const bool fp8 = is_fp8(c, sidx);
+  const void* wp = (const char*)w + (size_t)w_row0 * K * (fp8 ? 1 : 2);   // fp8 weights are bytes
+  const void* bp = bias ? (const uint16_t*)bias + w_row0 : nullptr;
+  const int ldr = res ? ldc : 0;
+  if (!fp8) return rtv_gemm(a, K, wp, K, out, ldc, M, N, K, bp, act, gate, gate_stride, rpf, row_off, res, ldr, RTV_DTYPE_BF16, cfg, s);
+  if (c.cfg->use_fp8 == 2)
+    return rtv_gemm_fp8_rows(c.b.q8, K, wp, K, c.b.frow, (const float*)c.w->fp8_row_scales[sidx] + w_row0, out, ldc, M, N, K, bp, act, gate,
+                             gate_stride, rpf, row_off, res, ldr, s);
+  return rtv_gemm_fp8(c.b.q8, K, wp, K, c.b.fscale, c.w->fp8_scales[sidx], out, ldc, M, N, K, bp, act, gate, gate_stride, rpf, row_off, res,
+                      ldr, s);
+}
+
+static int linear(Ctx& c, int sidx, const void* a, int K, const void* w, const void* bias, void* out, int M, int N, int act,
+                  const void* gate, int gate_stride, int rpf, int row_off, const void* res, int cfg, rtv_stream_t s) {
+  RTV_TRY(quantize_input(c, sidx, a, M, K, s));
+  return project(c, sidx, a, K, w, 0, bias, out, N, M, N, act, gate, gate_stride, rpf, row_off, res, cfg, s);
 }
 
 // LayerNorm of the local rows of b.x in front of a Linear: modulated by (shift, scale) per frame, or affine (weight, bias).
@@ -350,13 +371,8 @@ static int dit_layer_proj(Ctx& c, int l, int parts, int world, void* q_send, voi
   if (!q && !kv) return 0;
   // the fused weight is [3d, d] row-major: a column range of the output is a row range of the weight
   const int n0 = q ? 0 : d, nn = (q ? d : 0) + (kv ? 2 * d : 0);
-  const uint16_t* wq = (const uint16_t*)lw.qkv_w;
-  const uint16_t* bq = (const uint16_t*)lw.qkv_b;
-  const size_t welt = c.cfg->use_fp8 ? 1 : 2;   // fp8 weights are bytes
   bool v_in_place = false;
   {
-    const void* wp = (const char*)lw.qkv_w + (size_t)n0 * d * welt;
-    (void)wq;
     // r05: when this call's cache rows are ONE physical row range (always, unless a ring write wraps), the V third of the projection
     // is a GEMM of its own whose output matrix IS those rows of the V cache; the RoPE / cache kernel then moves a third less
     // (rope_parts | 4).  (One launch with a second output matrix was built first: three more kernel arguments, or one more epilogue
@@ -376,7 +392,6 @@ static int dit_layer_proj(Ctx& c, int l, int parts, int world, void* q_send, voi
       uint16_t* dst = (uint16_t*)st->kv_v[l] + (size_t)r0 * st->kv_row_stride;
       if (one_range && !((uintptr_t)dst & 15)) v_dst = dst;
     }
-    const void* wv = (const char*)lw.qkv_w + (size_t)2 * d * d * welt;   // the V rows of the fused weight
     // Everything the RoPE / cache launch behind the GEMMs would refuse is refused HERE, before a GEMM has written V rows into the
     // cache (a failing call used to leave the V rows overwritten and the K rows untouched).
     {
@@ -392,50 +407,20 @@ static int dit_layer_proj(Ctx& c, int l, int parts, int world, void* q_send, voi
                                    st->ring_lo, st->ring_size, st->ring_shift, rp));
       }
     }
-    if (!c.cfg->use_fp8) {
-      if (v_dst) {
-        // two launches: columns [n0, 2d) into the projection buffer, the V third straight into the cache rows (Q | K at M = 4680 is 760
-        // tiles = 2.97 rounds of the 256 CUs, V the o-projection's shape: +6 us on the fused launch's 563, against the 21 us the copy cost)
-        if (2 * d > n0)
-          RTV_TRY(rtv_gemm(b.xn, d, wp, d, b.qkv + n0, 3 * d, c.rc, 2 * d - n0, d, bq + n0, 0, nullptr, 0, 0, 0, nullptr, 0, RTV_DTYPE_BF16,
-                           c.tc, c.stream));
-        RTV_TRY(rtv_gemm(b.xn, d, wv, d, v_dst, (int)st->kv_row_stride, c.rc, d, d, bq + 2 * d, 0, nullptr, 0, 0, 0, nullptr, 0,
-                         RTV_DTYPE_BF16, c.tc, c.stream));
-        v_in_place = true;
-      } else {
-        RTV_TRY(rtv_gemm(b.xn, d, wp, d, b.qkv + n0, 3 * d, c.rc, nn, d, bq + n0, 0, nullptr, 0, 0, 0, nullptr, 0, RTV_DTYPE_BF16, c.tc,
-                         c.stream));
-      }
-    } else if (c.cfg->use_fp8 == 2) {
-      if (!c.w->fp8_row_scales || !c.w->fp8_row_scales[S_LAYER0 + S_PER_LAYER * l + S_QKV])
-        return set_error(-1, "dit: use_fp8 == 2 needs rtv_dit_weights.fp8_row_scales");
-      // the fused weight carries 3d row scales: a launch over a row range of it takes the matching slice
-      const float* wrs = (const float*)c.w->fp8_row_scales[S_LAYER0 + S_PER_LAYER * l + S_QKV];
-      if (v_dst) {
-        if (2 * d > n0)
-          RTV_TRY(rtv_gemm_fp8_rows(b.q8, d, wp, d, b.frow, wrs + n0, b.qkv + n0, 3 * d, c.rc, 2 * d - n0, d, bq + n0, 0, nullptr, 0, 0, 0,
-                                    nullptr, 0, c.stream));
-        RTV_TRY(rtv_gemm_fp8_rows(b.q8, d, wv, d, b.frow, wrs + 2 * d, v_dst, (int)st->kv_row_stride, c.rc, d, d, bq + 2 * d, 0, nullptr, 0, 0,
-                                  0, nullptr, 0, c.stream));
-        v_in_place = true;
-      } else {
-        RTV_TRY(rtv_gemm_fp8_rows(b.q8, d, wp, d, b.frow, wrs + n0, b.qkv + n0, 3 * d, c.rc, nn, d, bq + n0, 0, nullptr, 0, 0, 0, nullptr, 0,
-                                  c.stream));
-      }
+    const int sidx = S_LAYER0 + S_PER_LAYER * l + S_QKV;
+    const void* a = c.cfg->use_fp8 == 2 ? nullptr : b.xn;   // what the LN phase left: b.xn, or codes and row scales in q8 / frow
+    RTV_TRY(quantize_input(c, sidx, a, c.rc, d, c.stream));
+    auto proj = [&](int w_row0, int N, void* out, int ldc) {
+      return project(c, sidx, a, d, lw.qkv_w, w_row0, lw.qkv_b, out, ldc, c.rc, N, 0, nullptr, 0, 0, 0, nullptr, c.tc, c.stream);
+    };
+    if (v_dst) {
+      // two launches: columns [n0, 2d) into the projection buffer, the V third straight into the cache rows (Q | K at M = 4680 is 760
+      // tiles = 2.97 rounds of the 256 CUs, V the o-projection's shape: +6 us on the fused launch's 563, against the 21 us the copy cost)
+      if (2 * d > n0) RTV_TRY(proj(n0, 2 * d - n0, b.qkv + n0, 3 * d));
+      RTV_TRY(proj(2 * d, d, v_dst, (int)st->kv_row_stride));
+      v_in_place = true;
     } else {
-      if (!c.w->fp8_scales) return set_error(-1, "dit: use_fp8 needs rtv_dit_weights.fp8_scales");
-      if (rtv_quantize_fp8(b.xn, d, c.rc, d, b.q8, d, b.fscale, b.fscale + 1, c.stream)) return -1;
-      const float ws = c.w->fp8_scales[S_LAYER0 + S_PER_LAYER * l + S_QKV];   // ONE scale for the fused weight, whichever rows a launch takes
-      if (v_dst) {
-        if (2 * d > n0)
-          RTV_TRY(rtv_gemm_fp8(b.q8, d, wp, d, b.fscale, ws, b.qkv + n0, 3 * d, c.rc, 2 * d - n0, d, bq + n0, 0, nullptr, 0, 0, 0, nullptr, 0,
-                               c.stream));
-        RTV_TRY(rtv_gemm_fp8(b.q8, d, wv, d, b.fscale, ws, v_dst, (int)st->kv_row_stride, c.rc, d, d, bq + 2 * d, 0, nullptr, 0, 0, 0, nullptr,
-                             0, c.stream));
-        v_in_place = true;
-      } else {
-        RTV_TRY(rtv_gemm_fp8(b.q8, d, wp, d, b.fscale, ws, b.qkv + n0, 3 * d, c.rc, nn, d, bq + n0, 0, nullptr, 0, 0, 0, nullptr, 0, c.stream));
-      }
+      RTV_TRY(proj(n0, nn, b.qkv + n0, 3 * d));
     }
   }
   const int rope_parts = (q ? 1 : 0) | (kv ? 2 : 0) | (v_in_place ? 4 : 0);

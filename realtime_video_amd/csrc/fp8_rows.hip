@@ -7,32 +7,15 @@
 //   quantize_fp8_rows_kernel           x bf16 -> codes + scales; a wave per row up to 2048 columns, a workgroup per row above
 //   layernorm_modulate_fp8_rows_kernel elementwise.hip's layernorm_modulate_kernel with this quantiser behind its bf16 rounding
 // The GEMM that consumes the codes is gemm_fp8_rows.hip.
+#include "fp8_quant.h"
+#include "ln_row.h"
 #include "rtv_common.h"
 #include "rtv_internal.h"
 
 namespace rtv {
 
 namespace f8r {
-constexpr float FP8_MAX = 448.f;
-constexpr int THREADS = 256;
-constexpr int LN_MAXC = 4;   // layernorm_modulate_kernel's EW_MAXC: rows of up to 8192 elements
-
-// scale of a row from its max |x|: torch evaluates `amax / 448.0` (tensor / Python scalar) on the GPU as a multiplication by the
-// fp32 reciprocal (the per-tensor quantiser of gemm_fp8.hip does the same)
-__device__ __forceinline__ float row_scale(float amax) { return fmaxf(amax, 1e-12f) * (1.0f / FP8_MAX); }
-
-// 8 floats -> 8 e4m3 codes (round to nearest even), 8 bytes
-__device__ __forceinline__ u32x2 quantize8(const float* x, float scale) {
-  float v[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) v[j] = fminf(fmaxf(x[j] / scale, -FP8_MAX), FP8_MAX);
-  int w0 = 0, w1 = 0;
-  w0 = __builtin_amdgcn_cvt_pk_fp8_f32(v[0], v[1], w0, false);
-  w0 = __builtin_amdgcn_cvt_pk_fp8_f32(v[2], v[3], w0, true);
-  w1 = __builtin_amdgcn_cvt_pk_fp8_f32(v[4], v[5], w1, false);
-  w1 = __builtin_amdgcn_cvt_pk_fp8_f32(v[6], v[7], w1, true);
-  return u32x2{(uint32_t)w0, (uint32_t)w1};
-}
+constexpr int THREADS = EW_THREADS;
 
 // max over the workgroup's 4 waves (`red`: 4 floats nothing else uses - each kernel calls this once)
 __device__ __forceinline__ float block_max(float v, float* red) {
@@ -40,16 +23,6 @@ __device__ __forceinline__ float block_max(float v, float* red) {
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
   return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-}
-
-// layernorm_modulate_kernel's reduction, kept identical (same order of additions: the fused kernel must give its bits)
-__device__ __forceinline__ float block_sum(float v, float* red) {
-  v = wave_sum(v);
-  const int w = threadIdx.x >> 6;
-  __syncthreads();  // protect `red` from the previous use
-  if ((threadIdx.x & 63) == 0) red[w] = v;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
 }
 }  // namespace f8r
 
@@ -87,7 +60,7 @@ __global__ __launch_bounds__(f8r::THREADS) void quantize_fp8_rows_kernel(const u
     __shared__ float red[4];
     m = block_max(m, red);
   }
-  const float scale = row_scale(m);
+  const float scale = fp8_scale(m);
   if (lane == 0) row_scales[row] = scale;
   uint8_t* qr = q + (int64_t)row * ldq;
 #pragma unroll
@@ -102,9 +75,8 @@ __global__ __launch_bounds__(f8r::THREADS) void quantize_fp8_rows_kernel(const u
 }
 
 // ------------------------------------------------------------------ LayerNorm (+ modulation) + row quantiser, a workgroup per row
-// The first half is layernorm_modulate_kernel (elementwise.hip) statement for statement - same reductions, same rounding points -
-// up to the value it would store; that value is rounded to bf16 as the store would round it, kept in registers, and quantised as
-// quantize_fp8_rows_kernel quantises the stored row.
+// layernorm_modulate_kernel's row (ln_row.h: same reductions, same rounding points) up to the value it would store; that value is
+// rounded to bf16 as the store would round it, kept in registers, and quantised as quantize_fp8_rows_kernel quantises the stored row.
 __global__ __launch_bounds__(f8r::THREADS) void layernorm_modulate_fp8_rows_kernel(
     const bf16_t* __restrict__ x, uint8_t* __restrict__ q, int64_t ldq, float* __restrict__ row_scales, int d, float eps,
     const bf16_t* __restrict__ shift, const bf16_t* __restrict__ scale, int frame_stride, int rows_per_frame, int row_offset,
@@ -114,77 +86,20 @@ __global__ __launch_bounds__(f8r::THREADS) void layernorm_modulate_fp8_rows_kern
   __shared__ float redm[4];
   const int row = blockIdx.x;
   const int nchunks = d >> 3;
-  const bf16_t* xr = x + (size_t)row * d;
-  float v[LN_MAXC][8];
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < LN_MAXC; ++i) {
-    int c = threadIdx.x + i * THREADS;
-    if (c < nchunks) {
-      u32x4 raw = *(const u32x4*)(xr + c * 8);
-      unpack_bf16x8(raw, v[i]);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) s += v[i][j];
-    }
-  }
-  const float mean = block_sum(s, red) / (float)d;
-  float s2 = 0.f;
-#pragma unroll
-  for (int i = 0; i < LN_MAXC; ++i) {
-    int c = threadIdx.x + i * THREADS;
-    if (c < nchunks) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        float t = v[i][j] - mean;
-        s2 += t * t;
-      }
-    }
-  }
-  const float var = block_sum(s2, red) / (float)d;
-  const float rstd = rsqrtf(var + eps);
-  const int f = rows_per_frame > 0 ? (row_offset + row) / rows_per_frame : 0;
-  const bf16_t* sh = shift ? shift + (size_t)f * frame_stride : nullptr;
-  const bf16_t* sc = scale ? scale + (size_t)f * frame_stride : nullptr;
+  float v[EW_MAXC][8];
   float m = 0.f;
+  layernorm_row(x, d, eps, shift, scale, frame_stride, rows_per_frame, row_offset, weight, bias, red, [&](int i, int, const float* o) {
 #pragma unroll
-  for (int i = 0; i < LN_MAXC; ++i) {
-    int c = threadIdx.x + i * THREADS;
-    if (c < nchunks) {
-      float o[8];
-      if (weight) {  // affine LayerNorm: one rounding at the output (torch kernel computes in f32)
-        float w8[8], b8[8];
-        unpack_bf16x8(*(const u32x4*)(weight + c * 8), w8);
-        unpack_bf16x8(*(const u32x4*)(bias + c * 8), b8);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) o[j] = (v[i][j] - mean) * rstd * w8[j] + b8[j];
-      } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) o[j] = (v[i][j] - mean) * rstd;
-        if (sc) {  // bf16(bf16(bf16(ln) * bf16(1 + scale)) + shift)
-          float sc8[8], sh8[8];
-          unpack_bf16x8(*(const u32x4*)(sc + c * 8), sc8);
-          unpack_bf16x8(*(const u32x4*)(sh + c * 8), sh8);
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            float n = round_bf16(o[j]);
-            float a = round_bf16(1.0f + sc8[j]);
-            float p = round_bf16(n * a);
-            o[j] = p + sh8[j];
-          }
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        v[i][j] = round_bf16(o[j]);   // the bf16 value layernorm_modulate_kernel stores: what the Linear's input is
-        m = fmaxf(m, fabsf(v[i][j]));
-      }
+    for (int j = 0; j < 8; ++j) {
+      v[i][j] = round_bf16(o[j]);   // the bf16 value layernorm_modulate_kernel stores: what the Linear's input is
+      m = fmaxf(m, fabsf(v[i][j]));
     }
-  }
-  const float qs = row_scale(block_max(m, redm));
+  });
+  const float qs = fp8_scale(block_max(m, redm));
   if (threadIdx.x == 0) row_scales[row] = qs;
   uint8_t* qr = q + (int64_t)row * ldq;
 #pragma unroll
-  for (int i = 0; i < LN_MAXC; ++i) {
+  for (int i = 0; i < EW_MAXC; ++i) {
     int c = threadIdx.x + i * THREADS;
     if (c < nchunks) *(u32x2*)(qr + c * 8) = quantize8(v[i], qs);
   }
@@ -220,7 +135,7 @@ extern "C" int rtv_layernorm_modulate_fp8_rows(const void* x, void* q, int64_t l
                                                int row_offset, const void* weight, const void* bias, rtv_stream_t stream) {
   if (M <= 0) return 0;
   if (!x || !q || !row_scales) return set_error(-1, "layernorm_modulate_fp8_rows: null pointer");
-  if (d % 16 || d > f8r::THREADS * 8 * f8r::LN_MAXC) return set_error(-1, "layernorm_modulate_fp8_rows: d must be a multiple of 16 and <= 8192");
+  if (d % 16 || d > f8r::THREADS * 8 * EW_MAXC) return set_error(-1, "layernorm_modulate_fp8_rows: d must be a multiple of 16 and <= 8192");
   if ((ldq & 7) || ldq < d || ((uintptr_t)x & 15) || ((uintptr_t)q & 7))
     return set_error(-1, "layernorm_modulate_fp8_rows: ldq must be a multiple of 8 and >= d, x 16-byte aligned, q 8-byte aligned");
   if ((shift == nullptr) != (scale == nullptr)) return set_error(-1, "layernorm_modulate_fp8_rows: shift and scale go together");

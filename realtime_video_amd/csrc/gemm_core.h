@@ -33,6 +33,15 @@ struct GemmParams {
   int tiles_m, tiles_n;
 };
 
+// The C entry points' argument lists as GemmParams (the fp8 GEMMs pass their byte operands beside it: A = W = null); the launcher
+// fills in the tile counts.
+inline GemmParams gemm_params(const void* A, int lda, const void* W, int ldw, void* C, int ldc, int M, int N, int K, const void* bias,
+                              int act, const void* gate, int gate_stride, int rows_per_frame, int row_offset, const void* residual,
+                              int ldr) {
+  return GemmParams{(const uint16_t*)A, (const uint16_t*)W, (uint16_t*)C, lda, ldw, ldc, M, N, K, (const uint16_t*)bias, act,
+                    (const uint16_t*)gate, gate_stride, rows_per_frame, row_offset, (const uint16_t*)residual, ldr, 0, 0};
+}
+
 template <bool F16>
 struct Mfma32;
 template <>

@@ -235,25 +235,8 @@ int rtv_gemm(const void* A, int lda, const void* W, int ldw, void* C, int ldc, i
     return set_error(-1, "gemm: C/bias/gate/residual must be 8-byte aligned");
   if (gate && (gate_stride % 4)) return set_error(-1, "gemm: gate_stride must be a multiple of 4");
   if (act < 0 || act > 2) return set_error(-1, "gemm: unknown activation");
-  GemmParams p;
-  p.A = (const uint16_t*)A;
-  p.W = (const uint16_t*)W;
-  p.C = (uint16_t*)C;
-  p.lda = lda;
-  p.ldw = ldw;
-  p.ldc = ldc;
-  p.M = M;
-  p.N = N;
-  p.K = K;
-  p.bias = (const uint16_t*)bias;
-  p.act = act;
-  p.gate = (const uint16_t*)gate;
-  p.gate_stride = gate_stride;
-  p.rows_per_frame = rows_per_frame;
-  p.row_offset = row_offset;
-  p.residual = (const uint16_t*)residual;
-  p.ldr = ldr;
-  p.tiles_m = p.tiles_n = 0;
+  const GemmParams p = gemm_params(A, lda, W, ldw, C, ldc, M, N, K, bias, act, gate, gate_stride, rows_per_frame, row_offset, residual,
+                                   ldr);
   return launch_gemm(p, dtype, tile_cfg, (hipStream_t)stream);
 }
 

@@ -103,6 +103,28 @@ def test_gemm_rows_exact_case(ops):
     assert torch.equal(pad[:, :N].cpu().view(torch.int16), ref_b.view(torch.int16)) and float(pad[:, N:].abs().max()) == 0
 
 
+@pytest.mark.parametrize("with_bias", [False, True])
+@pytest.mark.parametrize("M,N,K", [(257, 264, 128), (4680, 5120, 1024)])
+def test_gemm_rows_equals_the_per_tensor_gemm_under_constant_power_of_two_scales(ops, M, N, K, with_bias):
+    """The two fp8 GEMM kernels are one body (csrc/gemm_fp8_body.h) around two de-quantise steps.  With power-of-two scales that
+    are constant over rows and columns both steps are exact - sum * 2^-8 against sum * 2^-3 * 2^-5 - so on any e4m3 codes the
+    kernels must agree bit for bit.  (257, 264, 128): M and N tails; (4680, 5120, 1024): the last round split along K, whose
+    partial sums are added in index order, so the arrival order cannot show."""
+    g = torch.Generator().manual_seed(M + K)
+
+    def codes(rows):                                                  # every e4m3 code but the two NaNs
+        c = torch.randint(0, 256, (rows, K), generator=g, dtype=torch.uint8)
+        return c.masked_fill((c & 0x7F) == 0x7F, 0).to(DEV).view(torch.float8_e4m3fn)
+
+    aq, wq = codes(M), codes(N)
+    s_x, s_w = 2.0 ** -3, 2.0 ** -5
+    bias = _randn(N, seed=5) if with_bias else None
+    rows = ops.gemm_fp8_rows(aq, torch.full((M,), s_x, device=DEV), wq, torch.full((N,), s_w, device=DEV), bias=bias)
+    tensor = ops.gemm_fp8(aq, torch.full((1,), s_x, device=DEV), wq, s_w, bias=bias)
+    assert bool(torch.isfinite(tensor).all()) and float(tensor.float().abs().max()) > 0
+    assert torch.equal(rows.view(torch.int16), tensor.view(torch.int16))
+
+
 def _quantised_pair(ops, M, N, K):
     a, w, b = _randn(M, K, seed=1), _randn(N, K, seed=2, scale=K ** -0.5), _randn(N, seed=3, scale=0.1)
     aq, sa = ops.quantize_fp8_rows(a)
