@@ -268,6 +268,17 @@ def test_attention_rejects_bad_arguments(ops):
 
 
 # ----------------------------------------------------------------------------------------- elementwise
+# What the row-kernel bars of this section can and cannot see: the rows are iid Gaussians and the bar is a whole-tensor
+# rel-L2 <= 3e-3 against the bf16 eager chain (plus a cap on the fraction of elements that differ at all).  That pins the
+# bf16 ROUNDING POINTS - a kernel that skips round_bf16(x * r) differs in a fifth of its elements - and the shapes the forward
+# uses.  It cannot see a reduction that loses a chunk, a lane column or a wave's partial (at d = 5120 one 8-element chunk is
+# 0.16 % of sum x^2, 0.08 % of every output, a fifth of a bf16 unit roundoff), one RoPE pair on the wrong axis, one row with its
+# neighbouring frame's modulation (a few wrong elements add less than 3e-3 to the rel-L2), a one-pass variance (zero-mean rows
+# are well conditioned) or a misplaced eps (var = 4); and it never sets row_offset > 0, ldx != ldo != d, a head_dim that does not
+# divide 512, or a width at a boundary of the chunk loops.  Those are the business of tests/test_row_kernels_gpu.py: rows in
+# which each chunk in turn carries the sum, offset, near-constant, constant, tiny, huge and mixed-magnitude rows, per-frame
+# tables that tell frames apart, every element against the fp64 definition under a bar derived from the kernel's rounding
+# points (tests/row_cases.py; the Gaussian data of this section under that bar: family `gaussian` there).
 def test_layernorm_modulate_matches_eager_chain(ops):
     """(norm1(x).unflatten(F, fs) * (1 + e[1]) + e[0]).flatten(1, 2), causal_model.py:471."""
     F_, fs, d = 3, 520, 1536
