@@ -12,6 +12,7 @@ Surface used by the reference's callers and reproduced here:
 """
 import collections
 import ctypes
+import math
 import os
 import types
 
@@ -29,6 +30,7 @@ _Cfg = _lib.STRUCTS["rtv_dit_config"]
 _LayerW = _lib.STRUCTS["rtv_dit_layer_weights"]
 _Weights = _lib.STRUCTS["rtv_dit_weights"]
 _Step = _lib.STRUCTS["rtv_dit_step"]
+_Fp8Shadow = _lib.ATTN_FP8_STRUCTS["rtv_attn_fp8_shadow"]
 _LAYER_FIELDS = tuple(n for n, _ in _LayerW._fields_)
 _TOP_FIELDS = tuple(n for n, t in _Weights._fields_ if t is c_vp)      # the device tensors; `layers` / `fp8_scales` are host arrays
 
@@ -135,6 +137,9 @@ class CausalWanModel:
         self._cfg = _Cfg(dim, ffn_dim, num_heads, num_layers, freq_dim, text_dim, text_len, in_dim, out_dim, eps, 0, 0)
         self._lora = {}               # name -> {"scale": float, "targets": {target: lora.Target with A / B on the device}}, in load order
         self._lora_base = {}          # _tensors key -> bf16 copy of the matrix as loaded; kept outside _tensors / parameters()
+        self._fp8_attn = None         # (k_scale, v_scale, epoch) while enable_fp8_attention() is on
+        self._fp8_attn_epoch = 0      # bumps at every enable / disable: a shadow filled before it is refilled from the bf16 cache
+        self._fp8_attn_amax = None    # float32 [num_layers, 2], allocated once
         self.lora_version = 0         # bumps when a merge changes ck_w / cv_w / co_w: crossattn_cache entries carry the one they were made with
 
     # ------------------------------------------------------------------ nn.Module-ish conveniences
@@ -334,6 +339,72 @@ class CausalWanModel:
         self._ws.clear()                  # the workspace grows by the fp8 activation buffer
         ops.ensure_gemm_workspace(self.device)
         return self
+
+    def enable_fp8_attention(self, k_scale=1.0, v_scale=1.0):
+        """Opt-in: self-attention in the precision of the reference's SageAttention backend (wan/modules/sage.py: 8-bit Q K^T, fp8
+        P V) on an OCP e4m3 shadow of the KV cache (include/rtv_hip_attn_fp8.h).  Independent of enable_fp8(), which concerns the
+        Linears; cross-attention and the VAE stay as they are.  K / V codes are e4m3(x / scale) with one scale per tensor kind, Q is
+        quantised per (row, head) inside the kernel.
+
+        The shadow lives in each layer's kv_cache dict ("k8", "v8t"): allocated once, zero-filled, by the first forward that finds
+        none and filled from the whole bf16 cache in one quantiser call (again, without allocating, when the scales change or the
+        mode was off in between); from then on every forward quantises exactly the rows it writes.  Nothing is allocated after
+        that first forward, so captured hipGraphs stay valid.  The bf16 cache is kept.
+
+        Choosing the scales: fp8_attention_amax() returns the largest |k| and |v| quantised so far, per layer.  A value approaching
+        448 * scale calls for a larger scale (beyond it the codes saturate).  K is RMS-normalised and V is a Linear of a LayerNormed
+        input, so 1.0 is the expected setting - but nobody has checked this on the real checkpoint, because none is available
+        offline: look at fp8_attention_amax() after the first blocks.
+
+        Under context parallelism the forward raises: the sharded phases and the KV split have no fp8 kernels."""
+        k_scale, v_scale = float(k_scale), float(v_scale)
+        for s in (k_scale, v_scale):
+            if not (math.isfinite(s) and s > 0):
+                raise ValueError("enable_fp8_attention: scales must be finite and positive")
+        self._fp8_attn_epoch += 1
+        self._fp8_attn = (k_scale, v_scale, self._fp8_attn_epoch)
+        return self
+
+    def disable_fp8_attention(self):
+        """Back to bf16 self-attention: every launch is the one a model that never enabled the mode issues.  The shadows stay in the
+        cache dicts and are refilled from the bf16 cache when the mode comes back."""
+        self._fp8_attn_epoch += 1
+        self._fp8_attn = None
+        return self
+
+    def fp8_attention_amax(self):
+        """float32 [num_layers, 2]: the largest |k| and |v| (raw bf16 values) quantised into a shadow since the mode first ran."""
+        if self._fp8_attn_amax is None:
+            raise RuntimeError("fp8 attention has not run yet")
+        return self._fp8_attn_amax
+
+    def _fp8_attention_shadow(self, kv_cache, use_cp):
+        """The rtv_attn_fp8_shadow of this forward (None: bf16 attention) and what must stay alive with it."""
+        if self._fp8_attn is None:
+            return None, None
+        if use_cp:
+            raise RuntimeError("fp8 attention does not support context parallelism (sharded calls and the KV split have no fp8 kernels)")
+        k_scale, v_scale, epoch = self._fp8_attn
+        L = self.num_layers
+        if self._fp8_attn_amax is None:
+            self._fp8_attn_amax = torch.zeros(L, 2, dtype=torch.float32, device=kv_cache[0]["k"].device)
+        rows = kv_cache[0]["k"].shape[1]
+        for l, c in enumerate(kv_cache):
+            if c["k"].shape[0] != 1 or c["k"].shape[1] != rows:
+                raise ValueError("fp8 attention: batch size 1 and the same number of rows in every layer's KV cache")
+            H = c["k"].shape[2]
+            if "k8" not in c or tuple(c["k8"].shape[:2]) != (rows, H) or c["k8"].device != c["k"].device:
+                c["k8"], c["v8t"] = ops.attn_fp8_shadow(rows, H, c["k"].device)
+                c["fp8_filled"] = None
+            state = (k_scale, v_scale, epoch, c["k"].data_ptr(), c["v"].data_ptr())
+            if c.get("fp8_filled") != state:
+                ops.attn_quantize_kv(c["k"][0], c["v"][0], c["k8"], c["v8t"], 0, rows, k_scale, v_scale, amax=self._fp8_attn_amax[l])
+                c["fp8_filled"] = state
+        arrs = [(c_vp * L)(*[t_.data_ptr() for t_ in ts]) for ts in ([c["k8"] for c in kv_cache], [c["v8t"] for c in kv_cache],
+                                                                     [self._fp8_attn_amax[l] for l in range(L)])]
+        pp = ctypes.POINTER(c_vp)
+        sh = _Fp8Shadow(ctypes.cast(arrs[0], pp), ctypes.cast(arrs[1], pp), rows, k_scale, v_scale, ctypes.cast(arrs[2], pp))
+        return sh, (sh, arrs)
 
     @staticmethod
     def _quantize_fp8(w):
@@ -686,6 +757,11 @@ class CausalWanModel:
                     raise ValueError("KV cache tensors must be [B, kv_size, H, 128] views with dense [H, 128] rows "
                                      "and one common row stride")
 
+        fp8_shadow, fp8_keep = self._fp8_attention_shadow(kv_cache, use_cp)
+        # (the unsharded forward with the shadows as an argument; the phase API of the context-parallel path has no fp8 form)
+        forward = ("rtv_dit_forward",) if fp8_shadow is None else ("rtv_dit_forward_attn_fp8", ctypes.byref(fp8_shadow))
+        fp8_key = (self._fp8_attn[:2] + (kv_cache[0]["k8"].data_ptr(), kv_cache[-1]["v8t"].data_ptr())) if fp8_shadow is not None else None
+
         def ptr_array(tensors):
             arr = (c_vp * L)(*[t_.data_ptr() for t_ in tensors])
             return arr, ctypes.cast(arr, ctypes.POINTER(c_vp))
@@ -728,7 +804,7 @@ class CausalWanModel:
                 # the latent / timestep / output live in static buffers.  The first sighting of a key runs eagerly.
                 graph_key = (F, gh, gw, row0, lo, hi, start_frame, causal_block, ring_lo, ring_size, ring_shift, kv_only, text_rows, fold_k,
                              int(self.gemm_tile_cfg), rs, self._weights_version,
-                             kv_cache[0]["k"].data_ptr(), kv_cache[-1]["v"].data_ptr(), crossattn_cache[0]["k"].data_ptr())
+                             kv_cache[0]["k"].data_ptr(), kv_cache[-1]["v"].data_ptr(), crossattn_cache[0]["k"].data_ptr(), fp8_key)
                 ent = self._graphs.get(graph_key)
                 if isinstance(ent, dict):
                     ent["u"].copy_(u)
@@ -737,7 +813,7 @@ class CausalWanModel:
                     commit()
                     return ent["out"].clone().unsqueeze(0)
             if graph_key is not None and self._graphs.get(graph_key) == "seen":
-                ent = {"u": u.clone(), "t": tt.clone(), "out": out, "keep": (kk_keep, kv_keep, ck_keep, cv_keep)}
+                ent = {"u": u.clone(), "t": tt.clone(), "out": out, "keep": (kk_keep, kv_keep, ck_keep, cv_keep, fp8_keep)}
                 u, tt = ent["u"], ent["t"]
                 g = torch.cuda.CUDAGraph()
                 if not hasattr(self, "_capture_stream"):
@@ -748,7 +824,7 @@ class CausalWanModel:
                 with torch.cuda.graph(g, stream=self._capture_stream):
                     stream = c_vp(torch.cuda.current_stream().cuda_stream)
                     st, wsa = make((0, 0), 0)
-                    _lib.call("rtv_dit_forward", cfg_p, w_p, ctypes.byref(st), *wsa)
+                    _lib.call(forward[0], cfg_p, w_p, ctypes.byref(st), *forward[1:], *wsa)
                 ent["graph"], ent["step"] = g, st
                 self._graphs[graph_key] = ent
                 g.replay()
@@ -757,7 +833,7 @@ class CausalWanModel:
             if graph_key is not None:
                 self._graphs[graph_key] = "seen"
             st, wsa = make((0, 0), 0)
-            _lib.call("rtv_dit_forward", cfg_p, w_p, ctypes.byref(st), *wsa)
+            _lib.call(forward[0], cfg_p, w_p, ctypes.byref(st), *forward[1:], *wsa)
             commit()
         else:
             # Context parallel.  With use_hip_graphs the whole forward - the per-layer C calls AND the collectives, which RCCL lets a

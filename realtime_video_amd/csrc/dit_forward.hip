@@ -15,6 +15,7 @@
 // rank instead of the all-gather's 2*M*d*(world-1)/world: world/2 times less xGMI traffic.
 #include <atomic>
 
+#include "../../include/rtv_hip_attn_fp8.h"
 #include "rtv_common.h"
 #include "rtv_internal.h"
 
@@ -150,6 +151,7 @@ struct Ctx {
   DitBuffers b;
   rtv_stream_t stream;
   int d, H, L, ffn, hd, F, gh, gw, fs, M, r0, rc, tc;
+  const rtv_attn_fp8_shadow* fp8;   // rtv_dit_forward_attn_fp8: self-attention on the e4m3 shadows; null in every other entry point
   int fold_kh, fold_k;   // cross-attention V folded into the output projection: columns per head / in all; 0 = the unfolded path
                          // (then st->ca_v[L + l] is layer l's folded weight, rtv_dit_step.ca_vo_ld)
 };
@@ -160,6 +162,7 @@ static int make_ctx(const rtv_dit_config* cfg, const rtv_dit_weights* w, const r
   c->cfg = cfg;
   c->w = w;
   c->st = st;
+  c->fp8 = nullptr;
   c->stream = stream;
   c->d = cfg->dim;
   c->H = cfg->num_heads;
@@ -348,11 +351,13 @@ static int dit_begin(Ctx& c) {
 }
 
 static int hp_check(Ctx& c, int world);
+static int quantize_written_rows(Ctx& c, int l);
 
 // ---- layer, part 1: LN+modulate -> QKV -> RMSNorm(q,k)+RoPE -> local K/V rows into the cache (or the exchange buffers).
 // `parts` selects what this call does, so that the host can put a collective between the two projections and let it run
 // under the other one (RTV_PROJ_*): LN (the shared input of both), Q (columns [0, d) of the fused QKV weight), KV (columns
 // [d, 3d)).  q_send / kv_send non-null = head-parallel exchange buffers (see below), null = local q + cache rows.
+static std::atomic<void*> g_capture_q{nullptr}, g_capture_o{nullptr};   // rtv_dit_lab_capture_self_attn (test hook, rtv_hip_attn_fp8.h)
 static std::atomic<int> g_direct_v{1};   // rtv_dit_set_direct_v(0): the V cache rows are copied by the RoPE / cache kernel (r04 form; A/B, tests)
 static int dit_layer_proj(Ctx& c, int l, int parts, int world, void* q_send, void* kv_send) {
   const rtv_dit_layer_weights& lw = c.w->layers[l];
@@ -432,9 +437,43 @@ static int dit_layer_proj(Ctx& c, int l, int parts, int world, void* q_send, voi
                                c.cfg->eps, lw.norm_q_w, lw.norm_k_w, c.w->rope_cs, c.F, c.gh, c.gw, st->start_frame, c.r0, gc,
                                (int64_t)c.rc * gc, (int64_t)c.rc * 2 * gc, 0, 0, 0, rope_parts, c.stream);
   }
-  return qk_norm_rope_launch(b.qkv, b.q, st->kv_k[l], st->kv_v[l], st->kv_row_stride, st->cache_row0, c.rc, d, c.H, c.cfg->eps,
-                             lw.norm_q_w, lw.norm_k_w, c.w->rope_cs, c.F, c.gh, c.gw, st->start_frame, c.r0, 0, 0, 0, st->ring_lo,
-                             st->ring_size, st->ring_shift, rope_parts, c.stream);
+  RTV_TRY(qk_norm_rope_launch(b.qkv, b.q, st->kv_k[l], st->kv_v[l], st->kv_row_stride, st->cache_row0, c.rc, d, c.H, c.cfg->eps,
+                              lw.norm_q_w, lw.norm_k_w, c.w->rope_cs, c.F, c.gh, c.gw, st->start_frame, c.r0, 0, 0, 0, st->ring_lo,
+                              st->ring_size, st->ring_shift, rope_parts, c.stream));
+  if (kv && c.fp8) return quantize_written_rows(c, l);   // K and V rows (direct V GEMM included) are in the cache here
+  return 0;
+}
+
+// fp8 attention: the physical cache rows this call has just written (the ring mapping of the write: sink rows as they are, ring
+// rows rotated, at most one wrap) go into the layer's e4m3 shadow.
+static int quantize_written_rows(Ctx& c, int l) {
+  const rtv_dit_step* st = c.st;
+  const rtv_attn_fp8_shadow* sh = c.fp8;
+  if (!sh->k8[l] || !sh->v8t[l]) return set_error(-1, "dit: fp8 attention: a layer has no shadow");
+  int a = st->cache_row0 + c.r0, n = c.rc;
+  const int S = st->ring_lo, R = st->ring_size;
+  int seg[3][2], ns = 0;
+  if (R <= 0) {
+    seg[ns][0] = a, seg[ns++][1] = n;
+  } else {
+    if (a < S) {
+      const int m = n < S - a ? n : S - a;
+      seg[ns][0] = a, seg[ns++][1] = m;
+      a += m, n -= m;
+    }
+    if (n > 0) {
+      const int p0 = S + (a - S + st->ring_shift) % R;
+      const int first = n < S + R - p0 ? n : S + R - p0;
+      seg[ns][0] = p0, seg[ns++][1] = first;
+      if (n - first > R) return set_error(-1, "dit: fp8 attention: a call writes more rows than the ring holds");
+      if (n > first) seg[ns][0] = S, seg[ns++][1] = n - first;
+    }
+  }
+  void* amax = sh->amax ? sh->amax[l] : nullptr;
+  for (int i = 0; i < ns; ++i)
+    RTV_TRY(rtv_attn_quantize_kv(st->kv_k[l], st->kv_v[l], st->kv_row_stride, seg[i][0], seg[i][1], c.H, sh->k8[l], sh->v8t[l],
+                                 sh->cache_rows, sh->k_scale, sh->v_scale, amax, c.stream));
+  return 0;
 }
 
 static int dit_layer_qkv(Ctx& c, int l) { return dit_layer_proj(c, l, RTV_PROJ_LN | RTV_PROJ_Q | RTV_PROJ_KV, 0, nullptr, nullptr); }
@@ -495,7 +534,11 @@ static int dit_layer_rest(Ctx& c, int l) {
   uint16_t* vc = (uint16_t*)st->kv_v[l];
   // self attention (causal_model.py:386-390, :470-476)
   KeyWindow kw = key_window(st);
-  if (rc < c.M) {   // token-sharded call: the query grid is rc / 256 tiles per head - optionally cut along the keys
+  if (c.fp8) {   // (never sharded, never split: rtv_dit_forward_attn_fp8)
+    const rtv_attn_fp8_shadow* sh = c.fp8;
+    RTV_TRY(rtv_attn_fwd_fp8(b.q, sh->k8[l], sh->v8t[l], b.ao, rc, H, sh->cache_rows, kw.row0, kw.n0, kw.row1, kw.n1, d, d, scale,
+                             sh->k_scale, sh->v_scale, st->causal_block, st->causal_block > 0 ? q_offset : 0, stream));
+  } else if (rc < c.M) {   // token-sharded call: the query grid is rc / 256 tiles per head - optionally cut along the keys
     RTV_TRY(sharded_self_attn(c, b.q, kc + (size_t)kw.row0 * rs, vc + (size_t)kw.row0 * rs, b.ao, rc, kw.n0, kw.n1,
                               kw.row1 - kw.row0, H, d, rs, d, q_offset));
   } else {
@@ -504,6 +547,13 @@ static int dit_layer_rest(Ctx& c, int l) {
                              st->causal_block > 0 ? q_offset : 0, RTV_DTYPE_BF16, stream));
   }
   (void)Lkv;
+  if (void* qd = g_capture_q.load(std::memory_order_relaxed)) {   // test hook: this launch's operands, for a repeat outside the forward
+    void* od = g_capture_o.load(std::memory_order_relaxed);
+    const size_t bytes = (size_t)rc * d * sizeof(uint16_t);
+    if (hipMemcpyAsync(qd, b.q, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess ||
+        (od && hipMemcpyAsync(od, b.ao, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess))
+      return set_error(-1, "dit: self-attention capture copy failed");
+  }
   return dit_after_attn(c, l);
 }
 
@@ -668,10 +718,20 @@ extern "C" int rtv_dit_finish(const rtv_dit_config* cfg, const rtv_dit_step* st,
   return rtv_unpatchify(head_rows, st->out, cfg->out_dim, st->F, st->gh, st->gw, stream);
 }
 
-extern "C" int rtv_dit_forward(const rtv_dit_config* cfg, const rtv_dit_weights* w, const rtv_dit_step* st,
-                               void* workspace, size_t workspace_bytes, rtv_stream_t stream) {
+// The unsharded composition; fp8 != null: self-attention on the e4m3 shadows (rtv_dit_forward_attn_fp8).
+static int dit_forward(const rtv_dit_config* cfg, const rtv_dit_weights* w, const rtv_dit_step* st, const rtv_attn_fp8_shadow* fp8,
+                       void* workspace, size_t workspace_bytes, rtv_stream_t stream) {
   Ctx c;
   RTV_TRY(make_ctx(cfg, w, st, workspace, workspace_bytes, stream, &c));
+  if (fp8) {
+    // the phase API takes no shadow, so a sharded call cannot reach the fp8 kernels; what is left to refuse is a sharded or split
+    // step handed to THIS entry point - never a bf16 run in its place
+    if (c.r0 != 0 || c.rc != c.M) return set_error(-1, "dit: fp8 attention does not support sharded calls (row_count < M)");
+    if (st->attn_kv_splits > 1) return set_error(-1, "dit: fp8 attention does not support attn_kv_splits > 1");
+    if (!fp8->k8 || !fp8->v8t || fp8->cache_rows <= 0)
+      return set_error(-1, "dit: fp8 attention needs the k8 / v8t shadow arrays and cache_rows");
+    c.fp8 = fp8;
+  }
   if (c.r0 != 0 || c.rc != c.M)
     return set_error(-1, "dit_forward: sharded row ranges need the phase API (rtv_dit_begin/layer_qkv/layer_rest/head/finish)");
   RTV_TRY(dit_begin(c));
@@ -683,6 +743,24 @@ extern "C" int rtv_dit_forward(const rtv_dit_config* cfg, const rtv_dit_weights*
   }
   RTV_TRY(dit_head(c, c.b.hrow));
   return rtv_unpatchify(c.b.hrow, st->out, cfg->out_dim, c.F, c.gh, c.gw, stream);
+}
+
+extern "C" int rtv_dit_forward(const rtv_dit_config* cfg, const rtv_dit_weights* w, const rtv_dit_step* st,
+                               void* workspace, size_t workspace_bytes, rtv_stream_t stream) {
+  return dit_forward(cfg, w, st, nullptr, workspace, workspace_bytes, stream);
+}
+
+extern "C" int rtv_dit_forward_attn_fp8(const rtv_dit_config* cfg, const rtv_dit_weights* w, const rtv_dit_step* st,
+                                        const rtv_attn_fp8_shadow* shadow, void* workspace, size_t workspace_bytes,
+                                        rtv_stream_t stream) {
+  if (!shadow) return set_error(-1, "dit: fp8 attention needs its shadow (rtv_attn_fp8_shadow)");
+  return dit_forward(cfg, w, st, shadow, workspace, workspace_bytes, stream);
+}
+
+extern "C" int rtv_dit_lab_capture_self_attn(void* q_copy, void* o_copy) {
+  g_capture_q = q_copy;
+  g_capture_o = o_copy;
+  return 0;
 }
 
 extern "C" int rtv_dit_set_direct_v(int on) {

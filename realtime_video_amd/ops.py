@@ -231,6 +231,62 @@ def attn_fwd_split(q, k_cache, v_cache, seg0, seg1=(0, 0), kv_splits=2, out=None
     return out
 
 
+# --------------------------------------------------------------------------------------- fp8 attention (e4m3 shadow of a KV cache)
+def attn_fp8_shadow(cache_rows, H, device):
+    """Zero-filled shadow of a cache [cache_rows][H][128]: (k8 uint8 [cache_rows, H, 128], v8t uint8 [ceil(cache_rows / 64), H, 128, 64])."""
+    return (torch.zeros((cache_rows, H, 128), dtype=torch.uint8, device=device),
+            torch.zeros(((cache_rows + 63) // 64, H, 128, 64), dtype=torch.uint8, device=device))
+
+
+def _check_shadow(k8, v8t, what):
+    _gpu(k8, v8t)
+    if k8.dtype != torch.uint8 or v8t.dtype != torch.uint8 or k8.dim() != 3 or v8t.dim() != 4 or not (k8.is_contiguous() and v8t.is_contiguous()):
+        raise ValueError(f"{what}: k8 / v8t must be dense uint8 tensors [rows, H, 128] / [tiles, H, 128, 64]")
+    rows, H, D = k8.shape
+    if D != 128 or tuple(v8t.shape) != ((rows + 63) // 64, H, 128, 64):
+        raise ValueError(f"{what}: v8t must be [ceil(rows / 64), H, 128, 64] for k8 [rows, H, 128]")
+    return rows, H
+
+
+def attn_quantize_kv(k_cache, v_cache, k8, v8t, row0=0, rows=None, k_scale=1.0, v_scale=1.0, amax=None):
+    """Quantise the physical rows [row0, row0 + rows) of a bf16 KV cache (k_cache / v_cache [rows, H, 128] with one row stride; the
+    two planes of an interleaved arena are fine) into its e4m3 shadow (rtv_attn_quantize_kv).  amax: optional float32 [2] tensor,
+    the running maxima of |k| and |v|."""
+    _gpu(k_cache, v_cache, amax)
+    cache_rows, H = _check_shadow(k8, v8t, "attn_quantize_kv")
+    for t in (k_cache, v_cache):
+        if t.dtype != torch.bfloat16 or t.dim() != 3 or tuple(t.shape) != (cache_rows, H, 128) or t.stride(2) != 1 or t.stride(1) != 128:
+            raise ValueError("attn_quantize_kv: caches must be bf16 [rows, H, 128] with dense [H, 128] inner dims, rows as in k8")
+    if k_cache.stride(0) != v_cache.stride(0):
+        raise ValueError("attn_quantize_kv: K and V need the same row stride")
+    if amax is not None and (amax.dtype != torch.float32 or amax.numel() != 2 or not amax.is_contiguous()):
+        raise ValueError("attn_quantize_kv: amax must be a dense float32 tensor of 2 elements")
+    if rows is None:
+        rows = cache_rows - row0
+    _lib.call("rtv_attn_quantize_kv", _ptr(k_cache), _ptr(v_cache), k_cache.stride(0), int(row0), int(rows), H, _ptr(k8), _ptr(v8t),
+              cache_rows, float(k_scale), float(v_scale), _ptr(amax), _stream())
+    return k8, v8t
+
+
+def attn_fwd_fp8(q, k8, v8t, seg0, seg1=(0, 0), out=None, scale=None, k_scale=1.0, v_scale=1.0, causal_block=0, q_offset=0):
+    """fp8 attention of q [Lq, H, 128] bf16 over the key window seg0 + seg1 (each (first physical row, rows)) of a shadow
+    (rtv_attn_fwd_fp8).  causal_block > 0: the block-causal prefix rule of attn_fwd, one range only."""
+    _gpu(q, out)
+    cache_rows, H = _check_shadow(k8, v8t, "attn_fwd_fp8")
+    if q.dtype != torch.bfloat16 or q.dim() != 3 or q.shape[1] != H or q.shape[2] != 128 or q.stride(2) != 1 or q.stride(1) != 128:
+        raise ValueError("attn_fwd_fp8: q must be bf16 [Lq, H, 128] with dense [H, 128] inner dims, H as in k8")
+    if out is None:
+        out = torch.empty((q.shape[0], H, 128), dtype=q.dtype, device=q.device)
+    elif out.dtype != q.dtype or out.shape != q.shape or out.stride(2) != 1 or out.stride(1) != 128:
+        raise ValueError("attn_fwd_fp8: out must match q")
+    if scale is None:
+        scale = 1.0 / math.sqrt(128)
+    (r0, n0), (r1, n1) = seg0, seg1
+    _lib.call("rtv_attn_fwd_fp8", _ptr(q), _ptr(k8), _ptr(v8t), _ptr(out), q.shape[0], H, cache_rows, int(r0), int(n0), int(r1), int(n1),
+              q.stride(0), out.stride(0), float(scale), float(k_scale), float(v_scale), int(causal_block), int(q_offset), _stream())
+    return out
+
+
 # --------------------------------------------------------------------------------------- GEMM
 _gemm_ws = {}
 
