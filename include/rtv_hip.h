@@ -233,7 +233,9 @@ typedef struct rtv_dit_config {
   float eps;
   int use_fp8;                  /* 1: every nn.Linear runs the e4m3 path (weights below are e4m3, fp8_scales set);
                                    2: the same with one scale per activation row and per weight row (fp8_row_scales set,
-                                   rtv_hip_fp8_rows.h) */
+                                   rtv_hip_fp8_rows.h);
+                                   3: MXFP4 - e2m1 codes, two per byte, with one e8m0 scale per 32 elements (the *_w pointers of the
+                                   Linears address codes, fp8_row_scales their block scales; rtv_hip_mxfp4.h) */
   int max_attn_kv_splits;       /* largest rtv_dit_step.attn_kv_splits this workspace must serve (0 / 1: none - the workspace then
                                    holds no split-attention partials: 97 MB at 14B, M = 4680); a step asking for more fails */
 } rtv_dit_config;
@@ -263,7 +265,9 @@ typedef struct rtv_dit_weights {
                                          pointers of those linears then address e4m3 [N][K] data.  NULL otherwise */
   const void* const* fp8_row_scales;  /* use_fp8 == 2: host array of device float pointers, one per Linear in the order of
                                          fp8_scales; entry i addresses the N per-row (output channel) scales of that weight -
-                                         3d of them for the fused qkv weight.  NULL otherwise */
+                                         3d of them for the fused qkv weight.  use_fp8 == 3: the same table, entry i addressing
+                                         the weight's MXFP4 block scales, [N][K / 32] bytes in the order of rtv_hip_mxfp4.h.
+                                         NULL otherwise */
 } rtv_dit_weights;
 
 typedef struct rtv_dit_step {

@@ -305,6 +305,8 @@ class CausalWanModel:
         if granularity not in ("tensor", "row"):
             raise ValueError(f"enable_fp8: granularity must be 'tensor' or 'row', got {granularity!r}")
         mode = 2 if granularity == "row" else 1
+        if self._cfg.use_fp8 == 3:
+            raise RuntimeError("enable_fp8 after enable_mxfp4(): the bf16 weights are gone - reload the weights first")
         if self._w is None:
             raise RuntimeError("load weights before enable_fp8()")
         if self._cfg.use_fp8:
@@ -337,6 +339,52 @@ class CausalWanModel:
         self._graphs.clear()              # captured graphs replay the bf16 launch sequence on freed bf16 weights
         self._weights_version += 1
         self._ws.clear()                  # the workspace grows by the fp8 activation buffer
+        ops.ensure_gemm_workspace(self.device)
+        return self
+
+    def enable_mxfp4(self):
+        """Opt-in: every nn.Linear that enable_fp8() covers runs on MXFP4 operands instead (include/rtv_hip_mxfp4.h: OCP e2m1 codes,
+        one e8m0 scale per 32 elements of the input width, multiplied by the block-scaled FP4 MFMA of gfx950, which applies the
+        scales itself).  The weights are quantised here, by the kernel that quantises the activations inside the forward
+        (rtv_quantize_mxfp4: one arithmetic); the quantiser is fused into the LayerNorm in front of qkv / cross-q / ffn.0.  The
+        Conv3d patch embedding stays bf16.  Not a reference mode - the reference has no FP4 path; the pin is the restatement of the
+        OCP Microscaling conversion in tests/mxfp4_oracle.py.  With one mantissa bit on both operands expect an error several times
+        that of the fp8 modes: DESIGN.md section 6 has the measured speed and the measured error side by side.
+
+        Call after load_state_dict / init_random_weights; the bf16 copies of the quantised weights are freed.  Mutually exclusive
+        with enable_fp8() in either direction (reload the weights first).  LoRA as under enable_fp8(): load adapters first -
+        set_lora_scale() / unload_lora() then re-merge from the bf16 bases and re-quantise in place - and load_lora() afterwards is
+        refused.  Context parallelism is refused: the sharded phases share the code path but are untested in this mode."""
+        if self._cfg.use_fp8 == 3:
+            return self
+        if self._cfg.use_fp8:
+            raise RuntimeError("enable_mxfp4 after enable_fp8(): the bf16 weights are gone - reload the weights first")
+        if self.context_parallel is not None:
+            raise RuntimeError("enable_mxfp4: context parallelism is not supported in this mode (sharded MXFP4 is untested)")
+        for k in (self.dim, self.ffn_dim, self.text_dim, self.freq_dim):
+            if k % 256:
+                raise ValueError("enable_mxfp4: every Linear input width must be a multiple of 256")
+        if self._w is None:
+            raise RuntimeError("load weights before enable_mxfp4()")
+        keys = list(_FP8_TOP) + [f"L{l}.{name}" for l in range(self.num_layers) for name in _FP8_LAYER]
+        table = (c_vp * len(keys))()
+        self._mxfp4_scales = {}           # _tensors key -> the weight's block scales, [N, K / 32] bytes
+        for i, key in enumerate(keys):
+            codes, scales = ops.quantize_mxfp4(self._tensors[key])
+            self._tensors[key], self._mxfp4_scales[key] = codes, scales
+            table[i] = scales.data_ptr()
+            if i < len(_FP8_TOP):
+                setattr(self._w, key, codes.data_ptr())
+            else:
+                layer, field = key[1:].split(".")
+                setattr(self._layers_arr[int(layer)], field, codes.data_ptr())
+        torch.cuda.synchronize(self.device)   # the bf16 weights the quantiser reads are released above, tensor by tensor
+        self._fp8_row_table = table
+        self._w.fp8_row_scales = ctypes.cast(table, ctypes.POINTER(c_vp))
+        self._cfg.use_fp8 = 3
+        self._graphs.clear()              # captured graphs replay the bf16 launch sequence on freed bf16 weights
+        self._weights_version += 1
+        self._ws.clear()                  # the workspace grows by the activation codes and their block scales
         ops.ensure_gemm_workspace(self.device)
         return self
 
@@ -474,7 +522,7 @@ class CausalWanModel:
         if self._w is None:
             raise RuntimeError("load weights before load_lora()")
         if self._cfg.use_fp8:
-            raise RuntimeError("load_lora after enable_fp8(): the bf16 weights are gone - load adapters first, then enable_fp8()")
+            raise RuntimeError("load_lora after enable_fp8() / enable_mxfp4(): the bf16 weights are gone - load adapters first, then enable the mode")
         dev, bf = self.device, torch.bfloat16
         on_dev = {t: tg._replace(A=tg.A.detach().to(device=dev, dtype=bf).contiguous(),
                                  B=tg.B.detach().to(device=dev, dtype=bf).contiguous()) for t, tg in targets.items()}
@@ -508,7 +556,7 @@ class CausalWanModel:
         """Rebuild the matrices `keys` from their bases with every adapter on them: one rtv_lora_merge per matrix, per q / k / v
         row block of a fused qkv_w.  bf16: into the live weight, in place.  fp8: into a temporary bf16 matrix, re-quantised with
         enable_fp8's routine into the existing e4m3 buffer; its scale is replaced (per-row scales: refreshed in their device tensor) and the
-        graphs, which may hold it by value, go."""
+        graphs, which may hold it by value, go.  MXFP4: the same with enable_mxfp4's quantiser, codes and block scales in place."""
         fp8, cross = bool(self._cfg.use_fp8), False
         for key in sorted(keys):
             base = self._lora_base[key]
@@ -518,7 +566,11 @@ class CausalWanModel:
             for row0, rows in blocks:
                 lora.merge(base[row0:row0 + rows], out[row0:row0 + rows],
                            [(tg.A, tg.B, s * tg.factor) for s, tg in live if (tg.row0, tg.rows) == (row0, rows)])
-            if self._cfg.use_fp8 == 2:
+            if self._cfg.use_fp8 == 3:
+                # the quantiser of enable_mxfp4 (and of the forward), into the existing code and scale tensors: the weight table and
+                # rtv_dit_weights.fp8_row_scales keep pointing at them
+                ops.quantize_mxfp4(out, codes=self._tensors[key], scales=self._mxfp4_scales[key])
+            elif self._cfg.use_fp8 == 2:
                 q, rs = self._quantize_fp8_rows(out)
                 self._tensors[key].copy_(q)
                 self._fp8_row_scales[key].copy_(rs)      # in place: rtv_dit_weights.fp8_row_scales keeps pointing at it
@@ -723,6 +775,8 @@ class CausalWanModel:
         cp = self.context_parallel
         # (a one-rank group takes the plain forward unless the ContextParallel object insists: bench.py --cp-host-probe)
         use_cp = cp is not None and (cp.world > 1 or getattr(cp, "force_single_rank", False))
+        if cp is not None and self._cfg.use_fp8 == 3:
+            raise RuntimeError("MXFP4 Linears do not support context parallelism (enable_mxfp4)")
         # `kv_cache_only` (a per-CALL argument, not in the reference signature: the session passes it for its KV-recompute pass,
         # whose output the reference discards as well, release_server.py:611-632): the forward stops behind the last layer's
         # K / V cache write; the returned tensor is zeros (not while the cross-attention caches are still to be filled: the last

@@ -447,6 +447,86 @@ def gemm_fp8_rows(a_q, a_scales, w_q, w_scales, bias=None, act=ACT_NONE, gate=No
     return out
 
 
+# --------------------------------------------------------------------------------------- MXFP4 path (include/rtv_hip_mxfp4.h)
+MXFP4_BLOCK = 32
+
+
+def mxfp4_scale_bytes(k):
+    """Bytes a row of k elements owns in a scales array (RTV_MXFP4_SCALE_BYTES)."""
+    return ((k // MXFP4_BLOCK) + 7) & ~7
+
+
+def _mxfp4_out(M, d, device, codes, scales):
+    if codes is None:
+        codes = torch.empty((M, d // 2), dtype=torch.uint8, device=device)
+    if scales is None:
+        # (zero-filled: a row whose last K-tile is short owns bytes the kernel never writes)
+        scales = torch.zeros((M, mxfp4_scale_bytes(d)), dtype=torch.uint8, device=device)
+    for t in (codes, scales):
+        if t.dtype != torch.uint8 or t.dim() != 2 or t.shape[0] != M or t.stride(1) != 1:
+            raise TypeError("mxfp4: codes and scales are uint8 matrices of M rows with contiguous rows")
+    if codes.shape[1] != d // 2 or scales.shape[1] != mxfp4_scale_bytes(d):
+        raise ValueError("mxfp4: codes must be [M, d / 2] and scales [M, RTV_MXFP4_SCALE_BYTES(d)]")
+    return codes, scales
+
+
+def quantize_mxfp4(x, codes=None, scales=None):
+    """MXFP4 quantisation of a bf16 matrix [M, d], d % 32 == 0: returns (codes, scales), uint8 [M, d / 2] (two e2m1 codes per
+    byte, element 2j in the low nibble) and uint8 [M, RTV_MXFP4_SCALE_BYTES(d)] (e8m0 block scales in the header's order)."""
+    _gpu(x, codes, scales)
+    if x.dtype != torch.bfloat16 or x.dim() != 2 or x.stride(1) != 1:
+        raise TypeError("quantize_mxfp4 expects a K-contiguous bf16 matrix")
+    M, d = x.shape
+    if d % MXFP4_BLOCK:
+        raise ValueError("quantize_mxfp4: d must be a multiple of 32")
+    codes, scales = _mxfp4_out(M, d, x.device, codes, scales)
+    _lib.call("rtv_quantize_mxfp4", _ptr(x), ctypes.c_int64(x.stride(0)), M, d, _ptr(codes), ctypes.c_int64(codes.stride(0)),
+              _ptr(scales), ctypes.c_int64(scales.stride(0)), _stream())
+    return codes, scales
+
+
+def layernorm_modulate_mxfp4(x, eps=1e-6, shift=None, scale=None, frame_stride=0, rows_per_frame=0, weight=None, bias=None,
+                             row_offset=0):
+    """layernorm_modulate followed by quantize_mxfp4 on its bf16 result, in one kernel and bit for bit: returns (codes, scales)."""
+    _gpu(x, shift, scale, weight, bias)
+    if x.dtype != torch.bfloat16 or x.dim() != 2 or not x.is_contiguous():
+        raise TypeError("layernorm_modulate_mxfp4 expects a contiguous bf16 matrix")
+    M, d = x.shape
+    if d % MXFP4_BLOCK:
+        raise ValueError("layernorm_modulate_mxfp4: d must be a multiple of 32")
+    codes, scales = _mxfp4_out(M, d, x.device, None, None)
+    _lib.call("rtv_layernorm_modulate_mxfp4", _ptr(x), _ptr(codes), ctypes.c_int64(codes.stride(0)), _ptr(scales),
+              ctypes.c_int64(scales.stride(0)), M, d, float(eps), _ptr(shift), _ptr(scale), int(frame_stride), int(rows_per_frame),
+              int(row_offset), _ptr(weight), _ptr(bias), _stream())
+    return codes, scales
+
+
+def gemm_mxfp4(a_codes, a_scales, w_codes, w_scales, bias=None, act=ACT_NONE, gate=None, gate_stride=0, rows_per_frame=0,
+               residual=None, out=None, row_offset=0):
+    """out[M,N] bf16 = epi(sum over 32-blocks of 2^(ea + ew) * (a . w^T)): uint8 code matrices [M, K / 2] and [N, K / 2], uint8
+    block scales [M, K / 32] and [N, K / 32] with dense rows, fp32 accumulation, rtv_gemm's epilogue.  K % 256 == 0."""
+    _gpu(a_codes, w_codes, a_scales, w_scales, bias, gate, residual, out)
+    for t in (a_codes, w_codes, a_scales, w_scales):
+        if t.dtype != torch.uint8 or t.dim() != 2:
+            raise TypeError("gemm_mxfp4 expects uint8 code and scale matrices")
+    M, K = a_codes.shape[0], a_codes.shape[1] * 2
+    N = w_codes.shape[0]
+    if w_codes.shape[1] * 2 != K or a_codes.stride(1) != 1 or w_codes.stride(1) != 1:
+        raise ValueError("gemm_mxfp4 shape / stride mismatch")
+    if K % 256:
+        raise ValueError("gemm_mxfp4: K must be a multiple of 256")
+    for s_, n in ((a_scales, M), (w_scales, N)):
+        if tuple(s_.shape) != (n, K // MXFP4_BLOCK) or not s_.is_contiguous():
+            raise ValueError("gemm_mxfp4 expects contiguous scale matrices [rows, K / 32]")
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.bfloat16, device=a_codes.device)
+    ensure_gemm_workspace(a_codes.device)
+    _lib.call("rtv_gemm_mxfp4", _ptr(a_codes), a_codes.stride(0), _ptr(w_codes), w_codes.stride(0), _ptr(a_scales), _ptr(w_scales),
+              _ptr(out), out.stride(0), M, N, K, _ptr(bias), int(act), _ptr(gate), int(gate_stride), int(rows_per_frame),
+              int(row_offset), _ptr(residual), residual.stride(0) if residual is not None else 0, _stream())
+    return out
+
+
 # --------------------------------------------------------------------------------------- norms
 def layernorm_modulate(x, eps=1e-6, shift=None, scale=None, frame_stride=0, rows_per_frame=0,
                        weight=None, bias=None, out=None, row_offset=0):
