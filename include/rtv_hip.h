@@ -235,7 +235,9 @@ typedef struct rtv_dit_config {
                                    2: the same with one scale per activation row and per weight row (fp8_row_scales set,
                                    rtv_hip_fp8_rows.h);
                                    3: MXFP4 - e2m1 codes, two per byte, with one e8m0 scale per 32 elements (the *_w pointers of the
-                                   Linears address codes, fp8_row_scales their block scales; rtv_hip_mxfp4.h) */
+                                   Linears address codes, fp8_row_scales their block scales; rtv_hip_mxfp4.h);
+                                   4: MXFP6 - e2m3 codes, 24 bytes per 32 elements, with one e8m0 scale per 32 elements (pointers as
+                                   for 3; rtv_hip_mxfp6.h) */
   int max_attn_kv_splits;       /* largest rtv_dit_step.attn_kv_splits this workspace must serve (0 / 1: none - the workspace then
                                    holds no split-attention partials: 97 MB at 14B, M = 4680); a step asking for more fails */
 } rtv_dit_config;
@@ -266,7 +268,8 @@ typedef struct rtv_dit_weights {
   const void* const* fp8_row_scales;  /* use_fp8 == 2: host array of device float pointers, one per Linear in the order of
                                          fp8_scales; entry i addresses the N per-row (output channel) scales of that weight -
                                          3d of them for the fused qkv weight.  use_fp8 == 3: the same table, entry i addressing
-                                         the weight's MXFP4 block scales, [N][K / 32] bytes in the order of rtv_hip_mxfp4.h.
+                                         the weight's MXFP4 block scales, [N][K / 32] bytes in the order of rtv_hip_mxfp4.h; use_fp8 == 4: its
+                                         MXFP6 block scales, [N][K / 32] bytes in the order of rtv_hip_mxfp6.h.
                                          NULL otherwise */
 } rtv_dit_weights;
 

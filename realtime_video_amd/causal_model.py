@@ -307,6 +307,8 @@ class CausalWanModel:
         mode = 2 if granularity == "row" else 1
         if self._cfg.use_fp8 == 3:
             raise RuntimeError("enable_fp8 after enable_mxfp4(): the bf16 weights are gone - reload the weights first")
+        if self._cfg.use_fp8 == 4:
+            raise RuntimeError("enable_fp8 after enable_mxfp6(): the bf16 weights are gone - reload the weights first")
         if self._w is None:
             raise RuntimeError("load weights before enable_fp8()")
         if self._cfg.use_fp8:
@@ -358,7 +360,7 @@ class CausalWanModel:
         if self._cfg.use_fp8 == 3:
             return self
         if self._cfg.use_fp8:
-            raise RuntimeError("enable_mxfp4 after enable_fp8(): the bf16 weights are gone - reload the weights first")
+            raise RuntimeError("enable_mxfp4 after enable_fp8() / enable_mxfp6(): the bf16 weights are gone - reload the weights first")
         if self.context_parallel is not None:
             raise RuntimeError("enable_mxfp4: context parallelism is not supported in this mode (sharded MXFP4 is untested)")
         for k in (self.dim, self.ffn_dim, self.text_dim, self.freq_dim):
@@ -382,6 +384,54 @@ class CausalWanModel:
         self._fp8_row_table = table
         self._w.fp8_row_scales = ctypes.cast(table, ctypes.POINTER(c_vp))
         self._cfg.use_fp8 = 3
+        self._graphs.clear()              # captured graphs replay the bf16 launch sequence on freed bf16 weights
+        self._weights_version += 1
+        self._ws.clear()                  # the workspace grows by the activation codes and their block scales
+        ops.ensure_gemm_workspace(self.device)
+        return self
+
+    def enable_mxfp6(self):
+        """Opt-in: every nn.Linear that enable_fp8() / enable_mxfp4() cover runs on MXFP6 operands instead (include/rtv_hip_mxfp6.h:
+        OCP e2m3 codes, one e8m0 scale per 32 elements of the input width, multiplied by the block-scaled MFMA of gfx950 in its FP6
+        form, which applies the scales itself and issues at the FP4 rate).  Three mantissa bits, as e4m3 has, and a scale per 32
+        elements: the error class of the fp8 modes at three quarters of their operand bytes.  The weights are quantised here, by
+        the kernel that quantises the activations inside the forward (rtv_quantize_mxfp6: one arithmetic); the quantiser is fused
+        into the LayerNorm in front of qkv / cross-q / ffn.0.  The Conv3d patch embedding stays bf16.  Not a reference mode - the
+        reference has no FP6 path; the pin is the restatement of the OCP Microscaling conversion in tests/mxfp6_oracle.py.
+        DESIGN.md section 6 has what was measured.
+
+        Call after load_state_dict / init_random_weights; the bf16 copies of the quantised weights are freed.  Mutually exclusive
+        with enable_fp8() and enable_mxfp4() in either direction (reload the weights first).  LoRA as under enable_mxfp4(): load
+        adapters first - set_lora_scale() / unload_lora() then re-merge from the bf16 bases and re-quantise in place - and
+        load_lora() afterwards is refused.  Context parallelism is refused: the sharded phases share the code path but are untested
+        in this mode."""
+        if self._cfg.use_fp8 == 4:
+            return self
+        if self._cfg.use_fp8:
+            raise RuntimeError("enable_mxfp6 after enable_fp8() / enable_mxfp4(): the bf16 weights are gone - reload the weights first")
+        if self.context_parallel is not None:
+            raise RuntimeError("enable_mxfp6: context parallelism is not supported in this mode (sharded MXFP6 is untested)")
+        for k in (self.dim, self.ffn_dim, self.text_dim, self.freq_dim):
+            if k % 128:
+                raise ValueError("enable_mxfp6: every Linear input width must be a multiple of 128")
+        if self._w is None:
+            raise RuntimeError("load weights before enable_mxfp6()")
+        keys = list(_FP8_TOP) + [f"L{l}.{name}" for l in range(self.num_layers) for name in _FP8_LAYER]
+        table = (c_vp * len(keys))()
+        self._mxfp6_scales = {}           # _tensors key -> the weight's block scales, [N, K / 32] bytes
+        for i, key in enumerate(keys):
+            codes, scales = ops.quantize_mxfp6(self._tensors[key])
+            self._tensors[key], self._mxfp6_scales[key] = codes, scales
+            table[i] = scales.data_ptr()
+            if i < len(_FP8_TOP):
+                setattr(self._w, key, codes.data_ptr())
+            else:
+                layer, field = key[1:].split(".")
+                setattr(self._layers_arr[int(layer)], field, codes.data_ptr())
+        torch.cuda.synchronize(self.device)   # the bf16 weights the quantiser reads are released above, tensor by tensor
+        self._fp8_row_table = table
+        self._w.fp8_row_scales = ctypes.cast(table, ctypes.POINTER(c_vp))
+        self._cfg.use_fp8 = 4
         self._graphs.clear()              # captured graphs replay the bf16 launch sequence on freed bf16 weights
         self._weights_version += 1
         self._ws.clear()                  # the workspace grows by the activation codes and their block scales
@@ -522,7 +572,7 @@ class CausalWanModel:
         if self._w is None:
             raise RuntimeError("load weights before load_lora()")
         if self._cfg.use_fp8:
-            raise RuntimeError("load_lora after enable_fp8() / enable_mxfp4(): the bf16 weights are gone - load adapters first, then enable the mode")
+            raise RuntimeError("load_lora after enable_fp8() / enable_mxfp4() / enable_mxfp6(): the bf16 weights are gone - load adapters first, then enable the mode")
         dev, bf = self.device, torch.bfloat16
         on_dev = {t: tg._replace(A=tg.A.detach().to(device=dev, dtype=bf).contiguous(),
                                  B=tg.B.detach().to(device=dev, dtype=bf).contiguous()) for t, tg in targets.items()}
@@ -556,7 +606,7 @@ class CausalWanModel:
         """Rebuild the matrices `keys` from their bases with every adapter on them: one rtv_lora_merge per matrix, per q / k / v
         row block of a fused qkv_w.  bf16: into the live weight, in place.  fp8: into a temporary bf16 matrix, re-quantised with
         enable_fp8's routine into the existing e4m3 buffer; its scale is replaced (per-row scales: refreshed in their device tensor) and the
-        graphs, which may hold it by value, go.  MXFP4: the same with enable_mxfp4's quantiser, codes and block scales in place."""
+        graphs, which may hold it by value, go.  MXFP4 / MXFP6: the same with that mode's quantiser, codes and block scales in place."""
         fp8, cross = bool(self._cfg.use_fp8), False
         for key in sorted(keys):
             base = self._lora_base[key]
@@ -570,6 +620,8 @@ class CausalWanModel:
                 # the quantiser of enable_mxfp4 (and of the forward), into the existing code and scale tensors: the weight table and
                 # rtv_dit_weights.fp8_row_scales keep pointing at them
                 ops.quantize_mxfp4(out, codes=self._tensors[key], scales=self._mxfp4_scales[key])
+            elif self._cfg.use_fp8 == 4:
+                ops.quantize_mxfp6(out, codes=self._tensors[key], scales=self._mxfp6_scales[key])
             elif self._cfg.use_fp8 == 2:
                 q, rs = self._quantize_fp8_rows(out)
                 self._tensors[key].copy_(q)
@@ -777,6 +829,8 @@ class CausalWanModel:
         use_cp = cp is not None and (cp.world > 1 or getattr(cp, "force_single_rank", False))
         if cp is not None and self._cfg.use_fp8 == 3:
             raise RuntimeError("MXFP4 Linears do not support context parallelism (enable_mxfp4)")
+        if cp is not None and self._cfg.use_fp8 == 4:
+            raise RuntimeError("MXFP6 Linears do not support context parallelism (enable_mxfp6)")
         # `kv_cache_only` (a per-CALL argument, not in the reference signature: the session passes it for its KV-recompute pass,
         # whose output the reference discards as well, release_server.py:611-632): the forward stops behind the last layer's
         # K / V cache write; the returned tensor is zeros (not while the cross-attention caches are still to be filled: the last

@@ -17,6 +17,7 @@
 
 #include "../../include/rtv_hip_attn_fp8.h"
 #include "../../include/rtv_hip_mxfp4.h"
+#include "../../include/rtv_hip_mxfp6.h"
 #include "rtv_common.h"
 #include "rtv_internal.h"
 
@@ -96,7 +97,8 @@ struct DitBuffers {
   uint16_t *x, *xn, *qkv, *q, *ao, *h, *prow, *hrow;
   uint16_t *sinus, *te1, *e, *se, *e0, *emod, *ehead, *ctx1, *ctx, *ktmp;
   uint8_t* q8;      // fp8 path: the quantised activation of the linear being computed (use_fp8 == 3, MXFP4: its e2m1 codes in the
-                    // first rows * K / 2 bytes and its block scales behind them - 17 / 32 of the fp8 size)
+                    // first rows * K / 2 bytes and its block scales behind them - 17 / 32 of the fp8 size; use_fp8 == 4, MXFP6: e2m3
+                    // codes in the first rows * 3 K / 4 bytes, block scales behind them - 25 / 32)
   float* frow;      // fp8 path with per-row scales (use_fp8 == 2): the row scales of the activation in q8
   float* fscale;    // fp8 path: its per-tensor scale (device), followed by the 4-byte absmax scratch
   float* attn_part; // KV-split self-attention of a sharded call: fp32 partial outputs + (m, l) of splits x heads x rows <= H x M
@@ -266,6 +268,8 @@ static bool is_fp8(const Ctx& c, int sidx) { return c.cfg->use_fp8 && sidx >= 0;
 // its own output).  The weight's scales are asked for here, in front of the first launch of the Linear.
 // MXFP4 (use_fp8 == 3, rtv_hip_mxfp4.h): the block scales of an [M][K] activation in q8, behind its codes
 static uint8_t* mx_scales(const Ctx& c, int M, int K) { return c.b.q8 + (size_t)M * K / 2; }
+// MXFP6 (use_fp8 == 4, rtv_hip_mxfp6.h): the same with 3 K / 4 bytes of codes per row
+static uint8_t* mx6_scales(const Ctx& c, int M, int K) { return c.b.q8 + (size_t)M * RTV_MXFP6_CODE_BYTES(K); }
 
 static int quantize_input(Ctx& c, int sidx, const void* a, int M, int K, rtv_stream_t s) {
   if (!is_fp8(c, sidx)) return 0;
@@ -273,6 +277,10 @@ static int quantize_input(Ctx& c, int sidx, const void* a, int M, int K, rtv_str
     // per 32-element block: like the row scales, the decisions of a row need that row alone
     if (!c.w->fp8_row_scales || !c.w->fp8_row_scales[sidx]) return set_error(-1, "dit: use_fp8 == 3 needs rtv_dit_weights.fp8_row_scales");
     return a ? rtv_quantize_mxfp4(a, K, M, K, c.b.q8, K / 2, mx_scales(c, M, K), K / 32, s) : 0;
+  }
+  if (c.cfg->use_fp8 == 4) {
+    if (!c.w->fp8_row_scales || !c.w->fp8_row_scales[sidx]) return set_error(-1, "dit: use_fp8 == 4 needs rtv_dit_weights.fp8_row_scales");
+    return a ? rtv_quantize_mxfp6(a, K, M, K, c.b.q8, RTV_MXFP6_CODE_BYTES(K), mx6_scales(c, M, K), K / 32, s) : 0;
   }
   if (c.cfg->use_fp8 == 2) {
     // per-row scales: the quantisation of a row needs that row alone, so a token shard takes the unsharded forward's decisions
@@ -291,13 +299,21 @@ static int project(Ctx& c, int sidx, const void* a, int K, const void* w, int w_
                    int act, const void* gate, int gate_stride, int rpf, int row_off, const void* res, int cfg, rtv_stream_t s) {
   const bool fp8 = is_fp8(c, sidx);
   const bool mx = fp8 && c.cfg->use_fp8 == 3;
-  const void* wp = (const char*)w + (mx ? (size_t)w_row0 * K / 2 : (size_t)w_row0 * K * (fp8 ? 1 : 2));   // fp8 weights are bytes, MXFP4 nibbles
+  const bool mx6 = fp8 && c.cfg->use_fp8 == 4;
+  // fp8 weights are bytes, MXFP4 nibbles, MXFP6 three bytes per four elements
+  const void* wp = (const char*)w + (mx    ? (size_t)w_row0 * K / 2
+                                     : mx6 ? (size_t)w_row0 * RTV_MXFP6_CODE_BYTES(K)
+                                           : (size_t)w_row0 * K * (fp8 ? 1 : 2));
   const void* bp = bias ? (const uint16_t*)bias + w_row0 : nullptr;
   const int ldr = res ? ldc : 0;
   if (!fp8) return rtv_gemm(a, K, wp, K, out, ldc, M, N, K, bp, act, gate, gate_stride, rpf, row_off, res, ldr, RTV_DTYPE_BF16, cfg, s);
   if (mx)
     return rtv_gemm_mxfp4(c.b.q8, K / 2, wp, K / 2, mx_scales(c, M, K), (const uint8_t*)c.w->fp8_row_scales[sidx] + (size_t)w_row0 * (K / 32), out,
                           ldc, M, N, K, bp, act, gate, gate_stride, rpf, row_off, res, ldr, s);
+  if (mx6)
+    return rtv_gemm_mxfp6(c.b.q8, RTV_MXFP6_CODE_BYTES(K), wp, RTV_MXFP6_CODE_BYTES(K), mx6_scales(c, M, K),
+                          (const uint8_t*)c.w->fp8_row_scales[sidx] + (size_t)w_row0 * (K / 32), out, ldc, M, N, K, bp, act, gate, gate_stride,
+                          rpf, row_off, res, ldr, s);
   if (c.cfg->use_fp8 == 2)
     return rtv_gemm_fp8_rows(c.b.q8, K, wp, K, c.b.frow, (const float*)c.w->fp8_row_scales[sidx] + w_row0, out, ldc, M, N, K, bp, act, gate,
                              gate_stride, rpf, row_off, res, ldr, s);
@@ -321,6 +337,11 @@ static int ln_input(Ctx& c, const void* shift, const void* scale, int frame_stri
     *a = nullptr;
     return rtv_layernorm_modulate_mxfp4(b.x, b.q8, c.d / 2, mx_scales(c, c.rc, c.d), c.d / 32, c.rc, c.d, c.cfg->eps, shift, scale, frame_stride,
                                         rpf, r0, weight, bias, c.stream);
+  }
+  if (c.cfg->use_fp8 == 4) {
+    *a = nullptr;
+    return rtv_layernorm_modulate_mxfp6(b.x, b.q8, RTV_MXFP6_CODE_BYTES(c.d), mx6_scales(c, c.rc, c.d), c.d / 32, c.rc, c.d, c.cfg->eps, shift,
+                                        scale, frame_stride, rpf, r0, weight, bias, c.stream);
   }
   if (c.cfg->use_fp8 == 2) {
     *a = nullptr;
@@ -432,7 +453,7 @@ static int dit_layer_proj(Ctx& c, int l, int parts, int world, void* q_send, voi
       }
     }
     const int sidx = S_LAYER0 + S_PER_LAYER * l + S_QKV;
-    const void* a = c.cfg->use_fp8 >= 2 ? nullptr : b.xn;   // what the LN phase left: b.xn, or codes and scales in q8 / frow (modes 2, 3)
+    const void* a = c.cfg->use_fp8 >= 2 ? nullptr : b.xn;   // what the LN phase left: b.xn, or codes and scales in q8 / frow (modes 2, 3, 4)
     RTV_TRY(quantize_input(c, sidx, a, c.rc, d, c.stream));
     auto proj = [&](int w_row0, int N, void* out, int ldc) {
       return project(c, sidx, a, d, lw.qkv_w, w_row0, lw.qkv_b, out, ldc, c.rc, N, 0, nullptr, 0, 0, 0, nullptr, c.tc, c.stream);

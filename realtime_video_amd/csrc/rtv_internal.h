@@ -43,7 +43,7 @@ struct ProfScope {
 enum DispatchKernel {
   DK_GEMM_128x128 = 0, DK_GEMM_OTHER_CFG, DK_GEMM8_256x256, DK_GEMM8M_128x256, DK_GEMM5_160x256, DK_GEMM_FP8_256x256,
   DK_ATTN_W4, DK_ATTN_FOUR_PHASE, DK_ATTN_LOCKSTEP_256ROW, DK_ATTN_LOCKSTEP_128ROW, DK_ATTN_SPLIT_COMBINE,
-  DK_CONV_HALO4P, DK_CONV_HALO4, DK_CONV_HALO, DK_CONV_IGEMM, DK_ATTN_PROBS, DK_GEMM_MXFP4_256x256, DK_COUNT
+  DK_CONV_HALO4P, DK_CONV_HALO4, DK_CONV_HALO, DK_CONV_IGEMM, DK_ATTN_PROBS, DK_GEMM_MXFP4_256x256, DK_GEMM_MXFP6_256x256, DK_COUNT
 };
 void note_kernel(int id);
 

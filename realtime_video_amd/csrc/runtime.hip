@@ -51,7 +51,7 @@ static const char* const g_dispatch_names[DK_COUNT] = {
     "attn_fwd_w4_kernel<one wave per SIMD>", "attn_fwd_pp_kernel<four-phase>", "attn_fwd_kernel<lockstep, 256 rows>",
     "attn_fwd_kernel<lockstep, 128 rows>", "attn_combine_kernel<kv split>",
     "conv_halo4p_kernel<persistent>", "conv_halo4_kernel", "conv_halo_kernel", "conv_igemm_kernel",
-    "attn_probs_kernel<short window, probabilities>", "gemm_mxfp4_kernel<256x256>"};
+    "attn_probs_kernel<short window, probabilities>", "gemm_mxfp4_kernel<256x256>", "gemm_mxfp6_kernel<256x256>"};
 void note_kernel(int id) {
   if (id >= 0 && id < DK_COUNT) g_dispatch[id].fetch_add(1, std::memory_order_relaxed);
 }

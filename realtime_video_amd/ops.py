@@ -527,6 +527,94 @@ def gemm_mxfp4(a_codes, a_scales, w_codes, w_scales, bias=None, act=ACT_NONE, ga
     return out
 
 
+# --------------------------------------------------------------------------------------- MXFP6 path (include/rtv_hip_mxfp6.h)
+MXFP6_BLOCK = 32
+
+
+def mxfp6_scale_bytes(k):
+    """Bytes a row of k elements owns in a scales array (RTV_MXFP6_SCALE_BYTES)."""
+    return ((k // MXFP6_BLOCK) + 3) & ~3
+
+
+def mxfp6_code_bytes(k):
+    """Bytes a row of k elements owns in a codes array (RTV_MXFP6_CODE_BYTES)."""
+    return k // 4 * 3
+
+
+def _mxfp6_out(M, d, device, codes, scales):
+    if codes is None:
+        codes = torch.empty((M, mxfp6_code_bytes(d)), dtype=torch.uint8, device=device)
+    if scales is None:
+        # (zero-filled: a row whose last K-tile is short owns bytes the kernel never writes)
+        scales = torch.zeros((M, mxfp6_scale_bytes(d)), dtype=torch.uint8, device=device)
+    for t in (codes, scales):
+        if t.dtype != torch.uint8 or t.dim() != 2 or t.shape[0] != M or t.stride(1) != 1:
+            raise TypeError("mxfp6: codes and scales are uint8 matrices of M rows with contiguous rows")
+    if codes.shape[1] != mxfp6_code_bytes(d) or scales.shape[1] != mxfp6_scale_bytes(d):
+        raise ValueError("mxfp6: codes must be [M, 3 d / 4] and scales [M, RTV_MXFP6_SCALE_BYTES(d)]")
+    return codes, scales
+
+
+def quantize_mxfp6(x, codes=None, scales=None):
+    """MXFP6 quantisation of a bf16 matrix [M, d], d % 32 == 0: returns (codes, scales), uint8 [M, 3 d / 4] (e2m3 codes, a block of
+    32 in 24 bytes, element j at bits [6 j, 6 j + 6)) and uint8 [M, RTV_MXFP6_SCALE_BYTES(d)] (e8m0 block scales in the header's
+    order)."""
+    _gpu(x, codes, scales)
+    if x.dtype != torch.bfloat16 or x.dim() != 2 or x.stride(1) != 1:
+        raise TypeError("quantize_mxfp6 expects a K-contiguous bf16 matrix")
+    M, d = x.shape
+    if d % MXFP6_BLOCK:
+        raise ValueError("quantize_mxfp6: d must be a multiple of 32")
+    codes, scales = _mxfp6_out(M, d, x.device, codes, scales)
+    _lib.call("rtv_quantize_mxfp6", _ptr(x), ctypes.c_int64(x.stride(0)), M, d, _ptr(codes), ctypes.c_int64(codes.stride(0)),
+              _ptr(scales), ctypes.c_int64(scales.stride(0)), _stream())
+    return codes, scales
+
+
+def layernorm_modulate_mxfp6(x, eps=1e-6, shift=None, scale=None, frame_stride=0, rows_per_frame=0, weight=None, bias=None,
+                             row_offset=0):
+    """layernorm_modulate followed by quantize_mxfp6 on its bf16 result, in one kernel and bit for bit: returns (codes, scales)."""
+    _gpu(x, shift, scale, weight, bias)
+    if x.dtype != torch.bfloat16 or x.dim() != 2 or not x.is_contiguous():
+        raise TypeError("layernorm_modulate_mxfp6 expects a contiguous bf16 matrix")
+    M, d = x.shape
+    if d % MXFP6_BLOCK:
+        raise ValueError("layernorm_modulate_mxfp6: d must be a multiple of 32")
+    codes, scales = _mxfp6_out(M, d, x.device, None, None)
+    _lib.call("rtv_layernorm_modulate_mxfp6", _ptr(x), _ptr(codes), ctypes.c_int64(codes.stride(0)), _ptr(scales),
+              ctypes.c_int64(scales.stride(0)), M, d, float(eps), _ptr(shift), _ptr(scale), int(frame_stride), int(rows_per_frame),
+              int(row_offset), _ptr(weight), _ptr(bias), _stream())
+    return codes, scales
+
+
+def gemm_mxfp6(a_codes, a_scales, w_codes, w_scales, bias=None, act=ACT_NONE, gate=None, gate_stride=0, rows_per_frame=0,
+               residual=None, out=None, row_offset=0):
+    """out[M,N] bf16 = epi(sum over 32-blocks of 2^(ea + ew) * (a . w^T)): uint8 code matrices [M, 3 K / 4] and [N, 3 K / 4], uint8
+    block scales [M, K / 32] and [N, K / 32] with dense rows, fp32 accumulation, rtv_gemm's epilogue.  K % 128 == 0."""
+    _gpu(a_codes, w_codes, a_scales, w_scales, bias, gate, residual, out)
+    for t in (a_codes, w_codes, a_scales, w_scales):
+        if t.dtype != torch.uint8 or t.dim() != 2:
+            raise TypeError("gemm_mxfp6 expects uint8 code and scale matrices")
+    if a_codes.shape[1] % 3:
+        raise ValueError("gemm_mxfp6: a row of codes is 3 K / 4 bytes")
+    M, K = a_codes.shape[0], a_codes.shape[1] // 3 * 4
+    N = w_codes.shape[0]
+    if w_codes.shape[1] != a_codes.shape[1] or a_codes.stride(1) != 1 or w_codes.stride(1) != 1:
+        raise ValueError("gemm_mxfp6 shape / stride mismatch")
+    if K % 128:
+        raise ValueError("gemm_mxfp6: K must be a multiple of 128")
+    for s_, n in ((a_scales, M), (w_scales, N)):
+        if tuple(s_.shape) != (n, K // MXFP6_BLOCK) or not s_.is_contiguous():
+            raise ValueError("gemm_mxfp6 expects contiguous scale matrices [rows, K / 32]")
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.bfloat16, device=a_codes.device)
+    ensure_gemm_workspace(a_codes.device)
+    _lib.call("rtv_gemm_mxfp6", _ptr(a_codes), a_codes.stride(0), _ptr(w_codes), w_codes.stride(0), _ptr(a_scales), _ptr(w_scales),
+              _ptr(out), out.stride(0), M, N, K, _ptr(bias), int(act), _ptr(gate), int(gate_stride), int(rows_per_frame),
+              int(row_offset), _ptr(residual), residual.stride(0) if residual is not None else 0, _stream())
+    return out
+
+
 # --------------------------------------------------------------------------------------- norms
 def layernorm_modulate(x, eps=1e-6, shift=None, scale=None, frame_stride=0, rows_per_frame=0,
                        weight=None, bias=None, out=None, row_offset=0):
