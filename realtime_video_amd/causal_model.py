@@ -37,6 +37,11 @@ _TOP_FIELDS = tuple(n for n, t in _Weights._fields_ if t is c_vp)      # the dev
 # nn.Linear weights in the order of rtv_dit_weights.fp8_scales (include/rtv_hip.h)
 _FP8_TOP = ("text0_w", "text2_w", "time0_w", "time2_w", "tproj_w", "head_w")
 _FP8_LAYER = ("qkv_w", "o_w", "cq_w", "ck_w", "cv_w", "co_w", "ffn0_w", "ffn2_w")
+# rtv_dit_config.use_fp8: how the Linears of _FP8_TOP / _FP8_LAYER run
+_BF16, _FP8_TENSOR, _FP8_ROWS, _MXFP4, _MXFP6 = range(5)
+# the block-scaled modes: (name, the Linear input widths' multiple, weight and LoRA quantiser, the enable_* calls it excludes)
+_MX_MODES = {_MXFP4: ("mxfp4", 256, ops.quantize_mxfp4, "enable_fp8() / enable_mxfp6()"),
+             _MXFP6: ("mxfp6", 128, ops.quantize_mxfp6, "enable_fp8() / enable_mxfp4()")}
 
 PROJ_LN, PROJ_Q, PROJ_KV = 1, 2, 4
 
@@ -279,7 +284,7 @@ class CausalWanModel:
         w.layers = ctypes.cast(layers, ctypes.POINTER(_LayerW))
         self._layers_arr = layers
         self._tensors, self._w = t, w
-        self._cfg.use_fp8 = 0           # (a reload replaces quantised weights; enable_fp8() again to re-quantise)
+        self._cfg.use_fp8 = _BF16           # (a reload replaces quantised weights; enable_fp8() again to re-quantise)
         if self._lora or self._lora_base:
             self._lora, self._lora_base = {}, {}      # adapters belong to the weights they were merged into
             self.lora_version += 1
@@ -304,11 +309,10 @@ class CausalWanModel:
         published source: tests/fp8_rows_oracle.py).  The granularity cannot be changed once fp8 is on: the bf16 weights are gone."""
         if granularity not in ("tensor", "row"):
             raise ValueError(f"enable_fp8: granularity must be 'tensor' or 'row', got {granularity!r}")
-        mode = 2 if granularity == "row" else 1
-        if self._cfg.use_fp8 == 3:
-            raise RuntimeError("enable_fp8 after enable_mxfp4(): the bf16 weights are gone - reload the weights first")
-        if self._cfg.use_fp8 == 4:
-            raise RuntimeError("enable_fp8 after enable_mxfp6(): the bf16 weights are gone - reload the weights first")
+        mode = _FP8_ROWS if granularity == "row" else _FP8_TENSOR
+        if self._cfg.use_fp8 in _MX_MODES:
+            raise RuntimeError(f"enable_fp8 after enable_{_MX_MODES[self._cfg.use_fp8][0]}(): the bf16 weights are gone - "
+                               "reload the weights first")
         if self._w is None:
             raise RuntimeError("load weights before enable_fp8()")
         if self._cfg.use_fp8:
@@ -319,7 +323,7 @@ class CausalWanModel:
         for k in (self.dim, self.ffn_dim, self.text_dim, self.freq_dim):
             if k % 128:
                 raise ValueError("enable_fp8: every Linear input width must be a multiple of 128")
-        if mode == 2:
+        if mode == _FP8_ROWS:
             return self._enable_fp8_rows()
         scales = (ctypes.c_float * (len(_FP8_TOP) + len(_FP8_LAYER) * self.num_layers))()
 
@@ -337,7 +341,7 @@ class CausalWanModel:
                 setattr(self._layers_arr[l], name, q.data_ptr())
         self._fp8_scales = scales
         self._w.fp8_scales = ctypes.cast(scales, ctypes.POINTER(ctypes.c_float))
-        self._cfg.use_fp8 = 1
+        self._cfg.use_fp8 = _FP8_TENSOR
         self._graphs.clear()              # captured graphs replay the bf16 launch sequence on freed bf16 weights
         self._weights_version += 1
         self._ws.clear()                  # the workspace grows by the fp8 activation buffer
@@ -357,38 +361,7 @@ class CausalWanModel:
         with enable_fp8() in either direction (reload the weights first).  LoRA as under enable_fp8(): load adapters first -
         set_lora_scale() / unload_lora() then re-merge from the bf16 bases and re-quantise in place - and load_lora() afterwards is
         refused.  Context parallelism is refused: the sharded phases share the code path but are untested in this mode."""
-        if self._cfg.use_fp8 == 3:
-            return self
-        if self._cfg.use_fp8:
-            raise RuntimeError("enable_mxfp4 after enable_fp8() / enable_mxfp6(): the bf16 weights are gone - reload the weights first")
-        if self.context_parallel is not None:
-            raise RuntimeError("enable_mxfp4: context parallelism is not supported in this mode (sharded MXFP4 is untested)")
-        for k in (self.dim, self.ffn_dim, self.text_dim, self.freq_dim):
-            if k % 256:
-                raise ValueError("enable_mxfp4: every Linear input width must be a multiple of 256")
-        if self._w is None:
-            raise RuntimeError("load weights before enable_mxfp4()")
-        keys = list(_FP8_TOP) + [f"L{l}.{name}" for l in range(self.num_layers) for name in _FP8_LAYER]
-        table = (c_vp * len(keys))()
-        self._mxfp4_scales = {}           # _tensors key -> the weight's block scales, [N, K / 32] bytes
-        for i, key in enumerate(keys):
-            codes, scales = ops.quantize_mxfp4(self._tensors[key])
-            self._tensors[key], self._mxfp4_scales[key] = codes, scales
-            table[i] = scales.data_ptr()
-            if i < len(_FP8_TOP):
-                setattr(self._w, key, codes.data_ptr())
-            else:
-                layer, field = key[1:].split(".")
-                setattr(self._layers_arr[int(layer)], field, codes.data_ptr())
-        torch.cuda.synchronize(self.device)   # the bf16 weights the quantiser reads are released above, tensor by tensor
-        self._fp8_row_table = table
-        self._w.fp8_row_scales = ctypes.cast(table, ctypes.POINTER(c_vp))
-        self._cfg.use_fp8 = 3
-        self._graphs.clear()              # captured graphs replay the bf16 launch sequence on freed bf16 weights
-        self._weights_version += 1
-        self._ws.clear()                  # the workspace grows by the activation codes and their block scales
-        ops.ensure_gemm_workspace(self.device)
-        return self
+        return self._enable_mx(_MXFP4)
 
     def enable_mxfp6(self):
         """Opt-in: every nn.Linear that enable_fp8() / enable_mxfp4() cover runs on MXFP6 operands instead (include/rtv_hip_mxfp6.h:
@@ -405,23 +378,27 @@ class CausalWanModel:
         adapters first - set_lora_scale() / unload_lora() then re-merge from the bf16 bases and re-quantise in place - and
         load_lora() afterwards is refused.  Context parallelism is refused: the sharded phases share the code path but are untested
         in this mode."""
-        if self._cfg.use_fp8 == 4:
+        return self._enable_mx(_MXFP6)
+
+    def _enable_mx(self, mode):
+        name, k_multiple, quantize, others = _MX_MODES[mode]
+        if self._cfg.use_fp8 == mode:
             return self
         if self._cfg.use_fp8:
-            raise RuntimeError("enable_mxfp6 after enable_fp8() / enable_mxfp4(): the bf16 weights are gone - reload the weights first")
+            raise RuntimeError(f"enable_{name} after {others}: the bf16 weights are gone - reload the weights first")
         if self.context_parallel is not None:
-            raise RuntimeError("enable_mxfp6: context parallelism is not supported in this mode (sharded MXFP6 is untested)")
+            raise RuntimeError(f"enable_{name}: context parallelism is not supported in this mode (sharded {name.upper()} is untested)")
         for k in (self.dim, self.ffn_dim, self.text_dim, self.freq_dim):
-            if k % 128:
-                raise ValueError("enable_mxfp6: every Linear input width must be a multiple of 128")
+            if k % k_multiple:
+                raise ValueError(f"enable_{name}: every Linear input width must be a multiple of {k_multiple}")
         if self._w is None:
-            raise RuntimeError("load weights before enable_mxfp6()")
-        keys = list(_FP8_TOP) + [f"L{l}.{name}" for l in range(self.num_layers) for name in _FP8_LAYER]
+            raise RuntimeError(f"load weights before enable_{name}()")
+        keys = list(_FP8_TOP) + [f"L{l}.{w}" for l in range(self.num_layers) for w in _FP8_LAYER]
         table = (c_vp * len(keys))()
-        self._mxfp6_scales = {}           # _tensors key -> the weight's block scales, [N, K / 32] bytes
+        self._mx_scales = {}              # _tensors key -> the weight's block scales, [N, K / 32] bytes
         for i, key in enumerate(keys):
-            codes, scales = ops.quantize_mxfp6(self._tensors[key])
-            self._tensors[key], self._mxfp6_scales[key] = codes, scales
+            codes, scales = quantize(self._tensors[key])
+            self._tensors[key], self._mx_scales[key] = codes, scales
             table[i] = scales.data_ptr()
             if i < len(_FP8_TOP):
                 setattr(self._w, key, codes.data_ptr())
@@ -431,7 +408,7 @@ class CausalWanModel:
         torch.cuda.synchronize(self.device)   # the bf16 weights the quantiser reads are released above, tensor by tensor
         self._fp8_row_table = table
         self._w.fp8_row_scales = ctypes.cast(table, ctypes.POINTER(c_vp))
-        self._cfg.use_fp8 = 4
+        self._cfg.use_fp8 = mode
         self._graphs.clear()              # captured graphs replay the bf16 launch sequence on freed bf16 weights
         self._weights_version += 1
         self._ws.clear()                  # the workspace grows by the activation codes and their block scales
@@ -528,7 +505,7 @@ class CausalWanModel:
                 setattr(self._layers_arr[int(layer)], field, q.data_ptr())
         self._fp8_row_table = table
         self._w.fp8_row_scales = ctypes.cast(table, ctypes.POINTER(c_vp))
-        self._cfg.use_fp8 = 2
+        self._cfg.use_fp8 = _FP8_ROWS
         self._graphs.clear()
         self._weights_version += 1
         self._ws.clear()                  # the workspace grows by the fp8 activation buffer and its row scales
@@ -616,13 +593,11 @@ class CausalWanModel:
             for row0, rows in blocks:
                 lora.merge(base[row0:row0 + rows], out[row0:row0 + rows],
                            [(tg.A, tg.B, s * tg.factor) for s, tg in live if (tg.row0, tg.rows) == (row0, rows)])
-            if self._cfg.use_fp8 == 3:
-                # the quantiser of enable_mxfp4 (and of the forward), into the existing code and scale tensors: the weight table and
+            if self._cfg.use_fp8 in _MX_MODES:
+                # the quantiser of _enable_mx (and of the forward), into the existing code and scale tensors: the weight table and
                 # rtv_dit_weights.fp8_row_scales keep pointing at them
-                ops.quantize_mxfp4(out, codes=self._tensors[key], scales=self._mxfp4_scales[key])
-            elif self._cfg.use_fp8 == 4:
-                ops.quantize_mxfp6(out, codes=self._tensors[key], scales=self._mxfp6_scales[key])
-            elif self._cfg.use_fp8 == 2:
+                _MX_MODES[self._cfg.use_fp8][2](out, codes=self._tensors[key], scales=self._mx_scales[key])
+            elif self._cfg.use_fp8 == _FP8_ROWS:
                 q, rs = self._quantize_fp8_rows(out)
                 self._tensors[key].copy_(q)
                 self._fp8_row_scales[key].copy_(rs)      # in place: rtv_dit_weights.fp8_row_scales keeps pointing at it
@@ -827,10 +802,9 @@ class CausalWanModel:
         cp = self.context_parallel
         # (a one-rank group takes the plain forward unless the ContextParallel object insists: bench.py --cp-host-probe)
         use_cp = cp is not None and (cp.world > 1 or getattr(cp, "force_single_rank", False))
-        if cp is not None and self._cfg.use_fp8 == 3:
-            raise RuntimeError("MXFP4 Linears do not support context parallelism (enable_mxfp4)")
-        if cp is not None and self._cfg.use_fp8 == 4:
-            raise RuntimeError("MXFP6 Linears do not support context parallelism (enable_mxfp6)")
+        if cp is not None and self._cfg.use_fp8 in _MX_MODES:
+            name = _MX_MODES[self._cfg.use_fp8][0]
+            raise RuntimeError(f"{name.upper()} Linears do not support context parallelism (enable_{name})")
         # `kv_cache_only` (a per-CALL argument, not in the reference signature: the session passes it for its KV-recompute pass,
         # whose output the reference discards as well, release_server.py:611-632): the forward stops behind the last layer's
         # K / V cache write; the returned tensor is zeros (not while the cross-attention caches are still to be filled: the last

@@ -14,6 +14,7 @@
 // heads.  Two all-to-alls per layer (q|k|v out, attention output back) move 4*(M/world)*d*(world-1)/world elements per
 // rank instead of the all-gather's 2*M*d*(world-1)/world: world/2 times less xGMI traffic.
 #include <atomic>
+#include <string>
 
 #include "../../include/rtv_hip_attn_fp8.h"
 #include "../../include/rtv_hip_mxfp4.h"
@@ -261,28 +262,37 @@ extern "C" size_t rtv_dit_workspace_bytes(const rtv_dit_config* cfg, int F, int 
 // not an nn.Linear - the Conv3d patch embedding - and stays bf16).
 enum { S_TEXT0 = 0, S_TEXT2, S_TIME0, S_TIME2, S_TPROJ, S_HEAD, S_LAYER0 };
 enum { S_QKV = 0, S_O, S_CQ, S_CK, S_CV, S_CO, S_FFN0, S_FFN2, S_PER_LAYER };
+enum { FP8_TENSOR = 1, FP8_ROWS = 2, MODE_MXFP4 = 3, MODE_MXFP6 = 4 };   // the values of cfg->use_fp8 (0: bf16)
 static bool is_fp8(const Ctx& c, int sidx) { return c.cfg->use_fp8 && sidx >= 0; }
+
+// A block-scaled mode (rtv_hip_mxfp4.h, rtv_hip_mxfp6.h): q8 holds an activation's codes, code_bytes(K) per row, then its scales.
+struct MxMode {
+  int (*code_bytes)(int K);
+  decltype(&rtv_quantize_mxfp4) quantize;
+  decltype(&rtv_layernorm_modulate_mxfp4) layernorm_modulate;
+  decltype(&rtv_gemm_mxfp4) gemm;
+};
+static const MxMode MX_MODES[] = {   // [use_fp8 - MODE_MXFP4]
+    {[](int K) { return K / 2; }, rtv_quantize_mxfp4, rtv_layernorm_modulate_mxfp4, rtv_gemm_mxfp4},
+    {[](int K) { return RTV_MXFP6_CODE_BYTES(K); }, rtv_quantize_mxfp6, rtv_layernorm_modulate_mxfp6, rtv_gemm_mxfp6},
+};
+static const MxMode* mx_mode(const Ctx& c) {
+  return c.cfg->use_fp8 == MODE_MXFP4 || c.cfg->use_fp8 == MODE_MXFP6 ? &MX_MODES[c.cfg->use_fp8 - MODE_MXFP4] : nullptr;
+}
+static uint8_t* mx_scales(const Ctx& c, const MxMode& mx, int M, int K) { return c.b.q8 + (size_t)M * mx.code_bytes(K); }
 
 // Quantise half of a Linear: its input `a` [M][K] becomes e4m3 codes in q8 and the mode's scales in fscale / frow.  Nothing to do in
 // bf16, and nothing when a == nullptr: the input is in q8 / frow already (ln_input: the LayerNorm in front of this Linear quantised
 // its own output).  The weight's scales are asked for here, in front of the first launch of the Linear.
-// MXFP4 (use_fp8 == 3, rtv_hip_mxfp4.h): the block scales of an [M][K] activation in q8, behind its codes
-static uint8_t* mx_scales(const Ctx& c, int M, int K) { return c.b.q8 + (size_t)M * K / 2; }
-// MXFP6 (use_fp8 == 4, rtv_hip_mxfp6.h): the same with 3 K / 4 bytes of codes per row
-static uint8_t* mx6_scales(const Ctx& c, int M, int K) { return c.b.q8 + (size_t)M * RTV_MXFP6_CODE_BYTES(K); }
-
 static int quantize_input(Ctx& c, int sidx, const void* a, int M, int K, rtv_stream_t s) {
   if (!is_fp8(c, sidx)) return 0;
-  if (c.cfg->use_fp8 == 3) {
+  if (const MxMode* mx = mx_mode(c)) {
     // per 32-element block: like the row scales, the decisions of a row need that row alone
-    if (!c.w->fp8_row_scales || !c.w->fp8_row_scales[sidx]) return set_error(-1, "dit: use_fp8 == 3 needs rtv_dit_weights.fp8_row_scales");
-    return a ? rtv_quantize_mxfp4(a, K, M, K, c.b.q8, K / 2, mx_scales(c, M, K), K / 32, s) : 0;
+    if (!c.w->fp8_row_scales || !c.w->fp8_row_scales[sidx])
+      return set_error(-1, ("dit: use_fp8 == " + std::to_string(c.cfg->use_fp8) + " needs rtv_dit_weights.fp8_row_scales").c_str());
+    return a ? mx->quantize(a, K, M, K, c.b.q8, mx->code_bytes(K), mx_scales(c, *mx, M, K), K / 32, s) : 0;
   }
-  if (c.cfg->use_fp8 == 4) {
-    if (!c.w->fp8_row_scales || !c.w->fp8_row_scales[sidx]) return set_error(-1, "dit: use_fp8 == 4 needs rtv_dit_weights.fp8_row_scales");
-    return a ? rtv_quantize_mxfp6(a, K, M, K, c.b.q8, RTV_MXFP6_CODE_BYTES(K), mx6_scales(c, M, K), K / 32, s) : 0;
-  }
-  if (c.cfg->use_fp8 == 2) {
+  if (c.cfg->use_fp8 == FP8_ROWS) {
     // per-row scales: the quantisation of a row needs that row alone, so a token shard takes the unsharded forward's decisions
     if (!c.w->fp8_row_scales || !c.w->fp8_row_scales[sidx]) return set_error(-1, "dit: use_fp8 == 2 needs rtv_dit_weights.fp8_row_scales");
     return a ? rtv_quantize_fp8_rows(a, K, M, K, c.b.q8, K, c.b.frow, s) : 0;
@@ -298,23 +308,17 @@ static int quantize_input(Ctx& c, int sidx, const void* a, int M, int K, rtv_str
 static int project(Ctx& c, int sidx, const void* a, int K, const void* w, int w_row0, const void* bias, void* out, int ldc, int M, int N,
                    int act, const void* gate, int gate_stride, int rpf, int row_off, const void* res, int cfg, rtv_stream_t s) {
   const bool fp8 = is_fp8(c, sidx);
-  const bool mx = fp8 && c.cfg->use_fp8 == 3;
-  const bool mx6 = fp8 && c.cfg->use_fp8 == 4;
+  const MxMode* mx = fp8 ? mx_mode(c) : nullptr;
   // fp8 weights are bytes, MXFP4 nibbles, MXFP6 three bytes per four elements
-  const void* wp = (const char*)w + (mx    ? (size_t)w_row0 * K / 2
-                                     : mx6 ? (size_t)w_row0 * RTV_MXFP6_CODE_BYTES(K)
-                                           : (size_t)w_row0 * K * (fp8 ? 1 : 2));
+  const void* wp = (const char*)w + (size_t)w_row0 * (mx ? mx->code_bytes(K) : K * (fp8 ? 1 : 2));
   const void* bp = bias ? (const uint16_t*)bias + w_row0 : nullptr;
   const int ldr = res ? ldc : 0;
   if (!fp8) return rtv_gemm(a, K, wp, K, out, ldc, M, N, K, bp, act, gate, gate_stride, rpf, row_off, res, ldr, RTV_DTYPE_BF16, cfg, s);
   if (mx)
-    return rtv_gemm_mxfp4(c.b.q8, K / 2, wp, K / 2, mx_scales(c, M, K), (const uint8_t*)c.w->fp8_row_scales[sidx] + (size_t)w_row0 * (K / 32), out,
-                          ldc, M, N, K, bp, act, gate, gate_stride, rpf, row_off, res, ldr, s);
-  if (mx6)
-    return rtv_gemm_mxfp6(c.b.q8, RTV_MXFP6_CODE_BYTES(K), wp, RTV_MXFP6_CODE_BYTES(K), mx6_scales(c, M, K),
-                          (const uint8_t*)c.w->fp8_row_scales[sidx] + (size_t)w_row0 * (K / 32), out, ldc, M, N, K, bp, act, gate, gate_stride,
-                          rpf, row_off, res, ldr, s);
-  if (c.cfg->use_fp8 == 2)
+    return mx->gemm(c.b.q8, mx->code_bytes(K), wp, mx->code_bytes(K), mx_scales(c, *mx, M, K),
+                    (const uint8_t*)c.w->fp8_row_scales[sidx] + (size_t)w_row0 * (K / 32), out, ldc, M, N, K, bp, act, gate, gate_stride, rpf,
+                    row_off, res, ldr, s);
+  if (c.cfg->use_fp8 == FP8_ROWS)
     return rtv_gemm_fp8_rows(c.b.q8, K, wp, K, c.b.frow, (const float*)c.w->fp8_row_scales[sidx] + w_row0, out, ldc, M, N, K, bp, act, gate,
                              gate_stride, rpf, row_off, res, ldr, s);
   return rtv_gemm_fp8(c.b.q8, K, wp, K, c.b.fscale, c.w->fp8_scales[sidx], out, ldc, M, N, K, bp, act, gate, gate_stride, rpf, row_off, res,
@@ -333,17 +337,12 @@ static int linear(Ctx& c, int sidx, const void* a, int K, const void* w, const v
 static int ln_input(Ctx& c, const void* shift, const void* scale, int frame_stride, const void* weight, const void* bias, const void** a) {
   DitBuffers& b = c.b;
   const int rpf = scale ? c.fs : 0, r0 = scale ? c.r0 : 0;
-  if (c.cfg->use_fp8 == 3) {
+  if (const MxMode* mx = mx_mode(c)) {
     *a = nullptr;
-    return rtv_layernorm_modulate_mxfp4(b.x, b.q8, c.d / 2, mx_scales(c, c.rc, c.d), c.d / 32, c.rc, c.d, c.cfg->eps, shift, scale, frame_stride,
-                                        rpf, r0, weight, bias, c.stream);
+    return mx->layernorm_modulate(b.x, b.q8, mx->code_bytes(c.d), mx_scales(c, *mx, c.rc, c.d), c.d / 32, c.rc, c.d, c.cfg->eps, shift, scale,
+                                  frame_stride, rpf, r0, weight, bias, c.stream);
   }
-  if (c.cfg->use_fp8 == 4) {
-    *a = nullptr;
-    return rtv_layernorm_modulate_mxfp6(b.x, b.q8, RTV_MXFP6_CODE_BYTES(c.d), mx6_scales(c, c.rc, c.d), c.d / 32, c.rc, c.d, c.cfg->eps, shift,
-                                        scale, frame_stride, rpf, r0, weight, bias, c.stream);
-  }
-  if (c.cfg->use_fp8 == 2) {
+  if (c.cfg->use_fp8 == FP8_ROWS) {
     *a = nullptr;
     return rtv_layernorm_modulate_fp8_rows(b.x, b.q8, c.d, b.frow, c.rc, c.d, c.cfg->eps, shift, scale, frame_stride, rpf, r0, weight, bias,
                                            c.stream);
@@ -453,7 +452,7 @@ static int dit_layer_proj(Ctx& c, int l, int parts, int world, void* q_send, voi
       }
     }
     const int sidx = S_LAYER0 + S_PER_LAYER * l + S_QKV;
-    const void* a = c.cfg->use_fp8 >= 2 ? nullptr : b.xn;   // what the LN phase left: b.xn, or codes and scales in q8 / frow (modes 2, 3, 4)
+    const void* a = c.cfg->use_fp8 >= FP8_ROWS ? nullptr : b.xn;   // what the LN phase left: b.xn, or codes and scales in q8 / frow (modes 2, 3, 4)
     RTV_TRY(quantize_input(c, sidx, a, c.rc, d, c.stream));
     auto proj = [&](int w_row0, int N, void* out, int ldc) {
       return project(c, sidx, a, d, lw.qkv_w, w_row0, lw.qkv_b, out, ldc, c.rc, N, 0, nullptr, 0, 0, 0, nullptr, c.tc, c.stream);

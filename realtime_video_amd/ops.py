@@ -3,6 +3,7 @@
 PyTorch is plumbing here: it owns device memory and the stream; all arithmetic happens in
 librtv_hip.so.  Every wrapper refuses non-GPU tensors (no CPU fallback).
 """
+import collections
 import ctypes
 import math
 
@@ -447,172 +448,144 @@ def gemm_fp8_rows(a_q, a_scales, w_q, w_scales, bias=None, act=ACT_NONE, gate=No
     return out
 
 
-# --------------------------------------------------------------------------------------- MXFP4 path (include/rtv_hip_mxfp4.h)
-MXFP4_BLOCK = 32
+# ------------------------------------------------------- block-scaled paths (include/rtv_hip_mxfp4.h, include/rtv_hip_mxfp6.h)
+class _MxFormat(collections.namedtuple("_MxFormat", "name group_elems group_bytes scale_align k_multiple min_codes")):
+    """A block-scaled format: `group_elems` codes fill `group_bytes` bytes, a row's scales are padded to `scale_align` bytes, the
+    GEMM takes K % k_multiple == 0; `min_codes` is the spelling of a row's code bytes in messages."""
+    block = 32
+
+    def code_bytes(self, k):
+        return k // self.group_elems * self.group_bytes
+
+    def scale_bytes(self, k):
+        return ((k // self.block) + self.scale_align - 1) & ~(self.scale_align - 1)
+
+
+_MXFP4 = _MxFormat("mxfp4", 2, 1, 8, 256, "d / 2")
+_MXFP6 = _MxFormat("mxfp6", 4, 3, 4, 128, "3 d / 4")
+MXFP4_BLOCK = _MXFP4.block
+MXFP6_BLOCK = _MXFP6.block
 
 
 def mxfp4_scale_bytes(k):
     """Bytes a row of k elements owns in a scales array (RTV_MXFP4_SCALE_BYTES)."""
-    return ((k // MXFP4_BLOCK) + 7) & ~7
+    return _MXFP4.scale_bytes(k)
 
 
-def _mxfp4_out(M, d, device, codes, scales):
+def mxfp6_scale_bytes(k):
+    """Bytes a row of k elements owns in a scales array (RTV_MXFP6_SCALE_BYTES)."""
+    return _MXFP6.scale_bytes(k)
+
+
+def mxfp6_code_bytes(k):
+    """Bytes a row of k elements owns in a codes array (RTV_MXFP6_CODE_BYTES)."""
+    return _MXFP6.code_bytes(k)
+
+
+def _mx_out(fmt, M, d, device, codes, scales):
     if codes is None:
-        codes = torch.empty((M, d // 2), dtype=torch.uint8, device=device)
+        codes = torch.empty((M, fmt.code_bytes(d)), dtype=torch.uint8, device=device)
     if scales is None:
         # (zero-filled: a row whose last K-tile is short owns bytes the kernel never writes)
-        scales = torch.zeros((M, mxfp4_scale_bytes(d)), dtype=torch.uint8, device=device)
+        scales = torch.zeros((M, fmt.scale_bytes(d)), dtype=torch.uint8, device=device)
     for t in (codes, scales):
         if t.dtype != torch.uint8 or t.dim() != 2 or t.shape[0] != M or t.stride(1) != 1:
-            raise TypeError("mxfp4: codes and scales are uint8 matrices of M rows with contiguous rows")
-    if codes.shape[1] != d // 2 or scales.shape[1] != mxfp4_scale_bytes(d):
-        raise ValueError("mxfp4: codes must be [M, d / 2] and scales [M, RTV_MXFP4_SCALE_BYTES(d)]")
+            raise TypeError(f"{fmt.name}: codes and scales are uint8 matrices of M rows with contiguous rows")
+    if codes.shape[1] != fmt.code_bytes(d) or scales.shape[1] != fmt.scale_bytes(d):
+        raise ValueError(f"{fmt.name}: codes must be [M, {fmt.min_codes}] and scales [M, RTV_{fmt.name.upper()}_SCALE_BYTES(d)]")
     return codes, scales
 
 
-def quantize_mxfp4(x, codes=None, scales=None):
-    """MXFP4 quantisation of a bf16 matrix [M, d], d % 32 == 0: returns (codes, scales), uint8 [M, d / 2] (two e2m1 codes per
-    byte, element 2j in the low nibble) and uint8 [M, RTV_MXFP4_SCALE_BYTES(d)] (e8m0 block scales in the header's order)."""
+def _quantize_mx(fmt, x, codes, scales):
     _gpu(x, codes, scales)
     if x.dtype != torch.bfloat16 or x.dim() != 2 or x.stride(1) != 1:
-        raise TypeError("quantize_mxfp4 expects a K-contiguous bf16 matrix")
+        raise TypeError(f"quantize_{fmt.name} expects a K-contiguous bf16 matrix")
     M, d = x.shape
-    if d % MXFP4_BLOCK:
-        raise ValueError("quantize_mxfp4: d must be a multiple of 32")
-    codes, scales = _mxfp4_out(M, d, x.device, codes, scales)
-    _lib.call("rtv_quantize_mxfp4", _ptr(x), ctypes.c_int64(x.stride(0)), M, d, _ptr(codes), ctypes.c_int64(codes.stride(0)),
+    if d % fmt.block:
+        raise ValueError(f"quantize_{fmt.name}: d must be a multiple of 32")
+    codes, scales = _mx_out(fmt, M, d, x.device, codes, scales)
+    _lib.call("rtv_quantize_" + fmt.name, _ptr(x), ctypes.c_int64(x.stride(0)), M, d, _ptr(codes), ctypes.c_int64(codes.stride(0)),
               _ptr(scales), ctypes.c_int64(scales.stride(0)), _stream())
     return codes, scales
 
 
-def layernorm_modulate_mxfp4(x, eps=1e-6, shift=None, scale=None, frame_stride=0, rows_per_frame=0, weight=None, bias=None,
-                             row_offset=0):
-    """layernorm_modulate followed by quantize_mxfp4 on its bf16 result, in one kernel and bit for bit: returns (codes, scales)."""
+def _layernorm_modulate_mx(fmt, x, eps, shift, scale, frame_stride, rows_per_frame, weight, bias, row_offset):
     _gpu(x, shift, scale, weight, bias)
     if x.dtype != torch.bfloat16 or x.dim() != 2 or not x.is_contiguous():
-        raise TypeError("layernorm_modulate_mxfp4 expects a contiguous bf16 matrix")
+        raise TypeError(f"layernorm_modulate_{fmt.name} expects a contiguous bf16 matrix")
     M, d = x.shape
-    if d % MXFP4_BLOCK:
-        raise ValueError("layernorm_modulate_mxfp4: d must be a multiple of 32")
-    codes, scales = _mxfp4_out(M, d, x.device, None, None)
-    _lib.call("rtv_layernorm_modulate_mxfp4", _ptr(x), _ptr(codes), ctypes.c_int64(codes.stride(0)), _ptr(scales),
+    if d % fmt.block:
+        raise ValueError(f"layernorm_modulate_{fmt.name}: d must be a multiple of 32")
+    codes, scales = _mx_out(fmt, M, d, x.device, None, None)
+    _lib.call("rtv_layernorm_modulate_" + fmt.name, _ptr(x), _ptr(codes), ctypes.c_int64(codes.stride(0)), _ptr(scales),
               ctypes.c_int64(scales.stride(0)), M, d, float(eps), _ptr(shift), _ptr(scale), int(frame_stride), int(rows_per_frame),
               int(row_offset), _ptr(weight), _ptr(bias), _stream())
     return codes, scales
 
 
-def gemm_mxfp4(a_codes, a_scales, w_codes, w_scales, bias=None, act=ACT_NONE, gate=None, gate_stride=0, rows_per_frame=0,
-               residual=None, out=None, row_offset=0):
-    """out[M,N] bf16 = epi(sum over 32-blocks of 2^(ea + ew) * (a . w^T)): uint8 code matrices [M, K / 2] and [N, K / 2], uint8
-    block scales [M, K / 32] and [N, K / 32] with dense rows, fp32 accumulation, rtv_gemm's epilogue.  K % 256 == 0."""
+def _gemm_mx(fmt, a_codes, a_scales, w_codes, w_scales, bias, act, gate, gate_stride, rows_per_frame, residual, out, row_offset):
+    who = "gemm_" + fmt.name
     _gpu(a_codes, w_codes, a_scales, w_scales, bias, gate, residual, out)
     for t in (a_codes, w_codes, a_scales, w_scales):
         if t.dtype != torch.uint8 or t.dim() != 2:
-            raise TypeError("gemm_mxfp4 expects uint8 code and scale matrices")
-    M, K = a_codes.shape[0], a_codes.shape[1] * 2
+            raise TypeError(f"{who} expects uint8 code and scale matrices")
+    if a_codes.shape[1] % fmt.group_bytes:
+        raise ValueError(f"{who}: a row of codes is {fmt.min_codes.replace('d', 'K')} bytes")
+    M, K = a_codes.shape[0], a_codes.shape[1] // fmt.group_bytes * fmt.group_elems
     N = w_codes.shape[0]
-    if w_codes.shape[1] * 2 != K or a_codes.stride(1) != 1 or w_codes.stride(1) != 1:
-        raise ValueError("gemm_mxfp4 shape / stride mismatch")
-    if K % 256:
-        raise ValueError("gemm_mxfp4: K must be a multiple of 256")
+    if w_codes.shape[1] != a_codes.shape[1] or a_codes.stride(1) != 1 or w_codes.stride(1) != 1:
+        raise ValueError(f"{who} shape / stride mismatch")
+    if K % fmt.k_multiple:
+        raise ValueError(f"{who}: K must be a multiple of {fmt.k_multiple}")
     for s_, n in ((a_scales, M), (w_scales, N)):
-        if tuple(s_.shape) != (n, K // MXFP4_BLOCK) or not s_.is_contiguous():
-            raise ValueError("gemm_mxfp4 expects contiguous scale matrices [rows, K / 32]")
+        if tuple(s_.shape) != (n, K // fmt.block) or not s_.is_contiguous():
+            raise ValueError(f"{who} expects contiguous scale matrices [rows, K / 32]")
     if out is None:
         out = torch.empty((M, N), dtype=torch.bfloat16, device=a_codes.device)
     ensure_gemm_workspace(a_codes.device)
-    _lib.call("rtv_gemm_mxfp4", _ptr(a_codes), a_codes.stride(0), _ptr(w_codes), w_codes.stride(0), _ptr(a_scales), _ptr(w_scales),
+    _lib.call("rtv_" + who, _ptr(a_codes), a_codes.stride(0), _ptr(w_codes), w_codes.stride(0), _ptr(a_scales), _ptr(w_scales),
               _ptr(out), out.stride(0), M, N, K, _ptr(bias), int(act), _ptr(gate), int(gate_stride), int(rows_per_frame),
               int(row_offset), _ptr(residual), residual.stride(0) if residual is not None else 0, _stream())
     return out
 
 
-# --------------------------------------------------------------------------------------- MXFP6 path (include/rtv_hip_mxfp6.h)
-MXFP6_BLOCK = 32
-
-
-def mxfp6_scale_bytes(k):
-    """Bytes a row of k elements owns in a scales array (RTV_MXFP6_SCALE_BYTES)."""
-    return ((k // MXFP6_BLOCK) + 3) & ~3
-
-
-def mxfp6_code_bytes(k):
-    """Bytes a row of k elements owns in a codes array (RTV_MXFP6_CODE_BYTES)."""
-    return k // 4 * 3
-
-
-def _mxfp6_out(M, d, device, codes, scales):
-    if codes is None:
-        codes = torch.empty((M, mxfp6_code_bytes(d)), dtype=torch.uint8, device=device)
-    if scales is None:
-        # (zero-filled: a row whose last K-tile is short owns bytes the kernel never writes)
-        scales = torch.zeros((M, mxfp6_scale_bytes(d)), dtype=torch.uint8, device=device)
-    for t in (codes, scales):
-        if t.dtype != torch.uint8 or t.dim() != 2 or t.shape[0] != M or t.stride(1) != 1:
-            raise TypeError("mxfp6: codes and scales are uint8 matrices of M rows with contiguous rows")
-    if codes.shape[1] != mxfp6_code_bytes(d) or scales.shape[1] != mxfp6_scale_bytes(d):
-        raise ValueError("mxfp6: codes must be [M, 3 d / 4] and scales [M, RTV_MXFP6_SCALE_BYTES(d)]")
-    return codes, scales
+def quantize_mxfp4(x, codes=None, scales=None):
+    """MXFP4 quantisation of a bf16 matrix [M, d], d % 32 == 0: returns (codes, scales), uint8 [M, d / 2] (two e2m1 codes per
+    byte, element 2j in the low nibble) and uint8 [M, RTV_MXFP4_SCALE_BYTES(d)] (e8m0 block scales in the header's order)."""
+    return _quantize_mx(_MXFP4, x, codes, scales)
 
 
 def quantize_mxfp6(x, codes=None, scales=None):
     """MXFP6 quantisation of a bf16 matrix [M, d], d % 32 == 0: returns (codes, scales), uint8 [M, 3 d / 4] (e2m3 codes, a block of
     32 in 24 bytes, element j at bits [6 j, 6 j + 6)) and uint8 [M, RTV_MXFP6_SCALE_BYTES(d)] (e8m0 block scales in the header's
     order)."""
-    _gpu(x, codes, scales)
-    if x.dtype != torch.bfloat16 or x.dim() != 2 or x.stride(1) != 1:
-        raise TypeError("quantize_mxfp6 expects a K-contiguous bf16 matrix")
-    M, d = x.shape
-    if d % MXFP6_BLOCK:
-        raise ValueError("quantize_mxfp6: d must be a multiple of 32")
-    codes, scales = _mxfp6_out(M, d, x.device, codes, scales)
-    _lib.call("rtv_quantize_mxfp6", _ptr(x), ctypes.c_int64(x.stride(0)), M, d, _ptr(codes), ctypes.c_int64(codes.stride(0)),
-              _ptr(scales), ctypes.c_int64(scales.stride(0)), _stream())
-    return codes, scales
+    return _quantize_mx(_MXFP6, x, codes, scales)
+
+
+def layernorm_modulate_mxfp4(x, eps=1e-6, shift=None, scale=None, frame_stride=0, rows_per_frame=0, weight=None, bias=None,
+                             row_offset=0):
+    """layernorm_modulate followed by quantize_mxfp4 on its bf16 result, in one kernel and bit for bit: returns (codes, scales)."""
+    return _layernorm_modulate_mx(_MXFP4, x, eps, shift, scale, frame_stride, rows_per_frame, weight, bias, row_offset)
 
 
 def layernorm_modulate_mxfp6(x, eps=1e-6, shift=None, scale=None, frame_stride=0, rows_per_frame=0, weight=None, bias=None,
                              row_offset=0):
     """layernorm_modulate followed by quantize_mxfp6 on its bf16 result, in one kernel and bit for bit: returns (codes, scales)."""
-    _gpu(x, shift, scale, weight, bias)
-    if x.dtype != torch.bfloat16 or x.dim() != 2 or not x.is_contiguous():
-        raise TypeError("layernorm_modulate_mxfp6 expects a contiguous bf16 matrix")
-    M, d = x.shape
-    if d % MXFP6_BLOCK:
-        raise ValueError("layernorm_modulate_mxfp6: d must be a multiple of 32")
-    codes, scales = _mxfp6_out(M, d, x.device, None, None)
-    _lib.call("rtv_layernorm_modulate_mxfp6", _ptr(x), _ptr(codes), ctypes.c_int64(codes.stride(0)), _ptr(scales),
-              ctypes.c_int64(scales.stride(0)), M, d, float(eps), _ptr(shift), _ptr(scale), int(frame_stride), int(rows_per_frame),
-              int(row_offset), _ptr(weight), _ptr(bias), _stream())
-    return codes, scales
+    return _layernorm_modulate_mx(_MXFP6, x, eps, shift, scale, frame_stride, rows_per_frame, weight, bias, row_offset)
+
+
+def gemm_mxfp4(a_codes, a_scales, w_codes, w_scales, bias=None, act=ACT_NONE, gate=None, gate_stride=0, rows_per_frame=0,
+               residual=None, out=None, row_offset=0):
+    """out[M,N] bf16 = epi(sum over 32-blocks of 2^(ea + ew) * (a . w^T)): uint8 code matrices [M, K / 2] and [N, K / 2], uint8
+    block scales [M, K / 32] and [N, K / 32] with dense rows, fp32 accumulation, rtv_gemm's epilogue.  K % 256 == 0."""
+    return _gemm_mx(_MXFP4, a_codes, a_scales, w_codes, w_scales, bias, act, gate, gate_stride, rows_per_frame, residual, out, row_offset)
 
 
 def gemm_mxfp6(a_codes, a_scales, w_codes, w_scales, bias=None, act=ACT_NONE, gate=None, gate_stride=0, rows_per_frame=0,
                residual=None, out=None, row_offset=0):
     """out[M,N] bf16 = epi(sum over 32-blocks of 2^(ea + ew) * (a . w^T)): uint8 code matrices [M, 3 K / 4] and [N, 3 K / 4], uint8
     block scales [M, K / 32] and [N, K / 32] with dense rows, fp32 accumulation, rtv_gemm's epilogue.  K % 128 == 0."""
-    _gpu(a_codes, w_codes, a_scales, w_scales, bias, gate, residual, out)
-    for t in (a_codes, w_codes, a_scales, w_scales):
-        if t.dtype != torch.uint8 or t.dim() != 2:
-            raise TypeError("gemm_mxfp6 expects uint8 code and scale matrices")
-    if a_codes.shape[1] % 3:
-        raise ValueError("gemm_mxfp6: a row of codes is 3 K / 4 bytes")
-    M, K = a_codes.shape[0], a_codes.shape[1] // 3 * 4
-    N = w_codes.shape[0]
-    if w_codes.shape[1] != a_codes.shape[1] or a_codes.stride(1) != 1 or w_codes.stride(1) != 1:
-        raise ValueError("gemm_mxfp6 shape / stride mismatch")
-    if K % 128:
-        raise ValueError("gemm_mxfp6: K must be a multiple of 128")
-    for s_, n in ((a_scales, M), (w_scales, N)):
-        if tuple(s_.shape) != (n, K // MXFP6_BLOCK) or not s_.is_contiguous():
-            raise ValueError("gemm_mxfp6 expects contiguous scale matrices [rows, K / 32]")
-    if out is None:
-        out = torch.empty((M, N), dtype=torch.bfloat16, device=a_codes.device)
-    ensure_gemm_workspace(a_codes.device)
-    _lib.call("rtv_gemm_mxfp6", _ptr(a_codes), a_codes.stride(0), _ptr(w_codes), w_codes.stride(0), _ptr(a_scales), _ptr(w_scales),
-              _ptr(out), out.stride(0), M, N, K, _ptr(bias), int(act), _ptr(gate), int(gate_stride), int(rows_per_frame),
-              int(row_offset), _ptr(residual), residual.stride(0) if residual is not None else 0, _stream())
-    return out
+    return _gemm_mx(_MXFP6, a_codes, a_scales, w_codes, w_scales, bias, act, gate, gate_stride, rows_per_frame, residual, out, row_offset)
 
 
 # --------------------------------------------------------------------------------------- norms

@@ -12,61 +12,18 @@ test installs it with `monkeypatch.setattr(wan_oracle, "fp8_linear", mx_linear)`
 tests/mxfp4_oracle.py is installed.  The packers are the Python twin of the header's storage macros; the structured inputs of the
 quantiser tests and the exact GEMM cases live here too, so that the CPU tests vet exactly what the GPU tests run."""
 import torch
-import torch.nn.functional as F
 
-BLOCK = 32
+import mx_oracle
+from mx_oracle import BLOCK, mx_dequantize, product_fp64   # (the shared restatement; re-exported)
+
 BLOCK_BYTES = 24
 # magnitude of code c (the 6-bit code is sign << 5 | c; c = exponent field << 3 | mantissa)
 E2M3 = tuple(m / 8 if ex == 0 else (1 + m / 8) * 2.0 ** (ex - 1) for ex in range(4) for m in range(8))
-_EVEN_FIRST = tuple(range(0, 32, 2)) + tuple(range(1, 32, 2))   # torch.argmin returns the first of equal minima: the even code wins
-_LARGE_FIRST = tuple(range(31, -1, -1))                         # mutant: the larger magnitude wins a tie (round half away from zero)
-
-
-def _blocks(t):
-    if t.shape[-1] % BLOCK:
-        raise ValueError("the last dim must be a multiple of 32")
-    return t.detach().double().reshape(*t.shape[:-1], t.shape[-1] // BLOCK, BLOCK)
-
-
-def _nearest(a, order):
-    grid = torch.tensor([E2M3[c] for c in order], dtype=torch.float64, device=a.device)
-    k = (a.unsqueeze(-1) - grid).abs().argmin(dim=-1)                 # exact: a has at most 24 significant bits
-    return torch.tensor(order, device=a.device)[k]
-
-
-def mx_quantize(t, tie_order=_EVEN_FIRST, ceil_scale=False, saturate=True):
-    """-> (code values in {0, +-1/8, ..., +-7.5} as float64, shape of t; block exponents e as int64 [..., K / 32]).
-    The keyword arguments build the mutants of tests/test_mxfp6_cpu.py; the defaults are the format."""
-    x = _blocks(t)
-    amax = x.abs().amax(dim=-1)
-    mant, ex = torch.frexp(amax)                                      # amax = mant * 2^ex, mant in [0.5, 1): floor(log2) = ex - 1
-    lg = ex.long() - 1
-    if ceil_scale:
-        lg = lg + (mant != 0.5).long()
-    e = torch.where(amax > 0, (lg - 2).clamp(-127, 127), torch.full_like(lg, -127))
-    y = torch.ldexp(x, -e.unsqueeze(-1))                              # exact in float64
-    a = y.abs()
-    c = _nearest(a, tie_order)
-    if not saturate:
-        # mutant: a format without saturation rounds [7.75, 8] to the next binade, 8, whose 5-bit magnitude code wraps to 0
-        c = torch.where(a >= 7.75, torch.zeros_like(c), c)
-    val = torch.tensor(E2M3, dtype=torch.float64, device=t.device)[c]
-    val = torch.where(torch.signbit(y), -val, val)
-    return val.reshape(t.shape), e
-
-
-def mx_dequantize(values, e):
-    return torch.ldexp(_blocks(values), e.unsqueeze(-1)).reshape(values.shape)
-
-
-def mx_linear(x, weight, bias, shards=1):
-    """nn.Linear on MXFP6 operands.  `shards` is accepted and ignored: a block needs nothing but itself."""
-    xq = mx_dequantize(*mx_quantize(x)).float()
-    wq = mx_dequantize(*mx_quantize(weight)).float()
-    y = F.linear(xq, wq)
-    if bias is not None:
-        y = y + bias.float()
-    return y.to(x.dtype)
+_FMT = mx_oracle.Format(E2M3, wrap_from=7.75)         # without saturation [7.75, 8] rounds to 8, whose 5-bit magnitude code wraps to 0
+_EVEN_FIRST, _LARGE_FIRST = _FMT.even_first, _FMT.large_first
+# mx_quantize -> (code values in {0, +-1/8, ..., +-7.5} as float64, shape of t; block exponents e as int64 [..., K / 32]);
+# every term of an exact_case product is a multiple of 2^-8 (two multiples of 1/8, scaled by >= 2^-2)
+mx_quantize, mx_linear, exact_case = _FMT.mx_quantize, _FMT.mx_linear, _FMT.exact_case
 
 
 # ------------------------------------------------------------------------------------------ storage (rtv_hip_mxfp6.h)
@@ -131,11 +88,7 @@ def code_values(s):
 
 def pack_scales(e):
     """block exponents int64 [M, K / 32] -> uint8 [M, RTV_MXFP6_SCALE_BYTES(K)] in the header's order (unowned bytes 0)."""
-    M, nb = e.shape
-    out = torch.zeros(M, scale_bytes(nb * BLOCK), dtype=torch.uint8, device=e.device)
-    pos = torch.tensor([scale_pos(b) for b in range(nb)], device=e.device)
-    out[:, pos] = (e + 127).to(torch.uint8)
-    return out
+    return mx_oracle.pack_scales(e, scale_pos, scale_bytes)
 
 
 # ------------------------------------------------------------------------------------------ test inputs
@@ -182,27 +135,3 @@ def structured_rows(M, d, seed=0):
         e = -100 + (200 * i) // (total - 1)
         x[i] = torch.ldexp(x[i], torch.tensor(e))
     return x.reshape(M, d).to(torch.bfloat16)
-
-
-def exact_case(M, N, K, seed=0):
-    """Operands of the exact GEMM case: codes uniform over all 32 magnitudes with random signs, block exponents in {-1, 0, 1},
-    distinct per row and per block, no symmetry between the operands.  -> dict of code values [M, K] / [N, K] (float64),
-    exponents [M, K / 32] / [N, K / 32] (int64).  Every term is a multiple of 2^-8 (two multiples of 1/8, scaled by >= 2^-2)."""
-    g = torch.Generator().manual_seed(seed)
-    val = torch.tensor(E2M3, dtype=torch.float64)
-
-    def operand(rows):
-        c = val[torch.randint(0, 32, (rows, K), generator=g)]
-        c = torch.where(torch.rand(rows, K, generator=g) < 0.5, -c, c)
-        e = torch.randint(-1, 2, (rows, K // BLOCK), generator=g)
-        return c, e
-
-    a, ea = operand(M)
-    w, ew = operand(N)
-    return dict(a=a, ea=ea, w=w, ew=ew)
-
-
-def product_fp64(a, ea, w, ew):
-    """-> (sum_k dq(a) dq(w) in float64 [M, N], sum_k |terms| [M, N])"""
-    da, dw = mx_dequantize(a, ea), mx_dequantize(w, ew)
-    return da @ dw.t(), da.abs() @ dw.abs().t()
