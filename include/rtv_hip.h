@@ -237,7 +237,10 @@ typedef struct rtv_dit_config {
                                    3: MXFP4 - e2m1 codes, two per byte, with one e8m0 scale per 32 elements (the *_w pointers of the
                                    Linears address codes, fp8_row_scales their block scales; rtv_hip_mxfp4.h);
                                    4: MXFP6 - e2m3 codes, 24 bytes per 32 elements, with one e8m0 scale per 32 elements (pointers as
-                                   for 3; rtv_hip_mxfp6.h) */
+                                   for 3; rtv_hip_mxfp6.h);
+                                   5 / 6: 3 / 4 with the 32-point block Hadamard rotation in front of both quantisers - the weights'
+                                   codes were made by rtv_quantize_mx*_rot at RTV_MX_ROT_WEIGHT_SHIFT (rtv_hip_mx_rotate.h; storage,
+                                   pointers and workspace as for 3 / 4) */
   int max_attn_kv_splits;       /* largest rtv_dit_step.attn_kv_splits this workspace must serve (0 / 1: none - the workspace then
                                    holds no split-attention partials: 97 MB at 14B, M = 4680); a step asking for more fails */
 } rtv_dit_config;

@@ -12,6 +12,7 @@ Surface used by the reference's callers and reproduced here:
 """
 import collections
 import ctypes
+import functools
 import math
 import os
 import types
@@ -38,10 +39,18 @@ _TOP_FIELDS = tuple(n for n, t in _Weights._fields_ if t is c_vp)      # the dev
 _FP8_TOP = ("text0_w", "text2_w", "time0_w", "time2_w", "tproj_w", "head_w")
 _FP8_LAYER = ("qkv_w", "o_w", "cq_w", "ck_w", "cv_w", "co_w", "ffn0_w", "ffn2_w")
 # rtv_dit_config.use_fp8: how the Linears of _FP8_TOP / _FP8_LAYER run
-_BF16, _FP8_TENSOR, _FP8_ROWS, _MXFP4, _MXFP6 = range(5)
-# the block-scaled modes: (name, the Linear input widths' multiple, weight and LoRA quantiser, the enable_* calls it excludes)
-_MX_MODES = {_MXFP4: ("mxfp4", 256, ops.quantize_mxfp4, "enable_fp8() / enable_mxfp6()"),
-             _MXFP6: ("mxfp6", 128, ops.quantize_mxfp6, "enable_fp8() / enable_mxfp4()")}
+_BF16, _FP8_TENSOR, _FP8_ROWS, _MXFP4, _MXFP6, _MXFP4_ROT, _MXFP6_ROT = range(7)
+# the block-scaled modes: (name, the Linear input widths' multiple, weight and LoRA quantiser, the enable_* calls it excludes).  The
+# rotated modes (include/rtv_hip_mx_rotate.h) quantise the weights with the rotated kernel at the weight shift; the forward rotates
+# the activations at the activation shift.
+def _rot_weights(quantize):
+    return functools.partial(quantize, rotate_shift=ops.MX_ROT_WEIGHT_SHIFT)
+
+
+_MX_MODES = {_MXFP4: ("mxfp4", 256, ops.quantize_mxfp4, "enable_fp8() / enable_mxfp6() / enable_mxfp4(rotate=True)"),
+             _MXFP6: ("mxfp6", 128, ops.quantize_mxfp6, "enable_fp8() / enable_mxfp4() / enable_mxfp6(rotate=True)"),
+             _MXFP4_ROT: ("mxfp4", 256, _rot_weights(ops.quantize_mxfp4), "enable_fp8() / enable_mxfp6() / enable_mxfp4(rotate=False)"),
+             _MXFP6_ROT: ("mxfp6", 128, _rot_weights(ops.quantize_mxfp6), "enable_fp8() / enable_mxfp4() / enable_mxfp6(rotate=False)")}
 
 PROJ_LN, PROJ_Q, PROJ_KV = 1, 2, 4
 
@@ -311,7 +320,8 @@ class CausalWanModel:
             raise ValueError(f"enable_fp8: granularity must be 'tensor' or 'row', got {granularity!r}")
         mode = _FP8_ROWS if granularity == "row" else _FP8_TENSOR
         if self._cfg.use_fp8 in _MX_MODES:
-            raise RuntimeError(f"enable_fp8 after enable_{_MX_MODES[self._cfg.use_fp8][0]}(): the bf16 weights are gone - "
+            rotate = "rotate=True" if self._cfg.use_fp8 in (_MXFP4_ROT, _MXFP6_ROT) else ""
+            raise RuntimeError(f"enable_fp8 after enable_{_MX_MODES[self._cfg.use_fp8][0]}({rotate}): the bf16 weights are gone - "
                                "reload the weights first")
         if self._w is None:
             raise RuntimeError("load weights before enable_fp8()")
@@ -348,7 +358,7 @@ class CausalWanModel:
         ops.ensure_gemm_workspace(self.device)
         return self
 
-    def enable_mxfp4(self):
+    def enable_mxfp4(self, rotate=False):
         """Opt-in: every nn.Linear that enable_fp8() covers runs on MXFP4 operands instead (include/rtv_hip_mxfp4.h: OCP e2m1 codes,
         one e8m0 scale per 32 elements of the input width, multiplied by the block-scaled FP4 MFMA of gfx950, which applies the
         scales itself).  The weights are quantised here, by the kernel that quantises the activations inside the forward
@@ -360,10 +370,18 @@ class CausalWanModel:
         Call after load_state_dict / init_random_weights; the bf16 copies of the quantised weights are freed.  Mutually exclusive
         with enable_fp8() in either direction (reload the weights first).  LoRA as under enable_fp8(): load adapters first -
         set_lora_scale() / unload_lora() then re-merge from the bf16 bases and re-quantise in place - and load_lora() afterwards is
-        refused.  Context parallelism is refused: the sharded phases share the code path but are untested in this mode."""
-        return self._enable_mx(_MXFP4)
+        refused.  Context parallelism is refused: the sharded phases share the code path but are untested in this mode.
 
-    def enable_mxfp6(self):
+        rotate=True (opt-in; rtv_dit_config.use_fp8 == 5): both operands of every such Linear go through a 32-point Hadamard
+        rotation of each MX block inside the quantisers (include/rtv_hip_mx_rotate.h; weights here at 2^-2, activations in the
+        forward at 2^-3, so the product is that of the plain operands).  An outlier channel then no longer sets the shared exponent
+        of its block alone: on Gaussian operands the error is unchanged, on operands with outlier channels it returns to the
+        Gaussian figure (tests/test_mx_rotate_cpu.py; DESIGN.md section 6 has what was measured on the GPU and what was not).  The
+        GEMM, the storage and the workspace are those of rotate=False; the pin is tests/mx_rotate_oracle.py.  The two values of
+        `rotate` exclude each other like two modes: the other one afterwards is refused (reload the weights first)."""
+        return self._enable_mx(_MXFP4_ROT if rotate else _MXFP4)
+
+    def enable_mxfp6(self, rotate=False):
         """Opt-in: every nn.Linear that enable_fp8() / enable_mxfp4() cover runs on MXFP6 operands instead (include/rtv_hip_mxfp6.h:
         OCP e2m3 codes, one e8m0 scale per 32 elements of the input width, multiplied by the block-scaled MFMA of gfx950 in its FP6
         form, which applies the scales itself and issues at the FP4 rate).  Three mantissa bits, as e4m3 has, and a scale per 32
@@ -377,8 +395,11 @@ class CausalWanModel:
         with enable_fp8() and enable_mxfp4() in either direction (reload the weights first).  LoRA as under enable_mxfp4(): load
         adapters first - set_lora_scale() / unload_lora() then re-merge from the bf16 bases and re-quantise in place - and
         load_lora() afterwards is refused.  Context parallelism is refused: the sharded phases share the code path but are untested
-        in this mode."""
-        return self._enable_mx(_MXFP6)
+        in this mode.
+
+        rotate=True (opt-in; rtv_dit_config.use_fp8 == 6): the block Hadamard rotation of enable_mxfp4(rotate=True) in front of the
+        MXFP6 quantisers, with the same exclusions."""
+        return self._enable_mx(_MXFP6_ROT if rotate else _MXFP6)
 
     def _enable_mx(self, mode):
         name, k_multiple, quantize, others = _MX_MODES[mode]

@@ -19,6 +19,7 @@
 #include "../../include/rtv_hip_attn_fp8.h"
 #include "../../include/rtv_hip_mxfp4.h"
 #include "../../include/rtv_hip_mxfp6.h"
+#include "../../include/rtv_hip_mx_rotate.h"
 #include "rtv_common.h"
 #include "rtv_internal.h"
 
@@ -99,7 +100,7 @@ struct DitBuffers {
   uint16_t *sinus, *te1, *e, *se, *e0, *emod, *ehead, *ctx1, *ctx, *ktmp;
   uint8_t* q8;      // fp8 path: the quantised activation of the linear being computed (use_fp8 == 3, MXFP4: its e2m1 codes in the
                     // first rows * K / 2 bytes and its block scales behind them - 17 / 32 of the fp8 size; use_fp8 == 4, MXFP6: e2m3
-                    // codes in the first rows * 3 K / 4 bytes, block scales behind them - 25 / 32)
+                    // codes in the first rows * 3 K / 4 bytes, block scales behind them - 25 / 32; 5 / 6, the rotated modes: as 3 / 4)
   float* frow;      // fp8 path with per-row scales (use_fp8 == 2): the row scales of the activation in q8
   float* fscale;    // fp8 path: its per-tensor scale (device), followed by the 4-byte absmax scratch
   float* attn_part; // KV-split self-attention of a sharded call: fp32 partial outputs + (m, l) of splits x heads x rows <= H x M
@@ -262,22 +263,32 @@ extern "C" size_t rtv_dit_workspace_bytes(const rtv_dit_config* cfg, int F, int 
 // not an nn.Linear - the Conv3d patch embedding - and stays bf16).
 enum { S_TEXT0 = 0, S_TEXT2, S_TIME0, S_TIME2, S_TPROJ, S_HEAD, S_LAYER0 };
 enum { S_QKV = 0, S_O, S_CQ, S_CK, S_CV, S_CO, S_FFN0, S_FFN2, S_PER_LAYER };
-enum { FP8_TENSOR = 1, FP8_ROWS = 2, MODE_MXFP4 = 3, MODE_MXFP6 = 4 };   // the values of cfg->use_fp8 (0: bf16)
+enum { FP8_TENSOR = 1, FP8_ROWS = 2, MODE_MXFP4 = 3, MODE_MXFP6 = 4, MODE_MXFP4_ROT = 5, MODE_MXFP6_ROT = 6 };   // the values of cfg->use_fp8 (0: bf16)
 static bool is_fp8(const Ctx& c, int sidx) { return c.cfg->use_fp8 && sidx >= 0; }
 
 // A block-scaled mode (rtv_hip_mxfp4.h, rtv_hip_mxfp6.h): q8 holds an activation's codes, code_bytes(K) per row, then its scales.
+// The rotated modes (rtv_hip_mx_rotate.h) are the same rows with the rotated quantisers: the weights were rotated at the weight shift
+// when they were quantised, the activations are at the activation shift here, and the GEMM is the unrotated mode's.
 struct MxMode {
   int (*code_bytes)(int K);
   decltype(&rtv_quantize_mxfp4) quantize;
   decltype(&rtv_layernorm_modulate_mxfp4) layernorm_modulate;
   decltype(&rtv_gemm_mxfp4) gemm;
 };
+template <decltype(&rtv_quantize_mxfp4_rot) Q>
+static int quantize_act_rot(const void* x, int64_t ld, int M, int d, void* codes, int64_t ld_codes, void* scales, int64_t ld_scales,
+                            rtv_stream_t s) {
+  return Q(x, ld, M, d, codes, ld_codes, scales, ld_scales, RTV_MX_ROT_ACT_SHIFT, s);
+}
 static const MxMode MX_MODES[] = {   // [use_fp8 - MODE_MXFP4]
     {[](int K) { return K / 2; }, rtv_quantize_mxfp4, rtv_layernorm_modulate_mxfp4, rtv_gemm_mxfp4},
     {[](int K) { return RTV_MXFP6_CODE_BYTES(K); }, rtv_quantize_mxfp6, rtv_layernorm_modulate_mxfp6, rtv_gemm_mxfp6},
+    {[](int K) { return K / 2; }, quantize_act_rot<rtv_quantize_mxfp4_rot>, rtv_layernorm_modulate_mxfp4_rot, rtv_gemm_mxfp4},
+    {[](int K) { return RTV_MXFP6_CODE_BYTES(K); }, quantize_act_rot<rtv_quantize_mxfp6_rot>, rtv_layernorm_modulate_mxfp6_rot,
+     rtv_gemm_mxfp6},
 };
 static const MxMode* mx_mode(const Ctx& c) {
-  return c.cfg->use_fp8 == MODE_MXFP4 || c.cfg->use_fp8 == MODE_MXFP6 ? &MX_MODES[c.cfg->use_fp8 - MODE_MXFP4] : nullptr;
+  return c.cfg->use_fp8 >= MODE_MXFP4 && c.cfg->use_fp8 <= MODE_MXFP6_ROT ? &MX_MODES[c.cfg->use_fp8 - MODE_MXFP4] : nullptr;
 }
 static uint8_t* mx_scales(const Ctx& c, const MxMode& mx, int M, int K) { return c.b.q8 + (size_t)M * mx.code_bytes(K); }
 
@@ -452,7 +463,7 @@ static int dit_layer_proj(Ctx& c, int l, int parts, int world, void* q_send, voi
       }
     }
     const int sidx = S_LAYER0 + S_PER_LAYER * l + S_QKV;
-    const void* a = c.cfg->use_fp8 >= FP8_ROWS ? nullptr : b.xn;   // what the LN phase left: b.xn, or codes and scales in q8 / frow (modes 2, 3, 4)
+    const void* a = c.cfg->use_fp8 >= FP8_ROWS ? nullptr : b.xn;   // what the LN phase left: b.xn, or codes and scales in q8 / frow (modes 2 to 6)
     RTV_TRY(quantize_input(c, sidx, a, c.rc, d, c.stream));
     auto proj = [&](int w_row0, int N, void* out, int ldc) {
       return project(c, sidx, a, d, lw.qkv_w, w_row0, lw.qkv_b, out, ldc, c.rc, N, 0, nullptr, 0, 0, 0, nullptr, c.tc, c.stream);

@@ -9,6 +9,9 @@
 //   layernorm_modulate_mx  elementwise.hip's layernorm_modulate_kernel with this quantiser behind its bf16 rounding
 // and the host functions behind the units' extern "C" entries, every check included.
 //
+// ROT (include/rtv_hip_mx_rotate.h; instantiated in mx_rotate.hip): both bodies with the 32-point Sylvester Hadamard transform of each
+// block in front of quantize_chunk - rotate_chunk below.  A template parameter: the ROT = false bodies are the text they were.
+//
 // A format trait F supplies
 //   BITS                          width of a code, sign on top; word_t = an unsigned type that holds a lane's 8 codes
 //   mag(t)                        __device__: the magnitude code of 0 <= t < 8, round to nearest even, saturating
@@ -22,6 +25,7 @@
 #pragma once
 #include <string>
 
+#include "../../include/rtv_hip_mx_rotate.h"
 #include "ln_row.h"
 #include "rtv_common.h"
 #include "rtv_internal.h"
@@ -45,18 +49,51 @@ __device__ __forceinline__ typename F::word_t quantize_chunk(const float* v, uin
   typename F::word_t w = 0;
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
-    const float t = ldexpf(fabsf(v[j]), 127 - eb);   // exact: a power-of-two scaling of a bf16 value, below 8 by construction
+    const float t = ldexpf(fabsf(v[j]), 127 - eb);   // exact: a power-of-two scaling of a bf16 value (ROT: of an fp32 value), below 8 by construction
     w |= (typename F::word_t)(F::mag(t) | ((__float_as_uint(v[j]) >> (32 - F::BITS)) & (1u << (F::BITS - 1)))) << (F::BITS * j);
   }
   return w;
 }
 
+// ------------------------------------------------------------------ block rotation
+// The lane xor 1 / xor 2 partner's value as a DPP quad_perm move: one VALU move inside the quad (a row of 4 lanes), no LDS crossbar
+// (__shfl_xor is ds_bpermute_b32).  Every lane of the quad must be active.
+template <int XOR>
+__device__ __forceinline__ float quad_partner(float x) {
+  static_assert(XOR == 1 || XOR == 2, "inside a quad");
+  constexpr int QUAD_PERM = XOR == 1 ? 0xB1 : 0x4E;   // quad_perm:[1,0,3,2] / [2,3,0,1]
+  return __uint_as_float((uint32_t)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(x), QUAD_PERM, 0xF, 0xF, false));
+}
+
+// v (this lane's 8 of its quad's 32 values, element k = 8 * (lane & 3) + j of the block) -> (v H) * scale with H the Sylvester
+// Hadamard matrix of order 32, by the butterflies of rtv_hip_mx_rotate.h: stage b = 0..4 in this order, (u, v) -> (u + v, u - v) on
+// the pairs (k, k | 1 << b), fp32 adds and subtracts (nothing to fuse: there is no multiplication), then the exact power of two
+// `scale`.  Stages 0-2 are inside the lane; stages 3 and 4 pair it with lane ^ 1 and lane ^ 2: the lane with the bit clear keeps
+// own + partner, the lane with the bit set partner - own = partner + (-own), the same fp32 sum with the sign bit of `own` flipped.
+__device__ __forceinline__ void rotate_chunk(float* v, float scale) {
+#pragma unroll
+  for (int b = 1; b < 8; b <<= 1)
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      if (!(j & b)) {
+        const float u = v[j], w = v[j | b];
+        v[j] = u + w;
+        v[j | b] = u - w;
+      }
+  const uint32_t neg1 = (threadIdx.x & 1u) << 31, neg2 = (threadIdx.x & 2u) << 30;   // (chunk c = lane + i * G, G % 4 == 0: c & 3 = lane & 3)
+#pragma unroll
+  for (int j = 0; j < 8; ++j) v[j] = quad_partner<1>(v[j]) + __uint_as_float(__float_as_uint(v[j]) ^ neg1);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) v[j] = (quad_partner<2>(v[j]) + __uint_as_float(__float_as_uint(v[j]) ^ neg2)) * scale;
+}
+
 // ------------------------------------------------------------------ row quantiser
 // WAVE: a wave per row (4 rows per workgroup); else a workgroup per row.  The G lanes of a row take its 16-byte chunks G apart,
 // MAXC of them each: rows of up to G * 8 * MAXC elements.  d % 32 == 0, so a quad's 4 chunks are inside the row or outside together.
-template <class F, int MAXC, bool WAVE>
+// ROT: each block is rotated and scaled by rot_scale = 2^-shift in front of the conversion (rotate_chunk).
+template <class F, int MAXC, bool WAVE, bool ROT = false>
 __device__ __forceinline__ void quantize_rows(const uint16_t* __restrict__ x, int64_t ld, int M, int d, uint8_t* __restrict__ codes,
-                                              int64_t ld_codes, uint8_t* __restrict__ scales, int64_t ld_scales) {
+                                              int64_t ld_codes, uint8_t* __restrict__ scales, int64_t ld_scales, float rot_scale = 1.f) {
   constexpr int G = WAVE ? 64 : THREADS;
   const int lane = WAVE ? (threadIdx.x & 63) : threadIdx.x;
   const int row = WAVE ? blockIdx.x * (THREADS / 64) + (threadIdx.x >> 6) : blockIdx.x;
@@ -76,6 +113,7 @@ __device__ __forceinline__ void quantize_rows(const uint16_t* __restrict__ x, in
     const int c = lane + i * G;
     float v[8];
     unpack_bf16x8(raw[i], v);
+    if constexpr (ROT) rotate_chunk(v, rot_scale);
     uint32_t E;
     const typename F::word_t w = quantize_chunk<F>(v, &E);
     F::store_chunk(cr, sr, c, c < nchunks, w, E);
@@ -85,7 +123,8 @@ __device__ __forceinline__ void quantize_rows(const uint16_t* __restrict__ x, in
 // ------------------------------------------------------------------ LayerNorm (+ modulation) + quantiser, a workgroup per row
 // layernorm_modulate_kernel's row (ln_row.h: same reductions, same rounding points) up to the value it would store; that value is
 // rounded to bf16 as the store would round it, kept in registers, and quantised as quantize_rows quantises the stored row.
-template <class F>
+// ROT: the kept values are rotated in place, block by block, at the activation shift.
+template <class F, bool ROT = false>
 __device__ __forceinline__ void layernorm_modulate_mx(const bf16_t* __restrict__ x, uint8_t* __restrict__ codes, int64_t ld_codes,
                                                       uint8_t* __restrict__ scales, int64_t ld_scales, int d, float eps,
                                                       const bf16_t* __restrict__ shift, const bf16_t* __restrict__ scale, int frame_stride,
@@ -108,6 +147,7 @@ __device__ __forceinline__ void layernorm_modulate_mx(const bf16_t* __restrict__
 #pragma unroll
   for (int i = 0; i < EW_MAXC; ++i) {
     const int c = threadIdx.x + i * THREADS;
+    if constexpr (ROT) rotate_chunk(v[i], 1.f / (1 << RTV_MX_ROT_ACT_SHIFT));
     uint32_t E;
     const typename F::word_t w = quantize_chunk<F>(v[i], &E);
     F::store_chunk(cr, sr, c, c < nchunks, w, E);
@@ -129,10 +169,11 @@ int check_out(const char* who, int d, const void* codes, int64_t ld_codes, int64
   return 0;
 }
 
-// wave4 / block3 / block7: the unit's quantize kernel as <4, true>, <3, false> and <7, false>
-template <class F>
-int quantize(QuantizeKernel wave4, QuantizeKernel block3, QuantizeKernel block7, const void* x, int64_t ld, int M, int d, void* codes,
-             int64_t ld_codes, void* scales, int64_t ld_scales, rtv_stream_t stream) {
+// wave4 / block3 / block7: the unit's quantize kernel as <4, true>, <3, false> and <7, false>; `extra`: what a kernel takes behind
+// ld_scales (the rotated kernels: rot_scale)
+template <class F, class Kernel = QuantizeKernel, class... Extra>
+int quantize(Kernel wave4, Kernel block3, Kernel block7, const void* x, int64_t ld, int M, int d, void* codes, int64_t ld_codes,
+             void* scales, int64_t ld_scales, rtv_stream_t stream, Extra... extra) {
   const char* who = F::QUANTIZE;
   if (!x || !codes || !scales) return fail(who, "null pointer");
   if (M <= 0 || d <= 0) return fail(who, "empty tensor");
@@ -142,10 +183,10 @@ int quantize(QuantizeKernel wave4, QuantizeKernel block3, QuantizeKernel block7,
   if (int st = check_out<F>(who, d, codes, ld_codes, ld_scales)) return st;
   hipStream_t s = (hipStream_t)stream;
   const bool wave = d <= 64 * 8 * 4;
-  const QuantizeKernel kernel = wave ? wave4 : d <= THREADS * 8 * 3 ? block3 : block7;
+  const Kernel kernel = wave ? wave4 : d <= THREADS * 8 * 3 ? block3 : block7;
   ProfScope prof(PROF_MISC, s, 0.0);
   hipLaunchKernelGGL(kernel, dim3(wave ? (M + 3) / 4 : M), dim3(THREADS), 0, s, (const uint16_t*)x, ld, M, d, (uint8_t*)codes, ld_codes,
-                     (uint8_t*)scales, ld_scales);
+                     (uint8_t*)scales, ld_scales, extra...);
   return check_launch(who);
 }
 

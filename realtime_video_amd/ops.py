@@ -496,20 +496,26 @@ def _mx_out(fmt, M, d, device, codes, scales):
     return codes, scales
 
 
-def _quantize_mx(fmt, x, codes, scales):
+MX_ROT_ACT_SHIFT, MX_ROT_WEIGHT_SHIFT = _lib.MX_ROT_ACT_SHIFT, _lib.MX_ROT_WEIGHT_SHIFT   # include/rtv_hip_mx_rotate.h
+
+
+def _quantize_mx(fmt, x, codes, scales, rotate_shift=None):
     _gpu(x, codes, scales)
     if x.dtype != torch.bfloat16 or x.dim() != 2 or x.stride(1) != 1:
         raise TypeError(f"quantize_{fmt.name} expects a K-contiguous bf16 matrix")
     M, d = x.shape
     if d % fmt.block:
         raise ValueError(f"quantize_{fmt.name}: d must be a multiple of 32")
+    if rotate_shift is not None and not 0 <= int(rotate_shift) <= _lib.MX_ROT_MAX_SHIFT:
+        raise ValueError(f"quantize_{fmt.name}: rotate_shift must be in 0 .. {_lib.MX_ROT_MAX_SHIFT}")
     codes, scales = _mx_out(fmt, M, d, x.device, codes, scales)
-    _lib.call("rtv_quantize_" + fmt.name, _ptr(x), ctypes.c_int64(x.stride(0)), M, d, _ptr(codes), ctypes.c_int64(codes.stride(0)),
-              _ptr(scales), ctypes.c_int64(scales.stride(0)), _stream())
+    rot = () if rotate_shift is None else (int(rotate_shift),)
+    _lib.call("rtv_quantize_" + fmt.name + ("_rot" if rot else ""), _ptr(x), ctypes.c_int64(x.stride(0)), M, d, _ptr(codes),
+              ctypes.c_int64(codes.stride(0)), _ptr(scales), ctypes.c_int64(scales.stride(0)), *rot, _stream())
     return codes, scales
 
 
-def _layernorm_modulate_mx(fmt, x, eps, shift, scale, frame_stride, rows_per_frame, weight, bias, row_offset):
+def _layernorm_modulate_mx(fmt, x, eps, shift, scale, frame_stride, rows_per_frame, weight, bias, row_offset, rotate=False):
     _gpu(x, shift, scale, weight, bias)
     if x.dtype != torch.bfloat16 or x.dim() != 2 or not x.is_contiguous():
         raise TypeError(f"layernorm_modulate_{fmt.name} expects a contiguous bf16 matrix")
@@ -517,10 +523,26 @@ def _layernorm_modulate_mx(fmt, x, eps, shift, scale, frame_stride, rows_per_fra
     if d % fmt.block:
         raise ValueError(f"layernorm_modulate_{fmt.name}: d must be a multiple of 32")
     codes, scales = _mx_out(fmt, M, d, x.device, None, None)
-    _lib.call("rtv_layernorm_modulate_" + fmt.name, _ptr(x), _ptr(codes), ctypes.c_int64(codes.stride(0)), _ptr(scales),
+    _lib.call("rtv_layernorm_modulate_" + fmt.name + ("_rot" if rotate else ""), _ptr(x), _ptr(codes), ctypes.c_int64(codes.stride(0)), _ptr(scales),
               ctypes.c_int64(scales.stride(0)), M, d, float(eps), _ptr(shift), _ptr(scale), int(frame_stride), int(rows_per_frame),
               int(row_offset), _ptr(weight), _ptr(bias), _stream())
     return codes, scales
+
+
+def _gate_in_bounds(gate, gate_stride, rows_per_frame, row_offset, M, N):
+    """The epilogue reads gate[((row_offset + m) // rows_per_frame) * gate_stride + n] for every row m < M and has no way to know
+    where the caller's table ends.  A table that ends in front of the last frame the rows address (a row offset that moves the last
+    rows past the last frame) would be read past its allocation: it is handed over in a copy that continues with zeros, so those
+    rows get a gate of 0.  A table that covers its rows - every call of the model - is passed as it is."""
+    if gate is None or int(rows_per_frame) <= 0:
+        return gate
+    need = ((int(row_offset) + M - 1) // int(rows_per_frame)) * int(gate_stride) + N
+    have = gate.untyped_storage().nbytes() // gate.element_size() - gate.storage_offset()
+    if have >= need:
+        return gate
+    padded = torch.zeros(need, dtype=gate.dtype, device=gate.device)
+    padded[:have] = torch.as_strided(gate, (have,), (1,))
+    return padded
 
 
 def _gemm_mx(fmt, a_codes, a_scales, w_codes, w_scales, bias, act, gate, gate_stride, rows_per_frame, residual, out, row_offset):
@@ -543,23 +565,26 @@ def _gemm_mx(fmt, a_codes, a_scales, w_codes, w_scales, bias, act, gate, gate_st
     if out is None:
         out = torch.empty((M, N), dtype=torch.bfloat16, device=a_codes.device)
     ensure_gemm_workspace(a_codes.device)
+    gate = _gate_in_bounds(gate, gate_stride, rows_per_frame, row_offset, M, N)
     _lib.call("rtv_" + who, _ptr(a_codes), a_codes.stride(0), _ptr(w_codes), w_codes.stride(0), _ptr(a_scales), _ptr(w_scales),
               _ptr(out), out.stride(0), M, N, K, _ptr(bias), int(act), _ptr(gate), int(gate_stride), int(rows_per_frame),
               int(row_offset), _ptr(residual), residual.stride(0) if residual is not None else 0, _stream())
     return out
 
 
-def quantize_mxfp4(x, codes=None, scales=None):
+def quantize_mxfp4(x, codes=None, scales=None, rotate_shift=None):
     """MXFP4 quantisation of a bf16 matrix [M, d], d % 32 == 0: returns (codes, scales), uint8 [M, d / 2] (two e2m1 codes per
-    byte, element 2j in the low nibble) and uint8 [M, RTV_MXFP4_SCALE_BYTES(d)] (e8m0 block scales in the header's order)."""
-    return _quantize_mx(_MXFP4, x, codes, scales)
+    byte, element 2j in the low nibble) and uint8 [M, RTV_MXFP4_SCALE_BYTES(d)] (e8m0 block scales in the header's order).
+    rotate_shift (None: no rotation): each block of 32 goes through the Hadamard butterflies of include/rtv_hip_mx_rotate.h and is
+    scaled by 2^-rotate_shift first (MX_ROT_ACT_SHIFT for activations, MX_ROT_WEIGHT_SHIFT for weights)."""
+    return _quantize_mx(_MXFP4, x, codes, scales, rotate_shift)
 
 
-def quantize_mxfp6(x, codes=None, scales=None):
+def quantize_mxfp6(x, codes=None, scales=None, rotate_shift=None):
     """MXFP6 quantisation of a bf16 matrix [M, d], d % 32 == 0: returns (codes, scales), uint8 [M, 3 d / 4] (e2m3 codes, a block of
     32 in 24 bytes, element j at bits [6 j, 6 j + 6)) and uint8 [M, RTV_MXFP6_SCALE_BYTES(d)] (e8m0 block scales in the header's
-    order)."""
-    return _quantize_mx(_MXFP6, x, codes, scales)
+    order).  rotate_shift: as for quantize_mxfp4."""
+    return _quantize_mx(_MXFP6, x, codes, scales, rotate_shift)
 
 
 def layernorm_modulate_mxfp4(x, eps=1e-6, shift=None, scale=None, frame_stride=0, rows_per_frame=0, weight=None, bias=None,
@@ -572,6 +597,20 @@ def layernorm_modulate_mxfp6(x, eps=1e-6, shift=None, scale=None, frame_stride=0
                              row_offset=0):
     """layernorm_modulate followed by quantize_mxfp6 on its bf16 result, in one kernel and bit for bit: returns (codes, scales)."""
     return _layernorm_modulate_mx(_MXFP6, x, eps, shift, scale, frame_stride, rows_per_frame, weight, bias, row_offset)
+
+
+def layernorm_modulate_mxfp4_rot(x, eps=1e-6, shift=None, scale=None, frame_stride=0, rows_per_frame=0, weight=None, bias=None,
+                                 row_offset=0):
+    """layernorm_modulate followed by quantize_mxfp4(rotate_shift=MX_ROT_ACT_SHIFT) on its bf16 result, in one kernel and bit for
+    bit: returns (codes, scales)."""
+    return _layernorm_modulate_mx(_MXFP4, x, eps, shift, scale, frame_stride, rows_per_frame, weight, bias, row_offset, rotate=True)
+
+
+def layernorm_modulate_mxfp6_rot(x, eps=1e-6, shift=None, scale=None, frame_stride=0, rows_per_frame=0, weight=None, bias=None,
+                                 row_offset=0):
+    """layernorm_modulate followed by quantize_mxfp6(rotate_shift=MX_ROT_ACT_SHIFT) on its bf16 result, in one kernel and bit for
+    bit: returns (codes, scales)."""
+    return _layernorm_modulate_mx(_MXFP6, x, eps, shift, scale, frame_stride, rows_per_frame, weight, bias, row_offset, rotate=True)
 
 
 def gemm_mxfp4(a_codes, a_scales, w_codes, w_scales, bias=None, act=ACT_NONE, gate=None, gate_stride=0, rows_per_frame=0,
