@@ -16,6 +16,7 @@
 #include "gemm_core.h"
 #include "rtv_common.h"
 #include "rtv_internal.h"
+#include "../../include/rtv_hip_t5_units.h"
 
 namespace rtv {
 
@@ -126,7 +127,10 @@ __global__ __launch_bounds__(64) void t5_attn_kernel(T5AttnParams p) {
   for (int dc = 0; dc < 4; ++dc) qf[dc] = *(const u32x4*)(qp + dc * 16);
   const bf16_t* kb = p.qk + p.da + h * 64 + g * 8;                       // + key * ld + dc * 16
   const bf16_t* vb = p.vt + (size_t)(h * 64 + l31) * p.rows + 4 * g;     // + db * 32 * rows + key0 + 16 s (+ 8)
-  const float* bias = p.bias + (size_t)h * (2 * p.max_len - 1) + (p.max_len - 1) - q_row;
+  // padding queries (q_row >= valid; their output is don't-care but must stay finite, the next layer's V^T holds it) look the
+  // table up as the last valid query: with valid <= max_len every index (max_len - 1) - bq + key then lies in [0, 2*max_len - 2]
+  const int bq = min(q_row, p.valid - 1);
+  const float* bias = p.bias + (size_t)h * (2 * p.max_len - 1) + (p.max_len - 1) - bq;
 
   f32x16 oacc[2];
 #pragma unroll
@@ -246,6 +250,90 @@ static int t5_gemm(const void* a, int lda, const void* w, int ldw, void* c, int 
   return rtv_gemm(a, lda, w, ldw, c, ldc, M, N, K, nullptr, 0, nullptr, 0, 0, 0, nullptr, 0, RTV_DTYPE_BF16, 0, s);
 }
 
+// The launches of the five kernels: rtv_t5_encode and the unit entry points of rtv_hip_t5_units.h both go through these, so the
+// grids and block sizes the tests see are the product's.  No argument checks here: the callers have made them.
+static int t5_ew_blocks(size_t n8) { return (int)((n8 + 255) / 256 > 4096 ? 4096 : (n8 + 255) / 256); }
+
+static int t5_launch_embed(const int* ids, const void* table, float* x, int rows, int valid, int dim, int vocab, hipStream_t st) {
+  hipLaunchKernelGGL(t5_embed_kernel, dim3(rows), dim3(128), 0, st, ids, (const bf16_t*)table, x, rows, valid, dim, vocab);
+  return check_launch("t5_embed");
+}
+
+static int t5_launch_rmsnorm(const float* x, const void* w, void* out, int rows, int dim, float eps, bool out_f32, hipStream_t st) {
+  if (out_f32)
+    hipLaunchKernelGGL(t5_rmsnorm_kernel<true>, dim3(rows), dim3(T5_THREADS), 0, st, x, (const bf16_t*)w, out, dim, eps);
+  else
+    hipLaunchKernelGGL(t5_rmsnorm_kernel<false>, dim3(rows), dim3(T5_THREADS), 0, st, x, (const bf16_t*)w, out, dim, eps);
+  return check_launch("t5_rmsnorm");
+}
+
+static int t5_launch_add(float* x, const void* y, size_t n8, hipStream_t st) {
+  hipLaunchKernelGGL(t5_add_kernel, dim3(t5_ew_blocks(n8)), dim3(256), 0, st, x, (const bf16_t*)y, n8);
+  return check_launch("t5_add");
+}
+
+static int t5_launch_geglu(const void* gf, void* h, int rows, int dff, hipStream_t st) {
+  hipLaunchKernelGGL(t5_geglu_kernel, dim3(t5_ew_blocks((size_t)rows * dff / 8)), dim3(256), 0, st, (const bf16_t*)gf, (bf16_t*)h,
+                     rows, dff);
+  return check_launch("t5_geglu");
+}
+
+static int t5_launch_attention(const void* qk, const void* vt, void* o, const void* bias, int rows, int valid, int H, int max_len,
+                               hipStream_t st) {
+  T5AttnParams ap{(const bf16_t*)qk, (const bf16_t*)vt, (bf16_t*)o, (const float*)bias, rows, valid, H * 64, H, max_len};
+  {
+    ProfScope prof(PROF_ATTN, st, 4.0 * rows * (double)valid * H * 64);
+    hipLaunchKernelGGL(t5_attn_kernel, dim3(rows / 32, H), dim3(64), 0, st, ap);
+  }
+  return check_launch("t5_attn");
+}
+
+static bool t5_misaligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
+
+extern "C" int rtv_t5_embed(const int* ids, const void* table, void* x, int rows, int valid, int dim, int vocab, rtv_stream_t stream) {
+  if (!ids || !table || !x) return set_error(-1, "t5_embed: null pointer");
+  if (rows <= 0 || valid < 0 || valid > rows) return set_error(-1, "t5_embed: need rows > 0 and 0 <= valid <= rows");
+  if (dim <= 0 || dim % 8 || vocab <= 0) return set_error(-1, "t5_embed: dim must be a positive multiple of 8 and vocab positive");
+  if (t5_misaligned(table, 16) || t5_misaligned(x, 16)) return set_error(-1, "t5_embed: table and x must be 16-byte aligned");
+  if (t5_misaligned(ids, 4)) return set_error(-1, "t5_embed: ids must be 4-byte aligned");
+  return t5_launch_embed(ids, table, (float*)x, rows, valid, dim, vocab, (hipStream_t)stream);
+}
+
+extern "C" int rtv_t5_rmsnorm(const void* x, const void* w, void* out, int rows, int dim, float eps, int out_f32, rtv_stream_t stream) {
+  if (!x || !w || !out) return set_error(-1, "t5_rmsnorm: null pointer");
+  if (rows <= 0 || dim <= 0 || dim % 4) return set_error(-1, "t5_rmsnorm: need rows > 0 and dim a positive multiple of 4");
+  if (out_f32 != 0 && out_f32 != 1) return set_error(-1, "t5_rmsnorm: out_f32 must be 0 or 1");
+  if (t5_misaligned(x, 16) || t5_misaligned(w, 2) || t5_misaligned(out, out_f32 ? 16 : 8))
+    return set_error(-1, "t5_rmsnorm: x must be 16-byte aligned, w 2-byte, out 16-byte (float32) or 8-byte (bf16)");
+  return t5_launch_rmsnorm((const float*)x, w, out, rows, dim, eps, out_f32 != 0, (hipStream_t)stream);
+}
+
+extern "C" int rtv_t5_add(void* x, const void* y, size_t n, rtv_stream_t stream) {
+  if (!x || !y) return set_error(-1, "t5_add: null pointer");
+  if (n == 0 || n % 8) return set_error(-1, "t5_add: n must be a positive multiple of 8");
+  if (t5_misaligned(x, 16) || t5_misaligned(y, 16)) return set_error(-1, "t5_add: x and y must be 16-byte aligned");
+  return t5_launch_add((float*)x, y, n / 8, (hipStream_t)stream);
+}
+
+extern "C" int rtv_t5_geglu(const void* gf, void* h, int rows, int dff, rtv_stream_t stream) {
+  if (!gf || !h) return set_error(-1, "t5_geglu: null pointer");
+  if (rows <= 0 || dff <= 0 || dff % 8) return set_error(-1, "t5_geglu: need rows > 0 and dff a positive multiple of 8");
+  if (t5_misaligned(gf, 16) || t5_misaligned(h, 16)) return set_error(-1, "t5_geglu: gf and h must be 16-byte aligned");
+  return t5_launch_geglu(gf, h, rows, dff, (hipStream_t)stream);
+}
+
+extern "C" int rtv_t5_attention(const void* qk, const void* vt, void* o, const void* bias, int rows, int valid, int num_heads,
+                                int max_len, rtv_stream_t stream) {
+  if (!qk || !vt || !o || !bias) return set_error(-1, "t5_attention: null pointer");
+  if (rows <= 0 || rows % 32) return set_error(-1, "t5_attention: rows must be a positive multiple of 32");
+  if (valid <= 0 || valid > rows || valid > max_len)
+    return set_error(-1, "t5_attention: need 0 < valid <= rows and valid <= max_len (the bias table's length)");
+  if (num_heads <= 0 || num_heads > 65535) return set_error(-1, "t5_attention: num_heads must be in 1 .. 65535");
+  if (t5_misaligned(qk, 16) || t5_misaligned(vt, 8) || t5_misaligned(o, 8) || t5_misaligned(bias, 4))
+    return set_error(-1, "t5_attention: qk must be 16-byte aligned, vt and o 8-byte, bias 4-byte");
+  return t5_launch_attention(qk, vt, o, bias, rows, valid, num_heads, max_len, (hipStream_t)stream);
+}
+
 extern "C" int rtv_t5_encode(const rtv_t5_config* cfg, const rtv_t5_weights* w, const int* ids, int seq_len, int out_rows,
                              void* workspace, size_t workspace_bytes, void* out, rtv_stream_t stream) {
   if (!cfg || !w || !ids || !workspace || !out) return set_error(-1, "t5_encode: null argument");
@@ -262,45 +350,24 @@ extern "C" int rtv_t5_encode(const rtv_t5_config* cfg, const rtv_t5_weights* w, 
   if (!ok) return set_error(-1, "t5_encode: workspace too small (see rtv_t5_workspace_bytes)");
   hipStream_t st = (hipStream_t)stream;
   const size_t n8 = (size_t)rows * d / 8;
-  const int ew_blocks = (int)((n8 + 255) / 256 > 4096 ? 4096 : (n8 + 255) / 256);
 
-  hipLaunchKernelGGL(t5_embed_kernel, dim3(rows), dim3(128), 0, st, ids, (const bf16_t*)w->token_embedding, b.x, rows, seq_len,
-                     d, cfg->vocab);
-  T5_TRY(check_launch("t5_embed"));
+  T5_TRY(t5_launch_embed(ids, w->token_embedding, b.x, rows, seq_len, d, cfg->vocab, st));
   for (int l = 0; l < cfg->num_layers; ++l) {
     const rtv_t5_layer_weights& lw = w->layers[l];
-    hipLaunchKernelGGL(t5_rmsnorm_kernel<false>, dim3(rows), dim3(T5_THREADS), 0, st, b.x, (const bf16_t*)lw.norm1_w, b.xn, d,
-                       cfg->eps);
-    T5_TRY(check_launch("t5_rmsnorm"));
+    T5_TRY(t5_launch_rmsnorm(b.x, lw.norm1_w, b.xn, rows, d, cfg->eps, false, st));
     T5_TRY(t5_gemm(b.xn, d, lw.qk_w, d, b.qk, 2 * da, rows, 2 * da, d, stream));        // q | k
     T5_TRY(t5_gemm(lw.v_w, d, b.xn, d, b.vt, rows, da, rows, d, stream));                // V^T = W_v . n^T
-    T5AttnParams ap{b.qk, b.vt, b.ao, (const float*)lw.pos_bias, rows, seq_len, da, H, w->max_len};
-    {
-      ProfScope prof(PROF_ATTN, st, 4.0 * rows * (double)seq_len * da);
-      hipLaunchKernelGGL(t5_attn_kernel, dim3(rows / 32, H), dim3(64), 0, st, ap);
-    }
-    T5_TRY(check_launch("t5_attn"));
+    T5_TRY(t5_launch_attention(b.qk, b.vt, b.ao, lw.pos_bias, rows, seq_len, H, w->max_len, st));
     T5_TRY(t5_gemm(b.ao, da, lw.o_w, da, b.tmp, d, rows, d, da, stream));
-    hipLaunchKernelGGL(t5_add_kernel, dim3(ew_blocks), dim3(256), 0, st, b.x, b.tmp, n8);
-    T5_TRY(check_launch("t5_add"));
-    hipLaunchKernelGGL(t5_rmsnorm_kernel<false>, dim3(rows), dim3(T5_THREADS), 0, st, b.x, (const bf16_t*)lw.norm2_w, b.xn, d,
-                       cfg->eps);
-    T5_TRY(check_launch("t5_rmsnorm"));
+    T5_TRY(t5_launch_add(b.x, b.tmp, n8, st));
+    T5_TRY(t5_launch_rmsnorm(b.x, lw.norm2_w, b.xn, rows, d, cfg->eps, false, st));
     T5_TRY(t5_gemm(b.xn, d, lw.gate_fc1_w, d, b.gf, 2 * dff, rows, 2 * dff, d, stream));  // gate | fc1
-    {
-      const size_t tot = (size_t)rows * dff / 8;
-      const int blocks = (int)((tot + 255) / 256 > 4096 ? 4096 : (tot + 255) / 256);
-      hipLaunchKernelGGL(t5_geglu_kernel, dim3(blocks), dim3(256), 0, st, b.gf, b.h, rows, dff);
-      T5_TRY(check_launch("t5_geglu"));
-    }
+    T5_TRY(t5_launch_geglu(b.gf, b.h, rows, dff, st));
     T5_TRY(t5_gemm(b.h, dff, lw.fc2_w, dff, b.tmp, d, rows, d, dff, stream));
-    hipLaunchKernelGGL(t5_add_kernel, dim3(ew_blocks), dim3(256), 0, st, b.x, b.tmp, n8);
-    T5_TRY(check_launch("t5_add"));
+    T5_TRY(t5_launch_add(b.x, b.tmp, n8, st));
   }
   // final norm on the prompt's rows; padding rows of the output are zero (wan_wrapper.py:52-53)
-  hipLaunchKernelGGL(t5_rmsnorm_kernel<true>, dim3(seq_len), dim3(T5_THREADS), 0, st, b.x, (const bf16_t*)w->final_norm_w, out, d,
-                     cfg->eps);
-  T5_TRY(check_launch("t5_rmsnorm"));
+  T5_TRY(t5_launch_rmsnorm(b.x, w->final_norm_w, out, seq_len, d, cfg->eps, true, st));
   if (out_rows > seq_len) {
     hipError_t e = hipMemsetAsync((float*)out + (size_t)seq_len * d, 0, (size_t)(out_rows - seq_len) * d * 4, st);
     if (e != hipSuccess) return set_error(e, "t5_encode: hipMemsetAsync");

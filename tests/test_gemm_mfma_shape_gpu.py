@@ -60,6 +60,24 @@ def test_gemm_exact_integer_product(ops, M, N, K):
         assert torch.equal(out, ref), (cfg, int((out != ref).sum()))
 
 
+@pytest.mark.parametrize("M,N,K", [(128, 32, 256), (256, 96, 64), (4096, 32, 4096)])
+def test_gemm_exact_integer_product_value_projection(ops, M, N, K):
+    """The text encoder's value projection V^T = W_v . n^T (t5_encoder.hip): A is the weight [dim_attn, dim], W the normed rows
+    [rows, dim], the output [dim_attn, rows] with ldc = rows - N as small as 32, where every other GEMM test starts at 64.  The
+    same integer-exact product, every tile config; at K = 4096 the 256 non-zero K columns are spread over the whole depth.  K = 64 is
+    one K tile: the 160x256 kernel (tile configs 9 and 19, which the default dispatch takes from K = 1024 on only) needs two and
+    says so instead of computing."""
+    a, w, ref = _integer_problem(M, N, min(K, 256), K if K > 256 else 0)
+    assert a.shape == (M, K) and w.shape == (N, K)
+    for cfg in CFGS:
+        if K < 128 and cfg in (9, 19):
+            with pytest.raises(RuntimeError, match="gemm5: K must be a multiple of 64, >= 128"):
+                ops.gemm(a, w, tile_cfg=cfg)
+            continue
+        out = ops.gemm(a, w, tile_cfg=cfg)
+        assert out.stride(0) == N and torch.equal(out, ref), (cfg, int((out != ref).sum()))
+
+
 def _direct_epilogue_out(M, N):
     """an output whose rows are 8 bytes off 16-byte alignment: the kernels take the direct register-layout epilogue (no LDS image)"""
     return torch.empty(M, N + 8, dtype=torch.bfloat16, device=DEV)[:, 4:4 + N]
