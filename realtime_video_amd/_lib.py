@@ -4,7 +4,7 @@ puts on the library) and ABI_VERSION are parsed from the headers at import; noth
 include/rtv_hip_io.h, is parsed the same way into tables of its own (IO_STRUCTS / IO_PROTOTYPES) until it is folded into rtv_hip.h,
 and so are the frame delivery side, include/rtv_hip_jpeg.h (JPEG_STRUCTS / JPEG_PROTOTYPES), and the JPEG frame decoder,
 include/rtv_hip_jpeg_decode.h (JPEGDEC_STRUCTS / JPEGDEC_PROTOTYPES), and the LoRA merge, include/rtv_hip_lora.h (LORA_STRUCTS /
-LORA_PROTOTYPES), and the folded text cross-attention, include/rtv_hip_cross_fold.h (CROSS_FOLD_PROTOTYPES), and the fp8 Linears
+LORA_PROTOTYPES), with its dense-delta and DoRA forms, include/rtv_hip_lora_ext.h (LORA_EXT_STRUCTS / LORA_EXT_PROTOTYPES), and the folded text cross-attention, include/rtv_hip_cross_fold.h (CROSS_FOLD_PROTOTYPES), and the fp8 Linears
 with per-row scales, include/rtv_hip_fp8_rows.h (FP8_ROWS_PROTOTYPES), and the fp8 self-attention on an e4m3 shadow of the KV cache,
 include/rtv_hip_attn_fp8.h (ATTN_FP8_STRUCTS / ATTN_FP8_PROTOTYPES), and the MXFP4 Linears, include/rtv_hip_mxfp4.h (MXFP4_PROTOTYPES), and the MXFP6
 Linears, include/rtv_hip_mxfp6.h (MXFP6_PROTOTYPES), and the block Hadamard rotation in front of both quantisers,
@@ -122,6 +122,10 @@ LORA_HEADER = "rtv_hip_lora.h"   # LoRA adapters merged into the DiT's weights i
 LORA_STRUCTS = dict(STRUCTS)
 LORA_PROTOTYPES = parse_header(_read(LORA_HEADER), LORA_STRUCTS)
 LORA_STRUCTS = {k: v for k, v in LORA_STRUCTS.items() if k not in STRUCTS}
+LORA_EXT_HEADER = "rtv_hip_lora_ext.h"   # dense-delta and DoRA merges: the term struct stays out of STRUCTS and of LORA_STRUCTS
+LORA_EXT_STRUCTS = dict(STRUCTS)
+LORA_EXT_PROTOTYPES = parse_header(_read(LORA_EXT_HEADER), LORA_EXT_STRUCTS)
+LORA_EXT_STRUCTS = {k: v for k, v in LORA_EXT_STRUCTS.items() if k not in STRUCTS}
 CROSS_FOLD_HEADER = "rtv_hip_cross_fold.h"   # the folded text cross-attention: three entry points, no struct of its own
 CROSS_FOLD_STRUCTS = dict(STRUCTS)
 CROSS_FOLD_PROTOTYPES = parse_header(_read(CROSS_FOLD_HEADER), CROSS_FOLD_STRUCTS)
@@ -181,7 +185,7 @@ def load():
             f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C realtime_video_amd/csrc`). There is no CPU fallback for the HIP path.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(IO_PROTOTYPES.items()) + list(JPEG_PROTOTYPES.items()) + list(JPEGDEC_PROTOTYPES.items()) + list(LORA_PROTOTYPES.items()) + list(CROSS_FOLD_PROTOTYPES.items()) + list(FP8_ROWS_PROTOTYPES.items()) + list(ATTN_FP8_PROTOTYPES.items()) + list(MXFP4_PROTOTYPES.items()) + list(MXFP6_PROTOTYPES.items()) + list(MX_ROTATE_PROTOTYPES.items()) + list(T5_UNITS_PROTOTYPES.items()):
+    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(IO_PROTOTYPES.items()) + list(JPEG_PROTOTYPES.items()) + list(JPEGDEC_PROTOTYPES.items()) + list(LORA_PROTOTYPES.items()) + list(LORA_EXT_PROTOTYPES.items()) + list(CROSS_FOLD_PROTOTYPES.items()) + list(FP8_ROWS_PROTOTYPES.items()) + list(ATTN_FP8_PROTOTYPES.items()) + list(MXFP4_PROTOTYPES.items()) + list(MXFP6_PROTOTYPES.items()) + list(MX_ROTATE_PROTOTYPES.items()) + list(T5_UNITS_PROTOTYPES.items()):
         fn = getattr(lib, name, None)
         if fn is None:
             # RTV_LIB_PATH = an older build of the same C ABI (A/B measurements): entry points added since are simply absent

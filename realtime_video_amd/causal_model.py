@@ -150,11 +150,12 @@ class CausalWanModel:
         self._weights_version = 0     # part of the graph key: a captured graph embeds weight pointers and the launch sequence
         self._cfg = _Cfg(dim, ffn_dim, num_heads, num_layers, freq_dim, text_dim, text_len, in_dim, out_dim, eps, 0, 0)
         self._lora = {}               # name -> {"scale": float, "targets": {target: lora.Target with A / B on the device}}, in load order
-        self._lora_base = {}          # _tensors key -> bf16 copy of the matrix as loaded; kept outside _tensors / parameters()
+        self._lora_base = {}          # _tensors key -> bf16 copy of the tensor as loaded; kept outside _tensors / parameters()
+        self._lora_dora_ws = None     # the DoRA merge's row-norm partials, sized once for the largest Linear
         self._fp8_attn = None         # (k_scale, v_scale, epoch) while enable_fp8_attention() is on
         self._fp8_attn_epoch = 0      # bumps at every enable / disable: a shadow filled before it is refilled from the bf16 cache
         self._fp8_attn_amax = None    # float32 [num_layers, 2], allocated once
-        self.lora_version = 0         # bumps when a merge changes ck_w / cv_w / co_w: crossattn_cache entries carry the one they were made with
+        self.lora_version = 0         # bumps when a merge changes ck / cv / co (weight or bias) or cnorm_k_w: crossattn_cache entries carry the one they were made with
 
     # ------------------------------------------------------------------ nn.Module-ish conveniences
     def eval(self):
@@ -296,6 +297,7 @@ class CausalWanModel:
         self._cfg.use_fp8 = _BF16           # (a reload replaces quantised weights; enable_fp8() again to re-quantise)
         if self._lora or self._lora_base:
             self._lora, self._lora_base = {}, {}      # adapters belong to the weights they were merged into
+            self._lora_dora_ws = None
             self.lora_version += 1
         self._graphs.clear()            # captured graphs point at the previous weights
         self._weights_version += 1
@@ -546,13 +548,18 @@ class CausalWanModel:
         """{name: scale} of the loaded adapters, in load order."""
         return {name: ad["scale"] for name, ad in self._lora.items()}
 
-    def load_lora(self, sd, scale=1.0, name=None, strict=True):
+    def load_lora(self, sd, scale=1.0, name=None, strict=True, extended=False):
         """Merge a LoRA state dict (lora.parse_lora_state_dict names the accepted keys) into the weights IN PLACE, at strength
         `scale`; returns the adapter's name.  The first adapter that touches a matrix keeps a bf16 copy of it (the base); every
         change re-merges each touched matrix from its base with all adapters on it, so results never depend on history.  Weight
         pointers do not move: captured hipGraphs stay valid.  Load adapters BEFORE enable_fp8(): afterwards the bf16 weights are gone.
-        (A device bf16 tensor that load_state_dict kept without a copy is shared with the caller's state dict and changes with it.)"""
-        targets, _ = lora.parse_lora_state_dict(sd, self.state_dict_shapes(), strict=strict)
+        (A device bf16 tensor that load_state_dict kept without a copy is shared with the caller's state dict and changes with it.)
+
+        extended=True (opt-in) takes the kohya / diffusers key styles, every Linear of the model, `.diff` / `.diff_b` deltas (biases
+        and norm weights get base copies like matrices) and DoRA magnitude vectors (lora._parse_extended).  DoRA is not additive:
+        a row range (q, k and v of a layer are separate ranges) holds either one DoRA adapter or additive ones, and loading one
+        kind onto a range that holds the other raises a ValueError before anything is changed."""
+        targets, _ = lora.parse_lora_state_dict(sd, self.state_dict_shapes(), strict=strict, extended=extended)
         scale = float(scale)
         if scale != scale or scale in (float("inf"), float("-inf")):
             raise ValueError("load_lora: scale must be finite")
@@ -571,14 +578,42 @@ class CausalWanModel:
             raise RuntimeError("load weights before load_lora()")
         if self._cfg.use_fp8:
             raise RuntimeError("load_lora after enable_fp8() / enable_mxfp4() / enable_mxfp6(): the bf16 weights are gone - load adapters first, then enable the mode")
+        held = {}          # weight range -> [(adapter, it is a DoRA adapter there)]
+        for other, ad in self._lora.items():
+            for tg in ad["targets"].values():
+                if tg.rank or tg.diff is not None:
+                    held.setdefault((tg.tensor, tg.row0, tg.rows), []).append((other, tg.dora is not None))
+        for t, tg in targets.items():
+            if tg.rank == 0 and tg.diff is None:
+                continue                # (a diff_b alone: the bias is another range)
+            for other, is_dora in held.get((tg.tensor, tg.row0, tg.rows), []):
+                if is_dora or tg.dora is not None:
+                    which = name if tg.dora is not None else other
+                    raise ValueError(f"load_lora: {name!r} and {other!r} both touch {t}, and {which!r} is a DoRA adapter there: the "
+                                     "DoRA merge is not additive, a row range with one carries no other adapter")
         dev, bf = self.device, torch.bfloat16
-        on_dev = {t: tg._replace(A=tg.A.detach().to(device=dev, dtype=bf).contiguous(),
-                                 B=tg.B.detach().to(device=dev, dtype=bf).contiguous()) for t, tg in targets.items()}
+
+        def put(x):
+            return None if x is None else x.detach().to(device=dev, dtype=bf).contiguous()
+
+        on_dev = {t: tg._replace(A=put(tg.A), B=put(tg.B), diff=put(tg.diff), diff_b=put(tg.diff_b), dora=put(tg.dora))
+                  for t, tg in targets.items()}
+        touched = set()
         for tg in on_dev.values():
-            if tg.tensor not in self._lora_base:
-                self._lora_base[tg.tensor] = self._tensors[tg.tensor].clone()
+            if tg.rank or tg.diff is not None:
+                touched.add(tg.tensor)
+            if tg.diff_b is not None:
+                touched.add(tg.bias)
+        if any(tg.dora is not None for tg in on_dev.values()) and self._lora_dora_ws is None:
+            # once per model, for the largest Linear it has (a few bytes per row and 128 columns): no merge allocates
+            need = max(lora.dora_workspace_bytes(v.shape[0], v.shape[1]) for k, v in self._tensors.items()
+                       if k.endswith("_w") and v.ndim == 2)
+            self._lora_dora_ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        for key in touched:
+            if key not in self._lora_base:
+                self._lora_base[key] = self._tensors[key].clone()
         self._lora[name] = {"scale": scale, "targets": on_dev}
-        self._remerge({tg.tensor for tg in on_dev.values()})
+        self._remerge(touched)
         return name
 
     def set_lora_scale(self, name, scale):
@@ -589,7 +624,7 @@ class CausalWanModel:
         if scale != scale or scale in (float("inf"), float("-inf")):
             raise ValueError("set_lora_scale: scale must be finite")
         self._lora[name]["scale"] = scale
-        self._remerge({tg.tensor for tg in self._lora[name]["targets"].values()})
+        self._remerge(self._lora_touched(self._lora[name]))
 
     def unload_lora(self, name=None):
         """Drop one adapter (None: all of them).  A matrix no adapter targets any more is restored bit for bit and its base freed."""
@@ -597,40 +632,70 @@ class CausalWanModel:
             raise KeyError(f"no LoRA adapter named {name!r} (loaded: {list(self._lora)})")
         touched = set()
         for n in [name] if name is not None else list(self._lora):
-            touched |= {tg.tensor for tg in self._lora.pop(n)["targets"].values()}
+            touched |= self._lora_touched(self._lora.pop(n))
         self._remerge(touched)
 
+    @staticmethod
+    def _lora_touched(adapter):
+        """_tensors keys an adapter changes: weights (low-rank, diff, DoRA; norm weights) and the vectors of its diff_b terms."""
+        tgs = adapter["targets"].values()
+        return {tg.tensor for tg in tgs if tg.rank or tg.diff is not None} | {tg.bias for tg in tgs if tg.diff_b is not None}
+
     def _remerge(self, keys):
-        """Rebuild the matrices `keys` from their bases with every adapter on them: one rtv_lora_merge per matrix, per q / k / v
-        row block of a fused qkv_w.  bf16: into the live weight, in place.  fp8: into a temporary bf16 matrix, re-quantised with
-        enable_fp8's routine into the existing e4m3 buffer; its scale is replaced (per-row scales: refreshed in their device tensor) and the
-        graphs, which may hold it by value, go.  MXFP4 / MXFP6: the same with that mode's quantiser, codes and block scales in place."""
-        fp8, cross = bool(self._cfg.use_fp8), False
+        """Rebuild the tensors `keys` from their bases with every adapter on them: one rtv_lora_merge_ex per matrix, per vector (as
+        [1, K]) and per q / k / v block of a fused qkv_w / qkv_b, carrying all live adapters (low-rank terms only: the bits of
+        rtv_lora_merge); one rtv_lora_merge_dora per range that holds a DoRA adapter.  bf16: into the live tensor, in place.  fp8,
+        for a tensor the mode holds quantised: into a temporary bf16 matrix, re-quantised with enable_fp8's routine into the existing
+        e4m3 buffer; its scale is replaced (per-row scales: refreshed in their device tensor) and the graphs, which may hold it by
+        value, go.  MXFP4 / MXFP6: the same with that mode's quantiser, codes and block scales in place.  Biases and norm weights
+        stay bf16 in every mode and are merged in place."""
+        cross, requantised = False, False
+        live = {}          # _tensors key -> {(start, n): [(target, scale, its diff for this tensor)]}, adapters in load order
+        for ad in self._lora.values():
+            for tg in ad["targets"].values():
+                if tg.rank or tg.diff is not None:
+                    block = (0, tg.cols) if self._tensors[tg.tensor].ndim == 1 else (tg.row0, tg.rows)      # (1-D: a norm weight)
+                    live.setdefault(tg.tensor, {}).setdefault(block, []).append((tg, ad["scale"], tg.diff))
+                if tg.diff_b is not None:
+                    live.setdefault(tg.bias, {}).setdefault((tg.bias0, tg.bias_n), []).append((tg, ad["scale"], tg.diff_b))
         for key in sorted(keys):
             base = self._lora_base[key]
-            live = [(ad["scale"], tg) for ad in self._lora.values() for tg in ad["targets"].values() if tg.tensor == key]
-            out = torch.empty_like(base) if fp8 else self._tensors[key]
-            blocks = ((0, base.shape[0]),) if not key.endswith(".qkv_w") else tuple((j * self.dim, self.dim) for j in range(3))
-            for row0, rows in blocks:
-                lora.merge(base[row0:row0 + rows], out[row0:row0 + rows],
-                           [(tg.A, tg.B, s * tg.factor) for s, tg in live if (tg.row0, tg.rows) == (row0, rows)])
-            if self._cfg.use_fp8 in _MX_MODES:
+            quantised = bool(self._cfg.use_fp8) and (key in _FP8_TOP or (key.startswith("L") and key.split(".")[-1] in _FP8_LAYER))
+            out = torch.empty_like(base) if quantised else self._tensors[key]
+            vector = base.ndim == 1
+            blocks = ((0, base.shape[0]),) if not key.endswith((".qkv_w", ".qkv_b")) else tuple((j * self.dim, self.dim) for j in range(3))
+            for start, n in blocks:
+                b_, o_ = base[start:start + n], out[start:start + n]
+                on = live.get(key, {}).get((start, n), [])
+                if vector:
+                    lora.merge_ex(b_.unsqueeze(0), o_.unsqueeze(0), [(None, None, 0.0, d.unsqueeze(0), s) for _, s, d in on])
+                elif any(tg.dora is not None for tg, _, _ in on):
+                    (tg, strength, _), = on          # (load_lora refuses a second adapter on a DoRA range)
+                    lora.merge_dora(b_, o_, tg.A, tg.B, tg.factor, tg.dora, strength, self._lora_dora_ws)
+                else:
+                    lora.merge_ex(b_, o_, [(tg.A, tg.B, s * tg.factor, d, s) for tg, s, d in on])
+            if quantised and self._cfg.use_fp8 in _MX_MODES:
                 # the quantiser of _enable_mx (and of the forward), into the existing code and scale tensors: the weight table and
                 # rtv_dit_weights.fp8_row_scales keep pointing at them
                 _MX_MODES[self._cfg.use_fp8][2](out, codes=self._tensors[key], scales=self._mx_scales[key])
-            elif self._cfg.use_fp8 == _FP8_ROWS:
+            elif quantised and self._cfg.use_fp8 == _FP8_ROWS:
                 q, rs = self._quantize_fp8_rows(out)
                 self._tensors[key].copy_(q)
                 self._fp8_row_scales[key].copy_(rs)      # in place: rtv_dit_weights.fp8_row_scales keeps pointing at it
-            elif fp8:
+            elif quantised:
                 q, s = self._quantize_fp8(out)
                 self._tensors[key].copy_(q)
-                layer, field = key[1:].split(".")
-                self._fp8_scales[len(_FP8_TOP) + len(_FP8_LAYER) * int(layer) + _FP8_LAYER.index(field)] = s
-            if not live:
+                if key in _FP8_TOP:
+                    self._fp8_scales[_FP8_TOP.index(key)] = s
+                else:
+                    layer, field = key[1:].split(".")
+                    self._fp8_scales[len(_FP8_TOP) + len(_FP8_LAYER) * int(layer) + _FP8_LAYER.index(field)] = s
+            requantised = requantised or quantised
+            if key not in live:
                 del self._lora_base[key]
-            cross = cross or key.endswith((".ck_w", ".cv_w", ".co_w"))      # (co_w: the folded V . Wo^T lives with the caches)
-        if fp8 and keys:
+            # (co_w: the folded V . Wo^T lives with the caches; cnorm_k_w and the k / v biases shape the cached text K / V rows)
+            cross = cross or key.endswith((".ck_w", ".cv_w", ".co_w", ".ck_b", ".cv_b", ".co_b", ".cnorm_k_w"))
+        if requantised:
             self._graphs.clear()
             self._weights_version += 1
         if cross:

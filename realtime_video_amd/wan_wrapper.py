@@ -84,8 +84,8 @@ class WanDiffusionWrapper:
         return self
 
     # ---- LoRA adapters: the model's methods (causal_model.py)
-    def load_lora(self, sd, scale=1.0, name=None, strict=True):
-        return self.model.load_lora(sd, scale=scale, name=name, strict=strict)
+    def load_lora(self, sd, scale=1.0, name=None, strict=True, extended=False):
+        return self.model.load_lora(sd, scale=scale, name=name, strict=strict, extended=extended)
 
     def set_lora_scale(self, name, scale):
         return self.model.set_lora_scale(name, scale)

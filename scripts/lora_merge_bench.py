@@ -13,6 +13,18 @@ used: every matrix has a base copy, as in CausalWanModel) - over the buffers of 
 traffic as copies.
 
     python scripts/lora_merge_bench.py [--iters 10] [--rounds 5] [--out profiles/r12_lora_merge.json]
+
+--ext: the extended merges (include/rtv_hip_lora_ext.h) instead, into --ext-out (profiles/r19_lora_ext.json).  Per matrix shape and
+rank 16 / 64, alternating in every round on the same buffers:
+  * merge         = rtv_lora_merge with one adapter (the kernel the extended ones are measured against),
+  * ex_lowrank    = rtv_lora_merge_ex with the same pair and no diff (the same arithmetic through the new kernel),
+  * ex_diff       = rtv_lora_merge_ex with the pair and a dense [N, K] diff (reads 2 N K bytes more),
+  * ex_diff_only  = rtv_lora_merge_ex with the diff alone,
+  * dora          = rtv_lora_merge_dora (two launches: base and the low-rank operands are read twice),
+  * copy          = W.copy_(base).
+The diffs rotate through the pool like the bases, so they stream from HBM too.  No threshold: the numbers are recorded.
+
+    python scripts/lora_merge_bench.py --ext [--iters 10] [--rounds 5] [--ext-out profiles/r19_lora_ext.json]
 """
 import argparse
 import json
@@ -57,16 +69,58 @@ def rnd(*shape, std):
     return (std * torch.randn(*shape, device="cuda", dtype=torch.float32)).to(BF)
 
 
+def extended(args, lora):
+    result = {"device": torch.cuda.get_device_name(0), "iters": args.iters, "rounds": args.rounds, "shapes": []}
+    for N, K in SHAPES:
+        pool = max(2, -(-(1 << 30) // (4 * N * K)))
+        bases = [rnd(N, K, std=0.02) for _ in range(pool)]
+        diffs = [rnd(N, K, std=0.01) for _ in range(pool)]
+        outs = [torch.empty(N, K, dtype=BF, device="cuda") for _ in range(pool)]
+        ws = torch.empty(lora.dora_workspace_bytes(N, K), dtype=torch.uint8, device="cuda")
+        mag = (bases[0].float().norm(dim=1)).to(BF)
+        for rank in RANKS[:2]:
+            A, B = rnd(rank, K, std=0.05), rnd(N, rank, std=0.05)
+            runs = interleaved({
+                "merge": lambda i: lora.merge(bases[i % pool], outs[i % pool], [(A, B, 0.7)]),
+                "ex_lowrank": lambda i: lora.merge_ex(bases[i % pool], outs[i % pool], [(A, B, 0.7, None, 0.0)]),
+                "ex_diff": lambda i: lora.merge_ex(bases[i % pool], outs[i % pool], [(A, B, 0.7, diffs[i % pool], 0.7)]),
+                "ex_diff_only": lambda i: lora.merge_ex(bases[i % pool], outs[i % pool], [(None, None, 0.0, diffs[i % pool], 0.7)]),
+                "dora": lambda i: lora.merge_dora(bases[i % pool], outs[i % pool], A, B, 0.5, mag, 0.7, ws),
+                "copy": lambda i: outs[i % pool].copy_(bases[i % pool])}, args.iters, args.rounds)
+            med = {k: statistics.median(v) for k, v in runs.items()}
+            nk = float(N) * K
+            moved = {"merge": 4 * nk, "ex_lowrank": 4 * nk, "ex_diff": 6 * nk, "ex_diff_only": 6 * nk, "dora": 6 * nk, "copy": 4 * nk}
+            row = {"N": N, "K": K, "rank": rank, "pool": pool}
+            for k in runs:
+                row[k + "_ms"] = med[k]
+                row[k + "_gbps"] = moved[k] / med[k] / 1e6
+                if k != "merge":
+                    row[k + "_over_merge"] = med[k] / med["merge"]
+            row["rounds_ms"] = runs
+            result["shapes"].append(row)
+            print(json.dumps({k: v for k, v in row.items() if k != "rounds_ms"}), flush=True)
+        del bases, diffs, outs
+    os.makedirs(os.path.dirname(os.path.abspath(args.ext_out)), exist_ok=True)
+    with open(args.ext_out, "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")
+    print("wrote", args.ext_out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--layers", type=int, default=2, help="layers' worth of buffers the whole-model pass rotates over")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r12_lora_merge.json"))
+    ap.add_argument("--ext", action="store_true", help="time rtv_lora_merge_ex / rtv_lora_merge_dora beside rtv_lora_merge instead")
+    ap.add_argument("--ext-out", default=os.path.join(ROOT, "profiles", "r19_lora_ext.json"))
     args = ap.parse_args()
     assert torch.cuda.is_available(), "lora_merge_bench needs a GPU"
     from realtime_video_amd import lora
     torch.manual_seed(0)
+    if args.ext:
+        return extended(args, lora)
     result = {"device": torch.cuda.get_device_name(0), "iters": args.iters, "rounds": args.rounds, "shapes": []}
     for N, K in SHAPES:
         pool = max(2, -(-(1 << 30) // (4 * N * K)))          # a pass over the pool reads + writes more than 1 GiB
