@@ -155,6 +155,10 @@ class CausalWanModel:
         self._fp8_attn = None         # (k_scale, v_scale, epoch) while enable_fp8_attention() is on
         self._fp8_attn_epoch = 0      # bumps at every enable / disable: a shadow filled before it is refilled from the bf16 cache
         self._fp8_attn_amax = None    # float32 [num_layers, 2], allocated once
+        self._fp8_attn_smooth = False       # enable_fp8_attention(smooth_k=True): the K codes of the shadows are those of k - centre
+        self._fp8_attn_center = None        # float32 [num_layers, H, 128], zero-filled, allocated once; fp8_attention_recenter() writes it
+        self._fp8_attn_center_ws = None     # workspace of the mean kernel, allocated with the centre
+        self._fp8_attn_center_epoch = 0     # bumps at every recentre: part of a shadow's "fp8_filled" state, like the scales
         self.lora_version = 0         # bumps when a merge changes ck / cv / co (weight or bias) or cnorm_k_w: crossattn_cache entries carry the one they were made with
 
     # ------------------------------------------------------------------ nn.Module-ish conveniences
@@ -438,7 +442,7 @@ class CausalWanModel:
         ops.ensure_gemm_workspace(self.device)
         return self
 
-    def enable_fp8_attention(self, k_scale=1.0, v_scale=1.0):
+    def enable_fp8_attention(self, k_scale=1.0, v_scale=1.0, smooth_k=False):
         """Opt-in: self-attention in the precision of the reference's SageAttention backend (wan/modules/sage.py: 8-bit Q K^T, fp8
         P V) on an OCP e4m3 shadow of the KV cache (include/rtv_hip_attn_fp8.h).  Independent of enable_fp8(), which concerns the
         Linears; cross-attention and the VAE stay as they are.  K / V codes are e4m3(x / scale) with one scale per tensor kind, Q is
@@ -454,6 +458,17 @@ class CausalWanModel:
         input, so 1.0 is the expected setting - but nobody has checked this on the real checkpoint, because none is available
         offline: look at fp8_attention_amax() after the first blocks.
 
+        smooth_k=True (opt-in; include/rtv_hip_attn_fp8_center.h): the K codes are e4m3((k - c) / k_scale) with one fp32 centre c per
+        layer, head and channel - the step SageAttention takes before it quantises K.  Every score of a query moves by the same
+        q . c, which softmax removes, so the attention kernel is unchanged and ANY fixed c is exact; a c close to the channel means
+        keeps keys that carry per-channel offsets (RMSNorm weights, slowly rotating RoPE pairs) from spending e4m3's three
+        mantissa bits on the offset.  The model owns the centres, one float32 [num_layers, H, 128] tensor, allocated zero-filled -
+        with the mean kernel's workspace - by the forward that allocates the shadows: until the first fp8_attention_recenter() the
+        mode computes bit for bit what smooth_k=False computes.  fp8_attention_recenter(kv_cache) sets them to the column means of
+        the cached keys, in place (captured hipGraphs hold the buffer's address and stay valid), and the next forward refills
+        the shadows; GenerationSession does it once, behind its first block.  The centres outlive disable / enable.  Measured on
+        synthetic keys and synthetic weights only: no real checkpoint was available.
+
         Under context parallelism the forward raises: the sharded phases and the KV split have no fp8 kernels."""
         k_scale, v_scale = float(k_scale), float(v_scale)
         for s in (k_scale, v_scale):
@@ -461,6 +476,7 @@ class CausalWanModel:
                 raise ValueError("enable_fp8_attention: scales must be finite and positive")
         self._fp8_attn_epoch += 1
         self._fp8_attn = (k_scale, v_scale, self._fp8_attn_epoch)
+        self._fp8_attn_smooth = bool(smooth_k)
         return self
 
     def disable_fp8_attention(self):
@@ -471,10 +487,35 @@ class CausalWanModel:
         return self
 
     def fp8_attention_amax(self):
-        """float32 [num_layers, 2]: the largest |k| and |v| (raw bf16 values) quantised into a shadow since the mode first ran."""
+        """float32 [num_layers, 2]: the largest |k| and |v| (raw bf16 values) quantised into a shadow since the mode first ran.
+        With smooth_k=True the K column follows |k - c| under the centre of the time - the value that saturates at 448 * k_scale."""
         if self._fp8_attn_amax is None:
             raise RuntimeError("fp8 attention has not run yet")
         return self._fp8_attn_amax
+
+    def fp8_attention_recenter(self, kv_cache):
+        """smooth_k=True: set every layer's K centre to the fp32 column means of the physical rows [0, min(local_end_index, rows)) of
+        its bf16 K cache (ops.attn_kv_center) and mark the shadows stale: the next forward refills each of them with one centred
+        quantiser call, as after a scale change.  Writes the centre buffer in place and allocates nothing.  The window moving on
+        afterwards is not an error - any fixed centre is exact -, only a slightly less good centre."""
+        if self._fp8_attn is None or not self._fp8_attn_smooth:
+            raise RuntimeError("fp8_attention_recenter needs enable_fp8_attention(smooth_k=True)")
+        if self._fp8_attn_center is None:
+            raise RuntimeError("fp8 attention has not run yet: the centres are allocated by the first forward")
+        if len(kv_cache) != self.num_layers:
+            raise ValueError("fp8_attention_recenter: one KV cache entry per layer")
+        for l, c in enumerate(kv_cache):
+            k = c["k"]
+            if k.shape[0] != 1 or tuple(k.shape[2:]) != tuple(self._fp8_attn_center.shape[1:]):
+                raise ValueError("fp8_attention_recenter: batch size 1 and the heads the centres were allocated for")
+            n = min(int(c["local_end_index"]), k.shape[1])
+            if n <= 0:
+                raise RuntimeError("fp8_attention_recenter: the KV cache is empty")
+            if ops.attn_kv_center_workspace_bytes(n, k.shape[2]) > self._fp8_attn_center_ws.numel() * 4:
+                raise RuntimeError("fp8_attention_recenter: this cache is larger than the one the workspace was allocated for")
+            ops.attn_kv_center(k[0], (0, n), out=self._fp8_attn_center[l], workspace=self._fp8_attn_center_ws)
+        self._fp8_attn_center_epoch += 1
+        return self
 
     def _fp8_attention_shadow(self, kv_cache, use_cp):
         """The rtv_attn_fp8_shadow of this forward (None: bf16 attention) and what must stay alive with it."""
@@ -487,21 +528,38 @@ class CausalWanModel:
         if self._fp8_attn_amax is None:
             self._fp8_attn_amax = torch.zeros(L, 2, dtype=torch.float32, device=kv_cache[0]["k"].device)
         rows = kv_cache[0]["k"].shape[1]
+        smooth = self._fp8_attn_smooth
+        if smooth:
+            k0 = kv_cache[0]["k"]
+            need = ops.attn_kv_center_workspace_bytes(rows, k0.shape[2])
+            if self._fp8_attn_center is None or tuple(self._fp8_attn_center.shape[1:]) != tuple(k0.shape[2:]) \
+                    or self._fp8_attn_center.device != k0.device:
+                self._fp8_attn_center = torch.zeros(L, k0.shape[2], 128, dtype=torch.float32, device=k0.device)
+                self._fp8_attn_center_ws = None
+            if self._fp8_attn_center_ws is None or self._fp8_attn_center_ws.numel() * 4 < need:      # (a larger cache than any before)
+                self._fp8_attn_center_ws = torch.empty(max(need, 16) // 4, dtype=torch.float32, device=k0.device)
         for l, c in enumerate(kv_cache):
             if c["k"].shape[0] != 1 or c["k"].shape[1] != rows:
                 raise ValueError("fp8 attention: batch size 1 and the same number of rows in every layer's KV cache")
             H = c["k"].shape[2]
+            if smooth and H != self._fp8_attn_center.shape[1]:
+                raise ValueError("fp8 attention: smooth_k needs the same number of heads in every layer's KV cache")
             if "k8" not in c or tuple(c["k8"].shape[:2]) != (rows, H) or c["k8"].device != c["k"].device:
                 c["k8"], c["v8t"] = ops.attn_fp8_shadow(rows, H, c["k"].device)
                 c["fp8_filled"] = None
             state = (k_scale, v_scale, epoch, c["k"].data_ptr(), c["v"].data_ptr())
+            if smooth:
+                state += (self._fp8_attn_center_epoch, self._fp8_attn_center.data_ptr())
             if c.get("fp8_filled") != state:
-                ops.attn_quantize_kv(c["k"][0], c["v"][0], c["k8"], c["v8t"], 0, rows, k_scale, v_scale, amax=self._fp8_attn_amax[l])
+                ops.attn_quantize_kv(c["k"][0], c["v"][0], c["k8"], c["v8t"], 0, rows, k_scale, v_scale, amax=self._fp8_attn_amax[l],
+                                     center=self._fp8_attn_center[l] if smooth else None)
                 c["fp8_filled"] = state
         arrs = [(c_vp * L)(*[t_.data_ptr() for t_ in ts]) for ts in ([c["k8"] for c in kv_cache], [c["v8t"] for c in kv_cache],
                                                                      [self._fp8_attn_amax[l] for l in range(L)])]
         pp = ctypes.POINTER(c_vp)
         sh = _Fp8Shadow(ctypes.cast(arrs[0], pp), ctypes.cast(arrs[1], pp), rows, k_scale, v_scale, ctypes.cast(arrs[2], pp))
+        if smooth:
+            arrs.append((c_vp * L)(*[self._fp8_attn_center[l].data_ptr() for l in range(L)]))
         return sh, (sh, arrs)
 
     @staticmethod
@@ -929,6 +987,9 @@ class CausalWanModel:
         # (the unsharded forward with the shadows as an argument; the phase API of the context-parallel path has no fp8 form)
         forward = ("rtv_dit_forward",) if fp8_shadow is None else ("rtv_dit_forward_attn_fp8", ctypes.byref(fp8_shadow))
         fp8_key = (self._fp8_attn[:2] + (kv_cache[0]["k8"].data_ptr(), kv_cache[-1]["v8t"].data_ptr())) if fp8_shadow is not None else None
+        if fp8_shadow is not None and self._fp8_attn_smooth:      # the centred entry point: the centre table behind the shadow
+            forward = ("rtv_dit_forward_attn_fp8_centered", ctypes.byref(fp8_shadow), fp8_keep[1][3])
+            fp8_key += (self._fp8_attn_center.data_ptr(),)
 
         def ptr_array(tensors):
             arr = (c_vp * L)(*[t_.data_ptr() for t_ in tensors])

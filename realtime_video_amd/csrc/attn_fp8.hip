@@ -2,7 +2,8 @@
 // reference's SageAttention backend (wan/modules/sage.py: 8-bit Q K^T, fp8 P V) at the plug-in point attn_fwd.hip serves in bf16.
 //
 //   attn_quantize_kv_kernel   rows of the bf16 cache -> k8 (row-major e4m3) and v8t (e4m3, transposed per 64-row storage tile, keys
-//                             in the slot order of the header)
+//                             in the slot order of the header); its CENTER instantiation codes k - c (rtv_hip_attn_fp8_center.h)
+//   attn_kv_center_*_kernel   c = the fp32 column means of K over a key window, in two stages without atomics
 //   attn_fwd_fp8_kernel       the structure of attn_fwd_kernel (attn_fwd.hip): 8 waves x 32 query rows of one head, 64-key tiles
 //                             through double-buffered LDS, compiler-scheduled.  S^T = K . Q^T and O^T += V^T . P^T both on
 //                             v_mfma_f32_32x32x64_f8f6f4: 4 + 4 MFMAs of 64 cycles per tile instead of 16 + 16 of 32.
@@ -14,7 +15,10 @@
 //     * Q is quantised in the prologue, one scale per (row, head): the lane and its partner lane ^ 32 hold the row.
 #include <cmath>
 
+#include <type_traits>
+
 #include "../../include/rtv_hip_attn_fp8.h"
+#include "../../include/rtv_hip_attn_fp8_center.h"
 #include "attn_common.h"
 #include "fp8_quant.h"
 
@@ -51,6 +55,18 @@ struct QuantParams {
   float k_scale, v_scale;
   unsigned* amax;
 };
+struct QuantParamsCentered : QuantParams {
+  const float* center;   // [H][128] fp32
+};
+
+struct CenterParams {
+  const uint16_t* k;
+  int64_t rs;
+  int row0, n0, row1, n1, H;
+  float* part;     // [chunks][H][128] fp32
+  float* center;   // [H][128] fp32
+  int chunks;
+};
 
 struct FwdParams {
   const uint16_t* q;
@@ -71,7 +87,9 @@ struct FwdParams {
 // and of V.  K codes leave at once (8 bytes per key); the V codes of the four keys make one 32-bit word per dim - four neighbouring
 // slots - which goes through LDS so that the tile leaves as whole 16-byte pieces of its [dim][64 slots] rows.  Only bytes of rows
 // inside [row0, row0 + rows) are written: a partly covered tile falls back to 4-byte words and single bytes.
-__global__ __launch_bounds__(256) void attn_quantize_kv_kernel(af8::QuantParams p) {
+// CENTER: the K codes are those of k - c; the thread's 8 channels of c stay in registers over its four keys.
+template <bool CENTER>
+__global__ __launch_bounds__(256) void attn_quantize_kv_kernel(std::conditional_t<CENTER, af8::QuantParamsCentered, af8::QuantParams> p) {
   constexpr int LD = 17;   // words per dim row of the LDS image (16 + 1: the dims of a wave do not all start in one bank)
   __shared__ __attribute__((aligned(16))) uint32_t sV[ATT_D * LD];
   __shared__ float s_max[2][4];
@@ -81,6 +99,12 @@ __global__ __launch_bounds__(256) void attn_quantize_kv_kernel(af8::QuantParams 
   const int r_lo = max(p.row0 - T * ATT_KT, 0), r_hi = min(p.row0 + p.rows - T * ATT_KT, ATT_KT);   // tile-local rows to convert
   float kmax = 0.f, vmax = 0.f;
   uint32_t vw[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+  float cen[8];
+  if constexpr (CENTER) {
+    const f32x4 c0 = *(const f32x4*)(p.center + (size_t)h * ATT_D + dc * 8), c1 = *(const f32x4*)(p.center + (size_t)h * ATT_D + dc * 8 + 4);
+#pragma unroll
+    for (int d = 0; d < 4; ++d) cen[d] = c0[d], cen[4 + d] = c1[d];
+  }
 #pragma unroll
   for (int jj = 0; jj < 4; ++jj) {
     const int key = 4 * kq + jj;
@@ -90,6 +114,10 @@ __global__ __launch_bounds__(256) void attn_quantize_kv_kernel(af8::QuantParams 
     const u32x4 kr = *(const u32x4*)(p.k + src), vr = *(const u32x4*)(p.v + src);
     float x[8];
     unpack_bf16x8(kr, x);
+    if constexpr (CENTER) {
+#pragma unroll
+      for (int d = 0; d < 8; ++d) x[d] -= cen[d];   // fp32, rounded once, before the division
+    }
 #pragma unroll
     for (int d = 0; d < 8; ++d) kmax = fmaxf(kmax, fabsf(x[d]));
     *(u32x2*)(p.k8 + ((size_t)phys * p.H + h) * ATT_D + dc * 8) = quantize8(x, p.k_scale);
@@ -148,6 +176,42 @@ __global__ __launch_bounds__(256) void attn_quantize_kv_kernel(af8::QuantParams 
       }
     }
   }
+}
+
+// Column means of K, stage 1.  One workgroup = one (chunk of RTV_ATTN_CENTER_CHUNK window rows, head): thread (rq, dc) adds the
+// rows rq, rq + 16, ... of the chunk, dims 8 dc .. 8 dc + 7, in ascending order; the 16 row groups are then added in ascending
+// order through LDS.  Window row j is physical row row0 + j, or row1 + (j - n0) behind the first range.
+__global__ __launch_bounds__(256) void attn_kv_center_partial_kernel(af8::CenterParams p) {
+  __shared__ float sP[16][ATT_D + 4];
+  const int tid = threadIdx.x, dc = tid & 15, rq = tid >> 4, h = blockIdx.y;
+  const int n = p.n0 + p.n1;
+  const int j0 = blockIdx.x * RTV_ATTN_CENTER_CHUNK, j1 = min(j0 + RTV_ATTN_CENTER_CHUNK, n);
+  float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  for (int j = j0 + rq; j < j1; j += 16) {
+    const int64_t phys = j < p.n0 ? (int64_t)p.row0 + j : (int64_t)p.row1 + (j - p.n0);
+    const u32x4 kr = *(const u32x4*)(p.k + (size_t)(phys * p.rs) + (size_t)h * ATT_D + dc * 8);
+    float x[8];
+    unpack_bf16x8(kr, x);
+#pragma unroll
+    for (int d = 0; d < 8; ++d) acc[d] += x[d];
+  }
+#pragma unroll
+  for (int d = 0; d < 8; ++d) sP[rq][dc * 8 + d] = acc[d];
+  __syncthreads();
+  if (tid < ATT_D) {
+    float s = sP[0][tid];
+#pragma unroll
+    for (int r = 1; r < 16; ++r) s += sP[r][tid];
+    p.part[((size_t)blockIdx.x * p.H + h) * ATT_D + tid] = s;
+  }
+}
+
+// Stage 2.  One workgroup = one head, one thread = one channel: the chunks in ascending order, then one division.
+__global__ __launch_bounds__(ATT_D) void attn_kv_center_reduce_kernel(af8::CenterParams p) {
+  const int d = threadIdx.x, h = blockIdx.x;
+  float s = 0.f;
+  for (int c = 0; c < p.chunks; ++c) s += p.part[((size_t)c * p.H + h) * ATT_D + d];
+  p.center[(size_t)h * ATT_D + d] = s / (float)(p.n0 + p.n1);
 }
 
 __global__ __launch_bounds__(af8::NW * 64) void attn_fwd_fp8_kernel(af8::FwdParams p) {
@@ -407,19 +471,23 @@ static bool good_scale(float s) { return std::isfinite(s) && s > 0.f; }
 
 using namespace rtv;
 
-extern "C" int rtv_attn_quantize_kv(const void* k, const void* v, int64_t row_stride, int row0, int rows, int H, void* k8,
-                                    void* v8t, int cache_rows, float k_scale, float v_scale, void* amax, rtv_stream_t stream) {
+// The checks and the launch of both quantisers; center != null selects the CENTER instantiation.
+static int quantize_kv_launch(const void* k, const void* v, int64_t row_stride, int row0, int rows, int H, void* k8, void* v8t,
+                              int cache_rows, float k_scale, float v_scale, void* amax, const float* center, bool centered,
+                              rtv_stream_t stream) {
   if (!k || !v || !k8 || !v8t) return set_error(-1, "attn_quantize_kv: null pointer");
   if (((uintptr_t)k | (uintptr_t)v | (uintptr_t)k8 | (uintptr_t)v8t) & 15)
     return set_error(-1, "attn_quantize_kv: k, v, k8 and v8t must be 16-byte aligned");
   if ((uintptr_t)amax & 3) return set_error(-1, "attn_quantize_kv: amax must be 4-byte aligned");
+  if (centered && (!center || ((uintptr_t)center & 15)))
+    return set_error(-1, "attn_quantize_kv: center must be a 16-byte aligned device float[H][128]");
   if (rows <= 0 || H <= 0 || cache_rows <= 0) return set_error(-1, "attn_quantize_kv: rows, H and cache_rows must be positive");
   if (row0 < 0 || (int64_t)row0 + rows > cache_rows) return set_error(-1, "attn_quantize_kv: row range outside [0, cache_rows)");
   if (row_stride < (int64_t)H * ATT_D || (row_stride & 7))
     return set_error(-1, "attn_quantize_kv: row stride must be a multiple of 8 elements and hold H heads");
   if (!good_scale(k_scale) || !good_scale(v_scale)) return set_error(-1, "attn_quantize_kv: scales must be finite and positive");
   if (H > 65535) return set_error(-1, "attn_quantize_kv: more than 65535 heads");
-  af8::QuantParams p;
+  af8::QuantParamsCentered p;
   p.k = (const uint16_t*)k;
   p.v = (const uint16_t*)v;
   p.rs = row_stride;
@@ -432,10 +500,61 @@ extern "C" int rtv_attn_quantize_kv(const void* k, const void* v, int64_t row_st
   p.k_scale = k_scale;
   p.v_scale = v_scale;
   p.amax = (unsigned*)amax;
+  p.center = center;
   const int tiles = ((row0 + rows - 1) >> 6) - p.tile0 + 1;
   ProfScope prof(PROF_MISC, (hipStream_t)stream, 0.0);
-  hipLaunchKernelGGL(attn_quantize_kv_kernel, dim3(tiles, H), dim3(256), 0, (hipStream_t)stream, p);
+  if (centered)
+    hipLaunchKernelGGL(attn_quantize_kv_kernel<true>, dim3(tiles, H), dim3(256), 0, (hipStream_t)stream, p);
+  else
+    hipLaunchKernelGGL(attn_quantize_kv_kernel<false>, dim3(tiles, H), dim3(256), 0, (hipStream_t)stream, (const af8::QuantParams&)p);
   return check_launch("attn_quantize_kv");
+}
+
+extern "C" int rtv_attn_quantize_kv(const void* k, const void* v, int64_t row_stride, int row0, int rows, int H, void* k8,
+                                    void* v8t, int cache_rows, float k_scale, float v_scale, void* amax, rtv_stream_t stream) {
+  return quantize_kv_launch(k, v, row_stride, row0, rows, H, k8, v8t, cache_rows, k_scale, v_scale, amax, nullptr, false, stream);
+}
+
+extern "C" int rtv_attn_quantize_kv_centered(const void* k, const void* v, int64_t row_stride, int row0, int rows, int H, void* k8,
+                                             void* v8t, int cache_rows, float k_scale, float v_scale, void* amax,
+                                             const float* center, rtv_stream_t stream) {
+  return quantize_kv_launch(k, v, row_stride, row0, rows, H, k8, v8t, cache_rows, k_scale, v_scale, amax, center, true, stream);
+}
+
+extern "C" size_t rtv_attn_kv_center_workspace_bytes(int rows, int H) {
+  if (rows <= 0 || H <= 0) return 0;
+  return (((size_t)rows + RTV_ATTN_CENTER_CHUNK - 1) / RTV_ATTN_CENTER_CHUNK) * (size_t)H * ATT_D * sizeof(float);
+}
+
+extern "C" int rtv_attn_kv_center(const void* k, int64_t row_stride, int row0, int n0, int row1, int n1, int H, float* center,
+                                  void* workspace, size_t workspace_bytes, rtv_stream_t stream) {
+  if (!k || !center || !workspace) return set_error(-1, "attn_kv_center: null pointer");
+  if (((uintptr_t)k | (uintptr_t)center | (uintptr_t)workspace) & 15)
+    return set_error(-1, "attn_kv_center: k, center and workspace must be 16-byte aligned");
+  if (n0 <= 0 || H <= 0) return set_error(-1, "attn_kv_center: n0 and H must be positive");
+  if (n1 < 0) return set_error(-1, "attn_kv_center: negative segment length");
+  if (row0 < 0 || (n1 > 0 && row1 < 0)) return set_error(-1, "attn_kv_center: negative first row");
+  if ((int64_t)n0 + n1 > INT32_MAX) return set_error(-1, "attn_kv_center: too many rows");
+  if (row_stride < (int64_t)H * ATT_D || (row_stride & 7))
+    return set_error(-1, "attn_kv_center: row stride must be a multiple of 8 elements and hold H heads");
+  if (H > 65535) return set_error(-1, "attn_kv_center: more than 65535 heads");
+  if (workspace_bytes < rtv_attn_kv_center_workspace_bytes(n0 + n1, H))
+    return set_error(-1, "attn_kv_center: workspace below rtv_attn_kv_center_workspace_bytes(n0 + n1, H)");
+  af8::CenterParams p;
+  p.k = (const uint16_t*)k;
+  p.rs = row_stride;
+  p.row0 = row0;
+  p.n0 = n0;
+  p.row1 = n1 > 0 ? row1 : 0;
+  p.n1 = n1;
+  p.H = H;
+  p.part = (float*)workspace;
+  p.center = center;
+  p.chunks = (n0 + n1 + RTV_ATTN_CENTER_CHUNK - 1) / RTV_ATTN_CENTER_CHUNK;
+  ProfScope prof(PROF_MISC, (hipStream_t)stream, 0.0);
+  hipLaunchKernelGGL(attn_kv_center_partial_kernel, dim3(p.chunks, H), dim3(256), 0, (hipStream_t)stream, p);
+  hipLaunchKernelGGL(attn_kv_center_reduce_kernel, dim3(H), dim3(ATT_D), 0, (hipStream_t)stream, p);
+  return check_launch("attn_kv_center");
 }
 
 extern "C" int rtv_attn_fwd_fp8(const void* q, const void* k8, const void* v8t, void* o, int Lq, int H, int cache_rows, int row0,

@@ -17,6 +17,7 @@
 #include <string>
 
 #include "../../include/rtv_hip_attn_fp8.h"
+#include "../../include/rtv_hip_attn_fp8_center.h"
 #include "../../include/rtv_hip_mxfp4.h"
 #include "../../include/rtv_hip_mxfp6.h"
 #include "../../include/rtv_hip_mx_rotate.h"
@@ -158,6 +159,7 @@ struct Ctx {
   rtv_stream_t stream;
   int d, H, L, ffn, hd, F, gh, gw, fs, M, r0, rc, tc;
   const rtv_attn_fp8_shadow* fp8;   // rtv_dit_forward_attn_fp8: self-attention on the e4m3 shadows; null in every other entry point
+  void* const* centers;             // rtv_dit_forward_attn_fp8_centered: per-layer K centres of the shadows; null in every other one
   int fold_kh, fold_k;   // cross-attention V folded into the output projection: columns per head / in all; 0 = the unfolded path
                          // (then st->ca_v[L + l] is layer l's folded weight, rtv_dit_step.ca_vo_ld)
 };
@@ -169,6 +171,7 @@ static int make_ctx(const rtv_dit_config* cfg, const rtv_dit_weights* w, const r
   c->w = w;
   c->st = st;
   c->fp8 = nullptr;
+  c->centers = nullptr;
   c->stream = stream;
   c->d = cfg->dim;
   c->H = cfg->num_heads;
@@ -520,9 +523,15 @@ static int quantize_written_rows(Ctx& c, int l) {
     }
   }
   void* amax = sh->amax ? sh->amax[l] : nullptr;
-  for (int i = 0; i < ns; ++i)
-    RTV_TRY(rtv_attn_quantize_kv(st->kv_k[l], st->kv_v[l], st->kv_row_stride, seg[i][0], seg[i][1], c.H, sh->k8[l], sh->v8t[l],
-                                 sh->cache_rows, sh->k_scale, sh->v_scale, amax, c.stream));
+  for (int i = 0; i < ns; ++i) {
+    if (c.centers)
+      RTV_TRY(rtv_attn_quantize_kv_centered(st->kv_k[l], st->kv_v[l], st->kv_row_stride, seg[i][0], seg[i][1], c.H, sh->k8[l],
+                                            sh->v8t[l], sh->cache_rows, sh->k_scale, sh->v_scale, amax, (const float*)c.centers[l],
+                                            c.stream));
+    else
+      RTV_TRY(rtv_attn_quantize_kv(st->kv_k[l], st->kv_v[l], st->kv_row_stride, seg[i][0], seg[i][1], c.H, sh->k8[l], sh->v8t[l],
+                                   sh->cache_rows, sh->k_scale, sh->v_scale, amax, c.stream));
+  }
   return 0;
 }
 
@@ -768,9 +777,10 @@ extern "C" int rtv_dit_finish(const rtv_dit_config* cfg, const rtv_dit_step* st,
   return rtv_unpatchify(head_rows, st->out, cfg->out_dim, st->F, st->gh, st->gw, stream);
 }
 
-// The unsharded composition; fp8 != null: self-attention on the e4m3 shadows (rtv_dit_forward_attn_fp8).
+// The unsharded composition; fp8 != null: self-attention on the e4m3 shadows (rtv_dit_forward_attn_fp8), centers != null: whose K
+// codes are centred (rtv_dit_forward_attn_fp8_centered).
 static int dit_forward(const rtv_dit_config* cfg, const rtv_dit_weights* w, const rtv_dit_step* st, const rtv_attn_fp8_shadow* fp8,
-                       void* workspace, size_t workspace_bytes, rtv_stream_t stream) {
+                       void* const* centers, void* workspace, size_t workspace_bytes, rtv_stream_t stream) {
   Ctx c;
   RTV_TRY(make_ctx(cfg, w, st, workspace, workspace_bytes, stream, &c));
   if (fp8) {
@@ -780,7 +790,11 @@ static int dit_forward(const rtv_dit_config* cfg, const rtv_dit_weights* w, cons
     if (st->attn_kv_splits > 1) return set_error(-1, "dit: fp8 attention does not support attn_kv_splits > 1");
     if (!fp8->k8 || !fp8->v8t || fp8->cache_rows <= 0)
       return set_error(-1, "dit: fp8 attention needs the k8 / v8t shadow arrays and cache_rows");
+    if (centers)
+      for (int l = 0; l < c.L; ++l)
+        if (!centers[l]) return set_error(-1, "dit: fp8 attention: a layer has no K centre");
     c.fp8 = fp8;
+    c.centers = centers;
   }
   if (c.r0 != 0 || c.rc != c.M)
     return set_error(-1, "dit_forward: sharded row ranges need the phase API (rtv_dit_begin/layer_qkv/layer_rest/head/finish)");
@@ -797,14 +811,22 @@ static int dit_forward(const rtv_dit_config* cfg, const rtv_dit_weights* w, cons
 
 extern "C" int rtv_dit_forward(const rtv_dit_config* cfg, const rtv_dit_weights* w, const rtv_dit_step* st,
                                void* workspace, size_t workspace_bytes, rtv_stream_t stream) {
-  return dit_forward(cfg, w, st, nullptr, workspace, workspace_bytes, stream);
+  return dit_forward(cfg, w, st, nullptr, nullptr, workspace, workspace_bytes, stream);
 }
 
 extern "C" int rtv_dit_forward_attn_fp8(const rtv_dit_config* cfg, const rtv_dit_weights* w, const rtv_dit_step* st,
                                         const rtv_attn_fp8_shadow* shadow, void* workspace, size_t workspace_bytes,
                                         rtv_stream_t stream) {
   if (!shadow) return set_error(-1, "dit: fp8 attention needs its shadow (rtv_attn_fp8_shadow)");
-  return dit_forward(cfg, w, st, shadow, workspace, workspace_bytes, stream);
+  return dit_forward(cfg, w, st, shadow, nullptr, workspace, workspace_bytes, stream);
+}
+
+extern "C" int rtv_dit_forward_attn_fp8_centered(const rtv_dit_config* cfg, const rtv_dit_weights* w, const rtv_dit_step* st,
+                                                 const rtv_attn_fp8_shadow* shadow, void* const* centers, void* workspace,
+                                                 size_t workspace_bytes, rtv_stream_t stream) {
+  if (!shadow) return set_error(-1, "dit: fp8 attention needs its shadow (rtv_attn_fp8_shadow)");
+  if (!centers) return set_error(-1, "dit: centred fp8 attention needs its table of K centres");
+  return dit_forward(cfg, w, st, shadow, centers, workspace, workspace_bytes, stream);
 }
 
 extern "C" int rtv_dit_lab_capture_self_attn(void* q_copy, void* o_copy) {

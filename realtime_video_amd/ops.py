@@ -249,11 +249,47 @@ def _check_shadow(k8, v8t, what):
     return rows, H
 
 
-def attn_quantize_kv(k_cache, v_cache, k8, v8t, row0=0, rows=None, k_scale=1.0, v_scale=1.0, amax=None):
+def _check_center(center, H, what):
+    if center.dtype != torch.float32 or tuple(center.shape) != (H, 128) or not center.is_contiguous() or center.data_ptr() % 16:
+        raise ValueError(f"{what}: center must be a dense, 16-byte aligned float32 tensor [H, 128]")
+
+
+def attn_kv_center_workspace_bytes(rows, H):
+    """Bytes of workspace attn_kv_center needs for a window of `rows` rows and H heads (rtv_attn_kv_center_workspace_bytes)."""
+    return int(_lib.load().rtv_attn_kv_center_workspace_bytes(int(rows), int(H)))
+
+
+def attn_kv_center(k_cache, seg0, seg1=(0, 0), out=None, workspace=None):
+    """fp32 column means [H, 128] of the bf16 K rows of the window seg0 + seg1 (each (first physical row, rows)) of a cache
+    k_cache [rows, H, 128] (rtv_attn_kv_center; the K plane of an interleaved arena is fine): the centre a smoothed shadow subtracts
+    (attn_quantize_kv(..., center=)).  Deterministic: the same rows give the same bits.  workspace: float32 tensor of at least
+    rtv_attn_kv_center_workspace_bytes(rows of the window, H) bytes (allocated when None)."""
+    _gpu(k_cache, out, workspace)
+    if k_cache.dtype != torch.bfloat16 or k_cache.dim() != 3 or k_cache.shape[2] != 128 or k_cache.stride(2) != 1 or k_cache.stride(1) != 128:
+        raise ValueError("attn_kv_center: k_cache must be bf16 [rows, H, 128] with dense [H, 128] inner dims")
+    cache_rows, H = k_cache.shape[0], k_cache.shape[1]
+    (r0, n0), (r1, n1) = seg0, seg1
+    if min(r0, n0, r1, n1) < 0 or r0 + n0 > cache_rows or (n1 and r1 + n1 > cache_rows):
+        raise ValueError("attn_kv_center: segment outside the cache")
+    if out is None:
+        out = torch.empty((H, 128), dtype=torch.float32, device=k_cache.device)
+    _check_center(out, H, "attn_kv_center")
+    need = attn_kv_center_workspace_bytes(n0 + n1, H)
+    if workspace is None:
+        workspace = torch.empty(max(need, 16) // 4, dtype=torch.float32, device=k_cache.device)
+    elif workspace.dtype != torch.float32 or not workspace.is_contiguous():
+        raise ValueError("attn_kv_center: workspace must be a dense float32 tensor")
+    _lib.call("rtv_attn_kv_center", _ptr(k_cache), k_cache.stride(0), int(r0), int(n0), int(r1), int(n1), H, _ptr(out), _ptr(workspace),
+              workspace.numel() * 4, _stream())
+    return out
+
+
+def attn_quantize_kv(k_cache, v_cache, k8, v8t, row0=0, rows=None, k_scale=1.0, v_scale=1.0, amax=None, center=None):
     """Quantise the physical rows [row0, row0 + rows) of a bf16 KV cache (k_cache / v_cache [rows, H, 128] with one row stride; the
     two planes of an interleaved arena are fine) into its e4m3 shadow (rtv_attn_quantize_kv).  amax: optional float32 [2] tensor,
-    the running maxima of |k| and |v|."""
-    _gpu(k_cache, v_cache, amax)
+    the running maxima of |k| and |v|.  center: optional float32 [H, 128]: the K codes are those of k - center, and amax[0] follows
+    |k - center| (rtv_attn_quantize_kv_centered, include/rtv_hip_attn_fp8_center.h)."""
+    _gpu(k_cache, v_cache, amax, center)
     cache_rows, H = _check_shadow(k8, v8t, "attn_quantize_kv")
     for t in (k_cache, v_cache):
         if t.dtype != torch.bfloat16 or t.dim() != 3 or tuple(t.shape) != (cache_rows, H, 128) or t.stride(2) != 1 or t.stride(1) != 128:
@@ -264,6 +300,11 @@ def attn_quantize_kv(k_cache, v_cache, k8, v8t, row0=0, rows=None, k_scale=1.0, 
         raise ValueError("attn_quantize_kv: amax must be a dense float32 tensor of 2 elements")
     if rows is None:
         rows = cache_rows - row0
+    if center is not None:
+        _check_center(center, H, "attn_quantize_kv")
+        _lib.call("rtv_attn_quantize_kv_centered", _ptr(k_cache), _ptr(v_cache), k_cache.stride(0), int(row0), int(rows), H, _ptr(k8),
+                  _ptr(v8t), cache_rows, float(k_scale), float(v_scale), _ptr(amax), _ptr(center), _stream())
+        return k8, v8t
     _lib.call("rtv_attn_quantize_kv", _ptr(k_cache), _ptr(v_cache), k_cache.stride(0), int(row0), int(rows), H, _ptr(k8), _ptr(v8t),
               cache_rows, float(k_scale), float(v_scale), _ptr(amax), _stream())
     return k8, v8t

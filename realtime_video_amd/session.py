@@ -103,6 +103,7 @@ class GenerationSession:
         self.current_prompt_embeds = None
         self.resume_latents = None
         self.last_pred = None
+        self._fp8_recentered = False                  # smooth_k: the one recentre behind the first block has happened
         self.init_models(models, params)
         self.denoising_step_list = get_denoising_schedule(self.zero_padded_timesteps, params.strength,
                                                           steps=params.num_denoising_steps)
@@ -339,6 +340,8 @@ class GenerationSession:
             denoised_pred = res[1]
             if renoise is not None:
                 noisy_input = res[2]
+        if not self._fp8_recentered and self._smooth_k_model(models) is not None:
+            self.fp8_attention_recenter(models)       # once, behind the first block that has filled the cache
         self.all_latents[:, self.current_start_frame:self.current_start_frame + nfpb] = denoised_pred
         self.last_pred = denoised_pred
         pixels = None
@@ -361,6 +364,25 @@ class GenerationSession:
         self.block_idx += 1
         self.resume_latents = None
         return pixels if pixels is not None else denoised_pred
+
+    @staticmethod
+    def _smooth_k_model(models):
+        """The native model behind models.transformer when it runs enable_fp8_attention(smooth_k=True), else None."""
+        model = getattr(models.transformer, "model", models.transformer)
+        on = getattr(model, "_fp8_attn", None) is not None and getattr(model, "_fp8_attn_smooth", False)
+        return model if on else None
+
+    def fp8_attention_recenter(self, models=None):
+        """enable_fp8_attention(smooth_k=True): set the K centres of the model to the channel means of this session's KV cache
+        (CausalWanModel.fp8_attention_recenter); the next forward refills the e4m3 shadows.  The session does it once by itself,
+        behind the first block that has filled the cache, and never periodically: call it again where the keys are expected to have
+        moved, e.g. after a prompt change."""
+        models = models or self.models
+        model = self._smooth_k_model(models)
+        if model is None:
+            raise RuntimeError("fp8_attention_recenter needs a model with enable_fp8_attention(smooth_k=True)")
+        model.fp8_attention_recenter(models.pipeline.kv_cache1)
+        self._fp8_recentered = True
 
     def set_lora_scale(self, name, scale):
         """Strength of a loaded LoRA adapter, between two blocks of a running session: the model re-merges the touched weights
