@@ -240,7 +240,11 @@ typedef struct rtv_dit_config {
                                    for 3; rtv_hip_mxfp6.h);
                                    5 / 6: 3 / 4 with the 32-point block Hadamard rotation in front of both quantisers - the weights'
                                    codes were made by rtv_quantize_mx*_rot at RTV_MX_ROT_WEIGHT_SHIFT (rtv_hip_mx_rotate.h; storage,
-                                   pointers and workspace as for 3 / 4) */
+                                   pointers and workspace as for 3 / 4);
+                                   7: mixed - every Linear runs its own mode, 0 (bf16) to 6: its *_w pointer, its fp8_scales entry
+                                   (mode 1) or its fp8_row_scales entry (modes 2 to 6) are what that mode takes, and the modes are
+                                   named by one more entry of fp8_row_scales (below); the workspace is sized for any mix.  No
+                                   layout changes, so like 3 to 6 this value came without a new revision */
   int max_attn_kv_splits;       /* largest rtv_dit_step.attn_kv_splits this workspace must serve (0 / 1: none - the workspace then
                                    holds no split-attention partials: 97 MB at 14B, M = 4680); a step asking for more fails */
 } rtv_dit_config;
@@ -273,7 +277,11 @@ typedef struct rtv_dit_weights {
                                          3d of them for the fused qkv weight.  use_fp8 == 3: the same table, entry i addressing
                                          the weight's MXFP4 block scales, [N][K / 32] bytes in the order of rtv_hip_mxfp4.h; use_fp8 == 4: its
                                          MXFP6 block scales, [N][K / 32] bytes in the order of rtv_hip_mxfp6.h.
-                                         NULL otherwise */
+                                         NULL otherwise.  use_fp8 == 7: the table has 6 + 8 L + 1 entries.  Entry i < 6 + 8 L is
+                                         what the mode of Linear i takes (modes 2 to 6; ignored, and may be NULL, for a Linear in
+                                         mode 0 or 1); the LAST entry, [6 + 8 L], is the address of linear_modes: a HOST array of
+                                         6 + 8 L bytes (uint8_t) in the order of fp8_scales, the mode (0 to 6, the values of
+                                         use_fp8) of each Linear */
 } rtv_dit_weights;
 
 typedef struct rtv_dit_step {

@@ -19,7 +19,7 @@ import types
 
 import torch
 
-from . import _lib, lora, ops
+from . import _lib, lora, ops, precision_policy
 from .rope import rope_cos_sin_table
 
 c_vp = ctypes.c_void_p
@@ -40,6 +40,8 @@ _FP8_TOP = ("text0_w", "text2_w", "time0_w", "time2_w", "tproj_w", "head_w")
 _FP8_LAYER = ("qkv_w", "o_w", "cq_w", "ck_w", "cv_w", "co_w", "ffn0_w", "ffn2_w")
 # rtv_dit_config.use_fp8: how the Linears of _FP8_TOP / _FP8_LAYER run
 _BF16, _FP8_TENSOR, _FP8_ROWS, _MXFP4, _MXFP6, _MXFP4_ROT, _MXFP6_ROT = range(7)
+_MIXED = precision_policy.MIXED     # one of the modes above per Linear (set_linear_precision; the last entry of fp8_row_scales names them)
+_RELOAD = "the bf16 weights are gone - reload the weights first"
 # the block-scaled modes: (name, the Linear input widths' multiple, weight and LoRA quantiser, the enable_* calls it excludes).  The
 # rotated modes (include/rtv_hip_mx_rotate.h) quantise the weights with the rotated kernel at the weight shift; the forward rotates
 # the activations at the activation shift.
@@ -325,6 +327,8 @@ class CausalWanModel:
         if granularity not in ("tensor", "row"):
             raise ValueError(f"enable_fp8: granularity must be 'tensor' or 'row', got {granularity!r}")
         mode = _FP8_ROWS if granularity == "row" else _FP8_TENSOR
+        if self._cfg.use_fp8 == _MIXED:
+            raise RuntimeError(f"enable_fp8 after set_linear_precision(): {_RELOAD}")
         if self._cfg.use_fp8 in _MX_MODES:
             rotate = "rotate=True" if self._cfg.use_fp8 in (_MXFP4_ROT, _MXFP6_ROT) else ""
             raise RuntimeError(f"enable_fp8 after enable_{_MX_MODES[self._cfg.use_fp8][0]}({rotate}): the bf16 weights are gone - "
@@ -411,6 +415,8 @@ class CausalWanModel:
         name, k_multiple, quantize, others = _MX_MODES[mode]
         if self._cfg.use_fp8 == mode:
             return self
+        if self._cfg.use_fp8 == _MIXED:
+            raise RuntimeError(f"enable_{name} after set_linear_precision(): {_RELOAD}")
         if self._cfg.use_fp8:
             raise RuntimeError(f"enable_{name} after {others}: the bf16 weights are gone - reload the weights first")
         if self.context_parallel is not None:
@@ -441,6 +447,88 @@ class CausalWanModel:
         self._ws.clear()                  # the workspace grows by the activation codes and their block scales
         ops.ensure_gemm_workspace(self.device)
         return self
+
+    def set_linear_precision(self, policy):
+        """Opt-in: one precision per nn.Linear instead of one for the model.  `policy` is a dict (precision_policy.py has the grammar):
+        values "bf16", "fp8", "fp8_row", "mxfp4", "mxfp6", "mxfp4_rot", "mxfp6_rot" - the modes of enable_fp8() / enable_fp8("row") /
+        enable_mxfp4() / enable_mxfp6() and their rotate=True forms; keys "default" (absent: "bf16"), a Linear kind ("text0", "text2",
+        "time0", "time2", "tproj", "head", "qkv", "o", "cq", "ck", "cv", "co", "ffn0", "ffn2") or one Linear of one layer
+        ("L0.ffn0"); the more specific key wins.  E.g. {"default": "fp8_row", "ffn0": "mxfp4", "ffn2": "mxfp4", "head": "bf16"}.
+
+        Every weight is prepared by the quantiser its mode uses in the pure modes and the forward runs each Linear with that mode's
+        kernels (rtv_dit_config.use_fp8 == 7; the mode table rides behind rtv_dit_weights.fp8_row_scales): a policy with one mode for every Linear computes bit
+        for bit what the matching enable_* call computes, and a bf16 Linear what it computes in a bf16 model.  A policy that leaves
+        every Linear in bf16 changes nothing.  The cross-attention V fold stays off, as under every quantised mode.
+
+        Call after load_state_dict / init_random_weights; the bf16 copies of the quantised weights are freed, so the same policy
+        again is a no-op and another one, or an enable_* call before or after, is refused (reload the weights first).  LoRA as
+        under the pure modes: load adapters first; set_lora_scale() / unload_lora() re-merge from the bf16 bases and re-quantise
+        each matrix with its own mode in place.  Context parallelism is refused: sharded mixed forwards are untested."""
+        widths = precision_policy.linear_widths(self.dim, self.ffn_dim, self.text_dim, self.freq_dim)
+        modes = precision_policy.resolve(policy, self.num_layers, widths)
+        if self._cfg.use_fp8 == _MIXED:
+            if modes == list(self._linear_modes):
+                return self
+            raise RuntimeError(f"set_linear_precision: another policy is in place and {_RELOAD}")
+        if self._cfg.use_fp8:
+            raise RuntimeError(f"set_linear_precision after enable_fp8() / enable_mxfp4() / enable_mxfp6(): {_RELOAD}")
+        if self.context_parallel is not None:
+            raise RuntimeError("set_linear_precision: context parallelism is not supported under a per-Linear precision policy "
+                               "(sharded mixed forwards are untested)")
+        if self._w is None:
+            raise RuntimeError("load weights before set_linear_precision()")
+        if not any(modes):
+            return self                       # all bf16: the model as it is
+        keys = list(_FP8_TOP) + [f"L{l}.{w}" for l in range(self.num_layers) for w in _FP8_LAYER]
+        # fp8_row_scales: per-row scales (mode 2) or block scales (modes 3 to 6), null for modes 0 / 1; behind them the address of the modes
+        table = (c_vp * (len(keys) + 1))()
+        scales = (ctypes.c_float * len(keys))()      # fp8_scales: the per-tensor scales of mode 1; 0 elsewhere
+        self._mx_scales, self._fp8_row_scales = {}, {}
+        for i, (key, mode) in enumerate(zip(keys, modes)):
+            if mode == _BF16:
+                continue
+            if mode in _MX_MODES:
+                q, self._mx_scales[key] = _MX_MODES[mode][2](self._tensors[key])
+                table[i] = self._mx_scales[key].data_ptr()
+            elif mode == _FP8_ROWS:
+                q, self._fp8_row_scales[key] = self._quantize_fp8_rows(self._tensors[key])
+                table[i] = self._fp8_row_scales[key].data_ptr()
+            else:
+                q, scales[i] = self._quantize_fp8(self._tensors[key])
+            self._tensors[key] = q
+            if i < len(_FP8_TOP):
+                setattr(self._w, key, q.data_ptr())
+            else:
+                layer, field = key[1:].split(".")
+                setattr(self._layers_arr[int(layer)], field, q.data_ptr())
+        torch.cuda.synchronize(self.device)   # the bf16 weights the quantisers read are released above, tensor by tensor
+        self._linear_modes = (ctypes.c_uint8 * len(keys))(*modes)
+        table[len(keys)] = ctypes.addressof(self._linear_modes)
+        self._fp8_row_table, self._fp8_scales = table, scales
+        self._w.fp8_row_scales = ctypes.cast(table, ctypes.POINTER(c_vp))
+        self._w.fp8_scales = ctypes.cast(scales, ctypes.POINTER(ctypes.c_float))
+        self._cfg.use_fp8 = _MIXED
+        self._graphs.clear()              # captured graphs replay the bf16 launch sequence on freed bf16 weights
+        self._weights_version += 1
+        self._ws.clear()                  # the workspace grows by the activation codes and their scales
+        ops.ensure_gemm_workspace(self.device)
+        return self
+
+    def linear_precision(self):
+        """{Linear: mode name} as the forward runs them, keys and names as in set_linear_precision ("text0", ..., "L0.qkv", ...)."""
+        keys = list(_FP8_TOP) + [f"L{l}.{w}" for l in range(self.num_layers) for w in _FP8_LAYER]
+        return precision_policy.named([self._linear_mode(k) for k in keys], self.num_layers)
+
+    def _linear_mode(self, key):
+        """How the tensor `key` of _tensors is held: 0 (bf16: every tensor that is no Linear weight too) to 6."""
+        if key in _FP8_TOP:
+            i = _FP8_TOP.index(key)
+        elif key.startswith("L") and key.split(".")[-1] in _FP8_LAYER:
+            layer, field = key[1:].split(".")
+            i = len(_FP8_TOP) + len(_FP8_LAYER) * int(layer) + _FP8_LAYER.index(field)
+        else:
+            return _BF16
+        return self._linear_modes[i] if self._cfg.use_fp8 == _MIXED else self._cfg.use_fp8
 
     def enable_fp8_attention(self, k_scale=1.0, v_scale=1.0, smooth_k=False):
         """Opt-in: self-attention in the precision of the reference's SageAttention backend (wan/modules/sage.py: 8-bit Q K^T, fp8
@@ -635,7 +723,8 @@ class CausalWanModel:
         if self._w is None:
             raise RuntimeError("load weights before load_lora()")
         if self._cfg.use_fp8:
-            raise RuntimeError("load_lora after enable_fp8() / enable_mxfp4() / enable_mxfp6(): the bf16 weights are gone - load adapters first, then enable the mode")
+            raise RuntimeError("load_lora after enable_fp8() / enable_mxfp4() / enable_mxfp6() / set_linear_precision(): the bf16 weights are "
+                               "gone - load adapters first, then enable the mode")
         held = {}          # weight range -> [(adapter, it is a DoRA adapter there)]
         for other, ad in self._lora.items():
             for tg in ad["targets"].values():
@@ -718,7 +807,8 @@ class CausalWanModel:
                     live.setdefault(tg.bias, {}).setdefault((tg.bias0, tg.bias_n), []).append((tg, ad["scale"], tg.diff_b))
         for key in sorted(keys):
             base = self._lora_base[key]
-            quantised = bool(self._cfg.use_fp8) and (key in _FP8_TOP or (key.startswith("L") and key.split(".")[-1] in _FP8_LAYER))
+            mode = self._linear_mode(key)            # the key's own: the model's one mode, or under a precision policy this Linear's
+            quantised = mode != _BF16
             out = torch.empty_like(base) if quantised else self._tensors[key]
             vector = base.ndim == 1
             blocks = ((0, base.shape[0]),) if not key.endswith((".qkv_w", ".qkv_b")) else tuple((j * self.dim, self.dim) for j in range(3))
@@ -732,11 +822,11 @@ class CausalWanModel:
                     lora.merge_dora(b_, o_, tg.A, tg.B, tg.factor, tg.dora, strength, self._lora_dora_ws)
                 else:
                     lora.merge_ex(b_, o_, [(tg.A, tg.B, s * tg.factor, d, s) for tg, s, d in on])
-            if quantised and self._cfg.use_fp8 in _MX_MODES:
+            if mode in _MX_MODES:
                 # the quantiser of _enable_mx (and of the forward), into the existing code and scale tensors: the weight table and
                 # rtv_dit_weights.fp8_row_scales keep pointing at them
-                _MX_MODES[self._cfg.use_fp8][2](out, codes=self._tensors[key], scales=self._mx_scales[key])
-            elif quantised and self._cfg.use_fp8 == _FP8_ROWS:
+                _MX_MODES[mode][2](out, codes=self._tensors[key], scales=self._mx_scales[key])
+            elif mode == _FP8_ROWS:
                 q, rs = self._quantize_fp8_rows(out)
                 self._tensors[key].copy_(q)
                 self._fp8_row_scales[key].copy_(rs)      # in place: rtv_dit_weights.fp8_row_scales keeps pointing at it
@@ -946,6 +1036,8 @@ class CausalWanModel:
         cp = self.context_parallel
         # (a one-rank group takes the plain forward unless the ContextParallel object insists: bench.py --cp-host-probe)
         use_cp = cp is not None and (cp.world > 1 or getattr(cp, "force_single_rank", False))
+        if cp is not None and self._cfg.use_fp8 == _MIXED:
+            raise RuntimeError("a per-Linear precision policy does not support context parallelism (set_linear_precision)")
         if cp is not None and self._cfg.use_fp8 in _MX_MODES:
             name = _MX_MODES[self._cfg.use_fp8][0]
             raise RuntimeError(f"{name.upper()} Linears do not support context parallelism (enable_{name})")

@@ -102,7 +102,7 @@ struct DitBuffers {
   uint8_t* q8;      // fp8 path: the quantised activation of the linear being computed (use_fp8 == 3, MXFP4: its e2m1 codes in the
                     // first rows * K / 2 bytes and its block scales behind them - 17 / 32 of the fp8 size; use_fp8 == 4, MXFP6: e2m3
                     // codes in the first rows * 3 K / 4 bytes, block scales behind them - 25 / 32; 5 / 6, the rotated modes: as 3 / 4)
-  float* frow;      // fp8 path with per-row scales (use_fp8 == 2): the row scales of the activation in q8
+  float* frow;      // fp8 path with per-row scales (use_fp8 == 2, and 7 for its Linears in mode 2): the row scales of the activation in q8
   float* fscale;    // fp8 path: its per-tensor scale (device), followed by the 4-byte absmax scratch
   float* attn_part; // KV-split self-attention of a sharded call: fp32 partial outputs + (m, l) of splits x heads x rows <= H x M
   size_t attn_part_bytes;
@@ -138,7 +138,9 @@ static size_t carve(const rtv_dit_config* c, int F, int gh, int gw, char* base, 
     if ((size_t)c->text_dim > k) k = c->text_dim;
     if ((size_t)c->freq_dim > k) k = c->freq_dim;
     t.q8 = (uint8_t*)ws.take(c->use_fp8 ? rows * k : 0);
-    t.frow = (float*)ws.take(c->use_fp8 == 2 ? rows * sizeof(float) : 0);   // (an empty take moves nothing: modes 0 / 1 keep their layout)
+    // (an empty take moves nothing: modes 0 / 1 keep their layout; 7, mixed: the union - q8 at the fp8 size, which covers both MX
+    // layouts, the row scales, and the per-tensor slots below)
+    t.frow = (float*)ws.take(c->use_fp8 == 2 || c->use_fp8 == 7 ? rows * sizeof(float) : 0);
     t.fscale = (float*)ws.take(256);
   }
   // KV-split self-attention of sharded calls, only when the configuration asks for it (97 MB per workspace at 14B
@@ -160,9 +162,41 @@ struct Ctx {
   int d, H, L, ffn, hd, F, gh, gw, fs, M, r0, rc, tc;
   const rtv_attn_fp8_shadow* fp8;   // rtv_dit_forward_attn_fp8: self-attention on the e4m3 shadows; null in every other entry point
   void* const* centers;             // rtv_dit_forward_attn_fp8_centered: per-layer K centres of the shadows; null in every other one
+  const uint8_t* modes;  // use_fp8 == 7: the mode of each Linear (linear_modes, checked by make_ctx); null otherwise
   int fold_kh, fold_k;   // cross-attention V folded into the output projection: columns per head / in all; 0 = the unfolded path
                          // (then st->ca_v[L + l] is layer l's folded weight, rtv_dit_step.ca_vo_ld)
 };
+
+// use_fp8 == 7: the modes of the Linears, a host array of 6 + 8 L bytes whose address is the entry behind the 6 + 8 L scale entries
+// of rtv_dit_weights.fp8_row_scales (the struct has no field for it: its layout is pinned).  Null when the table or the entry is.
+static const uint8_t* linear_modes(const rtv_dit_config* cfg, const rtv_dit_weights* w) {
+  return w->fp8_row_scales ? (const uint8_t*)w->fp8_row_scales[6 + 8 * (cfg->num_layers > 0 ? cfg->num_layers : 0)] : nullptr;
+}
+
+// use_fp8 == 7 (one mode per Linear): everything a Linear of that mode would ask for later is asked for here, in front of the first
+// launch.  The order of the table is that of fp8_scales; K = the Linear's input width.
+static int check_linear_modes(const rtv_dit_config* cfg, const rtv_dit_weights* w, const uint8_t* modes) {
+  if (!modes) return set_error(-1, "dit: use_fp8 == 7 needs linear_modes (the last entry of rtv_dit_weights.fp8_row_scales)");
+  static const char* const top[] = {"text0", "text2", "time0", "time2", "tproj", "head"};
+  static const char* const per_layer[] = {"qkv", "o", "cq", "ck", "cv", "co", "ffn0", "ffn2"};
+  const int n = 6 + 8 * cfg->num_layers;
+  for (int i = 0; i < n; ++i) {
+    const int mode = modes[i];
+    const int K = i == 0 ? cfg->text_dim : i == 2 ? cfg->freq_dim : (i >= 6 && (i - 6) % 8 == 7) ? cfg->ffn_dim : cfg->dim;
+    const int mult = mode == 3 || mode == 5 ? 256 : mode == 4 || mode == 6 ? 128 : 1;
+    const char* what = mode > 6                                                        ? " is not a mode (0 to 6)"
+                       : mode == 1 && !w->fp8_scales                                   ? " needs rtv_dit_weights.fp8_scales"
+                       : mode >= 2 && (!w->fp8_row_scales || !w->fp8_row_scales[i])    ? " needs its rtv_dit_weights.fp8_row_scales entry"
+                       : K % mult                                                      ? (mult == 256 ? " needs an input width that is a multiple of 256"
+                                                                                                      : " needs an input width that is a multiple of 128")
+                                                                                       : nullptr;
+    if (what) {   // (the name is put together for the message alone: this loop runs in front of every forward)
+      const std::string name = i < 6 ? std::string(top[i]) : "L" + std::to_string((i - 6) / 8) + "." + per_layer[(i - 6) % 8];
+      return set_error(-1, ("dit: linear_modes: " + name + ": mode " + std::to_string(mode) + what).c_str());
+    }
+  }
+  return 0;
+}
 
 static int make_ctx(const rtv_dit_config* cfg, const rtv_dit_weights* w, const rtv_dit_step* st, void* workspace,
                     size_t workspace_bytes, rtv_stream_t stream, Ctx* c) {
@@ -178,6 +212,12 @@ static int make_ctx(const rtv_dit_config* cfg, const rtv_dit_weights* w, const r
   c->L = cfg->num_layers;
   c->ffn = cfg->ffn_dim;
   if (c->H <= 0 || c->d % c->H || c->d / c->H != 128) return set_error(-1, "dit: head_dim must be 128");
+  c->modes = nullptr;
+  if (cfg->use_fp8 == 7) {
+    c->modes = linear_modes(cfg, w);
+    const int s = check_linear_modes(cfg, w, c->modes);
+    if (s) return s;
+  }
   c->hd = 128;
   c->F = st->F;
   c->gh = st->gh;
@@ -266,8 +306,13 @@ extern "C" size_t rtv_dit_workspace_bytes(const rtv_dit_config* cfg, int F, int 
 // not an nn.Linear - the Conv3d patch embedding - and stays bf16).
 enum { S_TEXT0 = 0, S_TEXT2, S_TIME0, S_TIME2, S_TPROJ, S_HEAD, S_LAYER0 };
 enum { S_QKV = 0, S_O, S_CQ, S_CK, S_CV, S_CO, S_FFN0, S_FFN2, S_PER_LAYER };
-enum { FP8_TENSOR = 1, FP8_ROWS = 2, MODE_MXFP4 = 3, MODE_MXFP6 = 4, MODE_MXFP4_ROT = 5, MODE_MXFP6_ROT = 6 };   // the values of cfg->use_fp8 (0: bf16)
-static bool is_fp8(const Ctx& c, int sidx) { return c.cfg->use_fp8 && sidx >= 0; }
+enum { FP8_TENSOR = 1, FP8_ROWS = 2, MODE_MXFP4 = 3, MODE_MXFP6 = 4, MODE_MXFP4_ROT = 5, MODE_MXFP6_ROT = 6, MODE_MIXED = 7 };   // the values of cfg->use_fp8 (0: bf16)
+// How Linear `sidx` runs, 0 to 6: the one mode of the model, or under MODE_MIXED the Linear's own (make_ctx has checked the table).
+static int mode_of(const Ctx& c, int sidx) {
+  if (sidx < 0) return 0;
+  return c.cfg->use_fp8 == MODE_MIXED ? c.modes[sidx] : c.cfg->use_fp8;
+}
+static bool is_fp8(const Ctx& c, int sidx) { return mode_of(c, sidx) != 0; }
 
 // A block-scaled mode (rtv_hip_mxfp4.h, rtv_hip_mxfp6.h): q8 holds an activation's codes, code_bytes(K) per row, then its scales.
 // The rotated modes (rtv_hip_mx_rotate.h) are the same rows with the rotated quantisers: the weights were rotated at the weight shift
@@ -283,15 +328,16 @@ static int quantize_act_rot(const void* x, int64_t ld, int M, int d, void* codes
                             rtv_stream_t s) {
   return Q(x, ld, M, d, codes, ld_codes, scales, ld_scales, RTV_MX_ROT_ACT_SHIFT, s);
 }
-static const MxMode MX_MODES[] = {   // [use_fp8 - MODE_MXFP4]
+static const MxMode MX_MODES[] = {   // [mode - MODE_MXFP4]
     {[](int K) { return K / 2; }, rtv_quantize_mxfp4, rtv_layernorm_modulate_mxfp4, rtv_gemm_mxfp4},
     {[](int K) { return RTV_MXFP6_CODE_BYTES(K); }, rtv_quantize_mxfp6, rtv_layernorm_modulate_mxfp6, rtv_gemm_mxfp6},
     {[](int K) { return K / 2; }, quantize_act_rot<rtv_quantize_mxfp4_rot>, rtv_layernorm_modulate_mxfp4_rot, rtv_gemm_mxfp4},
     {[](int K) { return RTV_MXFP6_CODE_BYTES(K); }, quantize_act_rot<rtv_quantize_mxfp6_rot>, rtv_layernorm_modulate_mxfp6_rot,
      rtv_gemm_mxfp6},
 };
-static const MxMode* mx_mode(const Ctx& c) {
-  return c.cfg->use_fp8 >= MODE_MXFP4 && c.cfg->use_fp8 <= MODE_MXFP6_ROT ? &MX_MODES[c.cfg->use_fp8 - MODE_MXFP4] : nullptr;
+static const MxMode* mx_mode(const Ctx& c, int sidx) {
+  const int mode = mode_of(c, sidx);
+  return mode >= MODE_MXFP4 && mode <= MODE_MXFP6_ROT ? &MX_MODES[mode - MODE_MXFP4] : nullptr;
 }
 static uint8_t* mx_scales(const Ctx& c, const MxMode& mx, int M, int K) { return c.b.q8 + (size_t)M * mx.code_bytes(K); }
 
@@ -300,13 +346,14 @@ static uint8_t* mx_scales(const Ctx& c, const MxMode& mx, int M, int K) { return
 // its own output).  The weight's scales are asked for here, in front of the first launch of the Linear.
 static int quantize_input(Ctx& c, int sidx, const void* a, int M, int K, rtv_stream_t s) {
   if (!is_fp8(c, sidx)) return 0;
-  if (const MxMode* mx = mx_mode(c)) {
+  const int mode = mode_of(c, sidx);
+  if (const MxMode* mx = mx_mode(c, sidx)) {
     // per 32-element block: like the row scales, the decisions of a row need that row alone
     if (!c.w->fp8_row_scales || !c.w->fp8_row_scales[sidx])
-      return set_error(-1, ("dit: use_fp8 == " + std::to_string(c.cfg->use_fp8) + " needs rtv_dit_weights.fp8_row_scales").c_str());
+      return set_error(-1, ("dit: use_fp8 == " + std::to_string(mode) + " needs rtv_dit_weights.fp8_row_scales").c_str());
     return a ? mx->quantize(a, K, M, K, c.b.q8, mx->code_bytes(K), mx_scales(c, *mx, M, K), K / 32, s) : 0;
   }
-  if (c.cfg->use_fp8 == FP8_ROWS) {
+  if (mode == FP8_ROWS) {
     // per-row scales: the quantisation of a row needs that row alone, so a token shard takes the unsharded forward's decisions
     if (!c.w->fp8_row_scales || !c.w->fp8_row_scales[sidx]) return set_error(-1, "dit: use_fp8 == 2 needs rtv_dit_weights.fp8_row_scales");
     return a ? rtv_quantize_fp8_rows(a, K, M, K, c.b.q8, K, c.b.frow, s) : 0;
@@ -322,7 +369,7 @@ static int quantize_input(Ctx& c, int sidx, const void* a, int M, int K, rtv_str
 static int project(Ctx& c, int sidx, const void* a, int K, const void* w, int w_row0, const void* bias, void* out, int ldc, int M, int N,
                    int act, const void* gate, int gate_stride, int rpf, int row_off, const void* res, int cfg, rtv_stream_t s) {
   const bool fp8 = is_fp8(c, sidx);
-  const MxMode* mx = fp8 ? mx_mode(c) : nullptr;
+  const MxMode* mx = mx_mode(c, sidx);
   // fp8 weights are bytes, MXFP4 nibbles, MXFP6 three bytes per four elements
   const void* wp = (const char*)w + (size_t)w_row0 * (mx ? mx->code_bytes(K) : K * (fp8 ? 1 : 2));
   const void* bp = bias ? (const uint16_t*)bias + w_row0 : nullptr;
@@ -332,7 +379,7 @@ static int project(Ctx& c, int sidx, const void* a, int K, const void* w, int w_
     return mx->gemm(c.b.q8, mx->code_bytes(K), wp, mx->code_bytes(K), mx_scales(c, *mx, M, K),
                     (const uint8_t*)c.w->fp8_row_scales[sidx] + (size_t)w_row0 * (K / 32), out, ldc, M, N, K, bp, act, gate, gate_stride, rpf,
                     row_off, res, ldr, s);
-  if (c.cfg->use_fp8 == FP8_ROWS)
+  if (mode_of(c, sidx) == FP8_ROWS)
     return rtv_gemm_fp8_rows(c.b.q8, K, wp, K, c.b.frow, (const float*)c.w->fp8_row_scales[sidx] + w_row0, out, ldc, M, N, K, bp, act, gate,
                              gate_stride, rpf, row_off, res, ldr, s);
   return rtv_gemm_fp8(c.b.q8, K, wp, K, c.b.fscale, c.w->fp8_scales[sidx], out, ldc, M, N, K, bp, act, gate, gate_stride, rpf, row_off, res,
@@ -347,16 +394,17 @@ static int linear(Ctx& c, int sidx, const void* a, int K, const void* w, const v
 
 // LayerNorm of the local rows of b.x in front of a Linear: modulated by (shift, scale) per frame, or affine (weight, bias).
 // The result goes to b.xn - or, with per-row fp8 scales, straight to e4m3 codes and row scales in q8 / frow: one kernel in place
-// of LayerNorm + quantiser, same bits.  *a = what linear() takes as that Linear's input (null: already quantised).
-static int ln_input(Ctx& c, const void* shift, const void* scale, int frame_stride, const void* weight, const void* bias, const void** a) {
+// of LayerNorm + quantiser, same bits.  *a = what linear() takes as that Linear's input (null: already quantised).  `sidx` is the
+// Linear that consumes the result (qkv, cq, ffn0): its mode chooses the form.
+static int ln_input(Ctx& c, int sidx, const void* shift, const void* scale, int frame_stride, const void* weight, const void* bias, const void** a) {
   DitBuffers& b = c.b;
   const int rpf = scale ? c.fs : 0, r0 = scale ? c.r0 : 0;
-  if (const MxMode* mx = mx_mode(c)) {
+  if (const MxMode* mx = mx_mode(c, sidx)) {
     *a = nullptr;
     return mx->layernorm_modulate(b.x, b.q8, mx->code_bytes(c.d), mx_scales(c, *mx, c.rc, c.d), c.d / 32, c.rc, c.d, c.cfg->eps, shift, scale,
                                   frame_stride, rpf, r0, weight, bias, c.stream);
   }
-  if (c.cfg->use_fp8 == FP8_ROWS) {
+  if (mode_of(c, sidx) == FP8_ROWS) {
     *a = nullptr;
     return rtv_layernorm_modulate_fp8_rows(b.x, b.q8, c.d, b.frow, c.rc, c.d, c.cfg->eps, shift, scale, frame_stride, rpf, r0, weight, bias,
                                            c.stream);
@@ -423,7 +471,7 @@ static int dit_layer_proj(Ctx& c, int l, int parts, int world, void* q_send, voi
   // this layer, as b.xn does in the other modes - no other Linear runs between the projection phases of a layer)
   if (parts & RTV_PROJ_LN) {
     const void* ln_out;   // b.xn or q8 / frow: the projections below read them by name
-    RTV_TRY(ln_input(c, em + 0 * d, em + 1 * d, 6 * d, nullptr, nullptr, &ln_out));
+    RTV_TRY(ln_input(c, S_LAYER0 + S_PER_LAYER * l + S_QKV, em + 0 * d, em + 1 * d, 6 * d, nullptr, nullptr, &ln_out));
   }
   const bool q = parts & RTV_PROJ_Q, kv = parts & RTV_PROJ_KV;
   if (!q && !kv) return 0;
@@ -466,7 +514,7 @@ static int dit_layer_proj(Ctx& c, int l, int parts, int world, void* q_send, voi
       }
     }
     const int sidx = S_LAYER0 + S_PER_LAYER * l + S_QKV;
-    const void* a = c.cfg->use_fp8 >= FP8_ROWS ? nullptr : b.xn;   // what the LN phase left: b.xn, or codes and scales in q8 / frow (modes 2 to 6)
+    const void* a = mode_of(c, sidx) >= FP8_ROWS ? nullptr : b.xn;   // what the LN phase left: b.xn, or codes and scales in q8 / frow (modes 2 to 6)
     RTV_TRY(quantize_input(c, sidx, a, c.rc, d, c.stream));
     auto proj = [&](int w_row0, int N, void* out, int ldc) {
       return project(c, sidx, a, d, lw.qkv_w, w_row0, lw.qkv_b, out, ldc, c.rc, N, 0, nullptr, 0, 0, 0, nullptr, c.tc, c.stream);
@@ -629,7 +677,7 @@ static int dit_after_attn(Ctx& c, int l) {
   RTV_TRY(linear(c, S_LAYER0 + S_PER_LAYER * l + S_O, b.ao, d, lw.o_w, lw.o_b, b.x, rc, d, 0, em + 2 * d, 6 * d, fs, r0, b.x, tc, stream));
   // cross attention (causal_model.py:480, model.py:171-228)
   const void* ln_out = nullptr;
-  RTV_TRY(ln_input(c, nullptr, nullptr, 0, lw.norm3_w, lw.norm3_b, &ln_out));
+  RTV_TRY(ln_input(c, S_LAYER0 + S_PER_LAYER * l + S_CQ, nullptr, nullptr, 0, lw.norm3_w, lw.norm3_b, &ln_out));
   RTV_TRY(linear(c, S_LAYER0 + S_PER_LAYER * l + S_CQ, ln_out, d, lw.cq_w, lw.cq_b, b.qkv, rc, d, 0, nullptr, 0, 0, 0, nullptr, tc, stream));
   RTV_TRY(rtv_rmsnorm(b.qkv, d, b.q, d, rc, d, eps, lw.cnorm_q_w, stream));
   if (c.fold_k) {
@@ -649,7 +697,7 @@ static int dit_after_attn(Ctx& c, int l) {
     RTV_TRY(linear(c, S_LAYER0 + S_PER_LAYER * l + S_CO, b.ao, d, lw.co_w, lw.co_b, b.x, rc, d, 0, nullptr, 0, 0, 0, b.x, tc, stream));
   }
   // FFN (causal_model.py:482-488)
-  RTV_TRY(ln_input(c, em + 3 * d, em + 4 * d, 6 * d, nullptr, nullptr, &ln_out));
+  RTV_TRY(ln_input(c, S_LAYER0 + S_PER_LAYER * l + S_FFN0, em + 3 * d, em + 4 * d, 6 * d, nullptr, nullptr, &ln_out));
   RTV_TRY(linear(c, S_LAYER0 + S_PER_LAYER * l + S_FFN0, ln_out, d, lw.ffn0_w, lw.ffn0_b, b.h, rc, c.ffn, RTV_ACT_GELU_TANH, nullptr, 0, 0, 0, nullptr, tc, stream));
   RTV_TRY(linear(c, S_LAYER0 + S_PER_LAYER * l + S_FFN2, b.h, c.ffn, lw.ffn2_w, lw.ffn2_b, b.x, rc, d, 0, em + 5 * d, 6 * d, fs, r0, b.x, tc, stream));
   return 0;
