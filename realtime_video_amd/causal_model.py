@@ -35,24 +35,14 @@ _Fp8Shadow = _lib.ATTN_FP8_STRUCTS["rtv_attn_fp8_shadow"]
 _LAYER_FIELDS = tuple(n for n, _ in _LayerW._fields_)
 _TOP_FIELDS = tuple(n for n, t in _Weights._fields_ if t is c_vp)      # the device tensors; `layers` / `fp8_scales` are host arrays
 
-# nn.Linear weights in the order of rtv_dit_weights.fp8_scales (include/rtv_hip.h)
-_FP8_TOP = ("text0_w", "text2_w", "time0_w", "time2_w", "tproj_w", "head_w")
-_FP8_LAYER = ("qkv_w", "o_w", "cq_w", "ck_w", "cv_w", "co_w", "ffn0_w", "ffn2_w")
-# rtv_dit_config.use_fp8: how the Linears of _FP8_TOP / _FP8_LAYER run
-_BF16, _FP8_TENSOR, _FP8_ROWS, _MXFP4, _MXFP6, _MXFP4_ROT, _MXFP6_ROT = range(7)
-_MIXED = precision_policy.MIXED     # one of the modes above per Linear (set_linear_precision; the last entry of fp8_row_scales names them)
-_RELOAD = "the bf16 weights are gone - reload the weights first"
-# the block-scaled modes: (name, the Linear input widths' multiple, weight and LoRA quantiser, the enable_* calls it excludes).  The
-# rotated modes (include/rtv_hip_mx_rotate.h) quantise the weights with the rotated kernel at the weight shift; the forward rotates
-# the activations at the activation shift.
-def _rot_weights(quantize):
-    return functools.partial(quantize, rotate_shift=ops.MX_ROT_WEIGHT_SHIFT)
-
-
-_MX_MODES = {_MXFP4: ("mxfp4", 256, ops.quantize_mxfp4, "enable_fp8() / enable_mxfp6() / enable_mxfp4(rotate=True)"),
-             _MXFP6: ("mxfp6", 128, ops.quantize_mxfp6, "enable_fp8() / enable_mxfp4() / enable_mxfp6(rotate=True)"),
-             _MXFP4_ROT: ("mxfp4", 256, _rot_weights(ops.quantize_mxfp4), "enable_fp8() / enable_mxfp6() / enable_mxfp4(rotate=False)"),
-             _MXFP6_ROT: ("mxfp6", 128, _rot_weights(ops.quantize_mxfp6), "enable_fp8() / enable_mxfp4() / enable_mxfp6(rotate=False)")}
+# rtv_dit_config.use_fp8: how the nn.Linears run.  precision_policy has the mode numbers (MODE_NAMES), the Linears in the order of
+# rtv_dit_weights.fp8_scales (linear_names(); their _tensors keys end in "_w") and the width multiples; _QUANT, behind the class, has
+# what needs the library: per quantised mode the weight quantiser and where its scales are kept.
+_BF16 = precision_policy.MODE_NAMES.index("bf16")
+_MIXED = precision_policy.MIXED     # one of the modes per Linear (set_linear_precision; the last entry of fp8_row_scales names them)
+# the Linears' field names in the weight tables, derived from precision_policy's kinds (tests compare the two orders)
+_FP8_TOP = tuple(kind + "_w" for kind in precision_policy.TOP_KINDS)
+_FP8_LAYER = tuple(kind + "_w" for kind in precision_policy.LAYER_KINDS)
 
 PROJ_LN, PROJ_Q, PROJ_KV = 1, 2, 4
 
@@ -139,6 +129,8 @@ class CausalWanModel:
         self.context_parallel = None   # realtime_video_amd.parallel.ContextParallel when the token axis is sharded
         self._tensors = {}      # name -> device tensor (keeps the memory alive)
         self._w = None          # ctypes weight table
+        # _tensors key of every nn.Linear weight -> its place in rtv_dit_weights.fp8_scales (include/rtv_hip.h), in that order
+        self._linear_index = {name + "_w": i for i, name in enumerate(precision_policy.linear_names(num_layers))}
         self._ws = {}           # (F, gh, gw) -> workspace tensor
         # cross-attention over the real prompt rows + ONE of the (identical) zero-padding rows weighted by their count instead of
         # all 512 text rows (rtv_attn_fwd_dup: mathematically identical, 8x less cross-attention work for a 64-token prompt)
@@ -326,47 +318,7 @@ class CausalWanModel:
         published source: tests/fp8_rows_oracle.py).  The granularity cannot be changed once fp8 is on: the bf16 weights are gone."""
         if granularity not in ("tensor", "row"):
             raise ValueError(f"enable_fp8: granularity must be 'tensor' or 'row', got {granularity!r}")
-        mode = _FP8_ROWS if granularity == "row" else _FP8_TENSOR
-        if self._cfg.use_fp8 == _MIXED:
-            raise RuntimeError(f"enable_fp8 after set_linear_precision(): {_RELOAD}")
-        if self._cfg.use_fp8 in _MX_MODES:
-            rotate = "rotate=True" if self._cfg.use_fp8 in (_MXFP4_ROT, _MXFP6_ROT) else ""
-            raise RuntimeError(f"enable_fp8 after enable_{_MX_MODES[self._cfg.use_fp8][0]}({rotate}): the bf16 weights are gone - "
-                               "reload the weights first")
-        if self._w is None:
-            raise RuntimeError("load weights before enable_fp8()")
-        if self._cfg.use_fp8:
-            if self._cfg.use_fp8 != mode:
-                raise RuntimeError(f"enable_fp8({granularity!r}): fp8 is on with the other granularity and the bf16 weights are gone - "
-                                   "reload the weights first")
-            return self
-        for k in (self.dim, self.ffn_dim, self.text_dim, self.freq_dim):
-            if k % 128:
-                raise ValueError("enable_fp8: every Linear input width must be a multiple of 128")
-        if mode == _FP8_ROWS:
-            return self._enable_fp8_rows()
-        scales = (ctypes.c_float * (len(_FP8_TOP) + len(_FP8_LAYER) * self.num_layers))()
-
-        def quant(key):
-            q, s = self._quantize_fp8(self._tensors[key])
-            self._tensors[key] = q
-            return q, s
-
-        for i, name in enumerate(_FP8_TOP):
-            q, scales[i] = quant(name)
-            setattr(self._w, name, q.data_ptr())
-        for l in range(self.num_layers):
-            for j, name in enumerate(_FP8_LAYER):
-                q, scales[len(_FP8_TOP) + len(_FP8_LAYER) * l + j] = quant(f"L{l}.{name}")
-                setattr(self._layers_arr[l], name, q.data_ptr())
-        self._fp8_scales = scales
-        self._w.fp8_scales = ctypes.cast(scales, ctypes.POINTER(ctypes.c_float))
-        self._cfg.use_fp8 = _FP8_TENSOR
-        self._graphs.clear()              # captured graphs replay the bf16 launch sequence on freed bf16 weights
-        self._weights_version += 1
-        self._ws.clear()                  # the workspace grows by the fp8 activation buffer
-        ops.ensure_gemm_workspace(self.device)
-        return self
+        return self._quantise_uniform("fp8_row" if granularity == "row" else "fp8")
 
     def enable_mxfp4(self, rotate=False):
         """Opt-in: every nn.Linear that enable_fp8() covers runs on MXFP4 operands instead (include/rtv_hip_mxfp4.h: OCP e2m1 codes,
@@ -389,7 +341,7 @@ class CausalWanModel:
         Gaussian figure (tests/test_mx_rotate_cpu.py; DESIGN.md section 6 has what was measured on the GPU and what was not).  The
         GEMM, the storage and the workspace are those of rotate=False; the pin is tests/mx_rotate_oracle.py.  The two values of
         `rotate` exclude each other like two modes: the other one afterwards is refused (reload the weights first)."""
-        return self._enable_mx(_MXFP4_ROT if rotate else _MXFP4)
+        return self._quantise_uniform("mxfp4_rot" if rotate else "mxfp4")
 
     def enable_mxfp6(self, rotate=False):
         """Opt-in: every nn.Linear that enable_fp8() / enable_mxfp4() cover runs on MXFP6 operands instead (include/rtv_hip_mxfp6.h:
@@ -409,44 +361,7 @@ class CausalWanModel:
 
         rotate=True (opt-in; rtv_dit_config.use_fp8 == 6): the block Hadamard rotation of enable_mxfp4(rotate=True) in front of the
         MXFP6 quantisers, with the same exclusions."""
-        return self._enable_mx(_MXFP6_ROT if rotate else _MXFP6)
-
-    def _enable_mx(self, mode):
-        name, k_multiple, quantize, others = _MX_MODES[mode]
-        if self._cfg.use_fp8 == mode:
-            return self
-        if self._cfg.use_fp8 == _MIXED:
-            raise RuntimeError(f"enable_{name} after set_linear_precision(): {_RELOAD}")
-        if self._cfg.use_fp8:
-            raise RuntimeError(f"enable_{name} after {others}: the bf16 weights are gone - reload the weights first")
-        if self.context_parallel is not None:
-            raise RuntimeError(f"enable_{name}: context parallelism is not supported in this mode (sharded {name.upper()} is untested)")
-        for k in (self.dim, self.ffn_dim, self.text_dim, self.freq_dim):
-            if k % k_multiple:
-                raise ValueError(f"enable_{name}: every Linear input width must be a multiple of {k_multiple}")
-        if self._w is None:
-            raise RuntimeError(f"load weights before enable_{name}()")
-        keys = list(_FP8_TOP) + [f"L{l}.{w}" for l in range(self.num_layers) for w in _FP8_LAYER]
-        table = (c_vp * len(keys))()
-        self._mx_scales = {}              # _tensors key -> the weight's block scales, [N, K / 32] bytes
-        for i, key in enumerate(keys):
-            codes, scales = quantize(self._tensors[key])
-            self._tensors[key], self._mx_scales[key] = codes, scales
-            table[i] = scales.data_ptr()
-            if i < len(_FP8_TOP):
-                setattr(self._w, key, codes.data_ptr())
-            else:
-                layer, field = key[1:].split(".")
-                setattr(self._layers_arr[int(layer)], field, codes.data_ptr())
-        torch.cuda.synchronize(self.device)   # the bf16 weights the quantiser reads are released above, tensor by tensor
-        self._fp8_row_table = table
-        self._w.fp8_row_scales = ctypes.cast(table, ctypes.POINTER(c_vp))
-        self._cfg.use_fp8 = mode
-        self._graphs.clear()              # captured graphs replay the bf16 launch sequence on freed bf16 weights
-        self._weights_version += 1
-        self._ws.clear()                  # the workspace grows by the activation codes and their block scales
-        ops.ensure_gemm_workspace(self.device)
-        return self
+        return self._quantise_uniform("mxfp6_rot" if rotate else "mxfp6")
 
     def set_linear_precision(self, policy):
         """Opt-in: one precision per nn.Linear instead of one for the model.  `policy` is a dict (precision_policy.py has the grammar):
@@ -464,69 +379,79 @@ class CausalWanModel:
         again is a no-op and another one, or an enable_* call before or after, is refused (reload the weights first).  LoRA as
         under the pure modes: load adapters first; set_lora_scale() / unload_lora() re-merge from the bf16 bases and re-quantise
         each matrix with its own mode in place.  Context parallelism is refused: sharded mixed forwards are untested."""
-        widths = precision_policy.linear_widths(self.dim, self.ffn_dim, self.text_dim, self.freq_dim)
-        modes = precision_policy.resolve(policy, self.num_layers, widths)
-        if self._cfg.use_fp8 == _MIXED:
-            if modes == list(self._linear_modes):
-                return self
-            raise RuntimeError(f"set_linear_precision: another policy is in place and {_RELOAD}")
-        if self._cfg.use_fp8:
-            raise RuntimeError(f"set_linear_precision after enable_fp8() / enable_mxfp4() / enable_mxfp6(): {_RELOAD}")
-        if self.context_parallel is not None:
-            raise RuntimeError("set_linear_precision: context parallelism is not supported under a per-Linear precision policy "
-                               "(sharded mixed forwards are untested)")
+        return self._quantise_linears(precision_policy.resolve(policy, self.num_layers), _MIXED)
+
+    def _quantise_uniform(self, mode_name):
+        """The enable_* calls: every Linear in one mode, and that mode's number in rtv_dit_config.use_fp8."""
+        mode = precision_policy.MODE_NAMES.index(mode_name)
+        return self._quantise_linears([mode] * len(self._linear_index), mode)
+
+    def _quantise_linears(self, modes, use_fp8):
+        """The weight preparation of every quantised mode.  `modes`: one mode number per Linear, in the order of _linear_index;
+        `use_fp8`: the value rtv_dit_config.use_fp8 takes - the one mode of an enable_* call, or _MIXED.  Each quantised weight
+        replaces the bf16 one in _tensors and in the weight table, and its scales go where the native side looks for them: a
+        per-tensor scale (mode 1) into fp8_scales, the address of per-row scales (2) or block scales (3 to 6) into fp8_row_scales.
+        Behind those 6 + 8 L entries comes the address of the modes, which the native side reads under _MIXED.  An entry no mode
+        reads stays 0, and a store no Linear uses (_mx_scales, _fp8_row_scales: _tensors key -> scales) stays empty."""
+        state = self._cfg.use_fp8
+        call = "set_linear_precision" if use_fp8 == _MIXED else _QUANT[use_fp8].name
+        if state:
+            if state == use_fp8 and (state != _MIXED or modes == list(self._linear_modes)):
+                return self                   # already in this state
+            same_call = state != _MIXED and _QUANT[state].name == call
+            raise RuntimeError(f"{call} after {self._quantised_state()}: {'its other granularity / rotation is on and ' if same_call else ''}"
+                               "the bf16 weights are gone - reload the weights first")
+        if self.context_parallel is not None and (use_fp8 == _MIXED or not all(_QUANT[m].sharded for m in set(modes) - {_BF16})):
+            raise RuntimeError(f"{call}: context parallelism is not supported (sharded block-scaled and mixed forwards are untested)")
+        precision_policy.check_widths(modes, self.num_layers, precision_policy.linear_widths(self.dim, self.ffn_dim, self.text_dim,
+                                                                                             self.freq_dim), call)
         if self._w is None:
-            raise RuntimeError("load weights before set_linear_precision()")
+            raise RuntimeError(f"load weights before {call}()")
         if not any(modes):
             return self                       # all bf16: the model as it is
-        keys = list(_FP8_TOP) + [f"L{l}.{w}" for l in range(self.num_layers) for w in _FP8_LAYER]
-        # fp8_row_scales: per-row scales (mode 2) or block scales (modes 3 to 6), null for modes 0 / 1; behind them the address of the modes
+        keys = list(self._linear_index)
         table = (c_vp * (len(keys) + 1))()
-        scales = (ctypes.c_float * len(keys))()      # fp8_scales: the per-tensor scales of mode 1; 0 elsewhere
+        scales = (ctypes.c_float * len(keys))()
         self._mx_scales, self._fp8_row_scales = {}, {}
         for i, (key, mode) in enumerate(zip(keys, modes)):
             if mode == _BF16:
                 continue
-            if mode in _MX_MODES:
-                q, self._mx_scales[key] = _MX_MODES[mode][2](self._tensors[key])
-                table[i] = self._mx_scales[key].data_ptr()
-            elif mode == _FP8_ROWS:
-                q, self._fp8_row_scales[key] = self._quantize_fp8_rows(self._tensors[key])
-                table[i] = self._fp8_row_scales[key].data_ptr()
-            else:
-                q, scales[i] = self._quantize_fp8(self._tensors[key])
+            q, s = _QUANT[mode].quantize(self._tensors[key])
             self._tensors[key] = q
-            if i < len(_FP8_TOP):
-                setattr(self._w, key, q.data_ptr())
+            if _QUANT[mode].store:
+                getattr(self, _QUANT[mode].store)[key] = s
+                table[i] = s.data_ptr()
             else:
-                layer, field = key[1:].split(".")
-                setattr(self._layers_arr[int(layer)], field, q.data_ptr())
+                scales[i] = s
+            layer = (i - len(_FP8_TOP)) // len(_FP8_LAYER)      # < 0: a top-level Linear
+            setattr(self._w if layer < 0 else self._layers_arr[layer], key.split(".")[-1], q.data_ptr())
         torch.cuda.synchronize(self.device)   # the bf16 weights the quantisers read are released above, tensor by tensor
         self._linear_modes = (ctypes.c_uint8 * len(keys))(*modes)
         table[len(keys)] = ctypes.addressof(self._linear_modes)
         self._fp8_row_table, self._fp8_scales = table, scales
         self._w.fp8_row_scales = ctypes.cast(table, ctypes.POINTER(c_vp))
         self._w.fp8_scales = ctypes.cast(scales, ctypes.POINTER(ctypes.c_float))
-        self._cfg.use_fp8 = _MIXED
+        self._cfg.use_fp8 = use_fp8
         self._graphs.clear()              # captured graphs replay the bf16 launch sequence on freed bf16 weights
         self._weights_version += 1
         self._ws.clear()                  # the workspace grows by the activation codes and their scales
         ops.ensure_gemm_workspace(self.device)
         return self
 
+    def _quantised_state(self):
+        """What put the Linears into the state they are in, for the refusals: the enable_* call, or the policy by the modes it uses."""
+        if self._cfg.use_fp8 != _MIXED:
+            return _QUANT[self._cfg.use_fp8].call
+        return f"set_linear_precision() [{', '.join(sorted(set(self.linear_precision().values())))}]"
+
     def linear_precision(self):
         """{Linear: mode name} as the forward runs them, keys and names as in set_linear_precision ("text0", ..., "L0.qkv", ...)."""
-        keys = list(_FP8_TOP) + [f"L{l}.{w}" for l in range(self.num_layers) for w in _FP8_LAYER]
-        return precision_policy.named([self._linear_mode(k) for k in keys], self.num_layers)
+        return precision_policy.named([self._linear_mode(k) for k in self._linear_index], self.num_layers)
 
     def _linear_mode(self, key):
         """How the tensor `key` of _tensors is held: 0 (bf16: every tensor that is no Linear weight too) to 6."""
-        if key in _FP8_TOP:
-            i = _FP8_TOP.index(key)
-        elif key.startswith("L") and key.split(".")[-1] in _FP8_LAYER:
-            layer, field = key[1:].split(".")
-            i = len(_FP8_TOP) + len(_FP8_LAYER) * int(layer) + _FP8_LAYER.index(field)
-        else:
+        i = self._linear_index.get(key)
+        if i is None:
             return _BF16
         return self._linear_modes[i] if self._cfg.use_fp8 == _MIXED else self._cfg.use_fp8
 
@@ -657,34 +582,11 @@ class CausalWanModel:
         q = (w.float() / s).clamp(-448.0, 448.0).to(torch.float8_e4m3fn).contiguous()
         return q, float(s)
 
-    def _enable_fp8_rows(self):
-        """enable_fp8("row"): every Linear weight becomes e4m3 with one scale per row; the scales stay on the device, one fp32 [N]
-        tensor per weight, and rtv_dit_weights.fp8_row_scales is the host table of their addresses (order of fp8_scales)."""
-        keys = list(_FP8_TOP) + [f"L{l}.{name}" for l in range(self.num_layers) for name in _FP8_LAYER]
-        table = (c_vp * len(keys))()
-        self._fp8_row_scales = {}         # _tensors key -> its row scales; a LoRA re-merge refreshes them in place
-        for i, key in enumerate(keys):
-            q, rs = self._quantize_fp8_rows(self._tensors[key])
-            self._tensors[key], self._fp8_row_scales[key] = q, rs
-            table[i] = rs.data_ptr()
-            if i < len(_FP8_TOP):
-                setattr(self._w, key, q.data_ptr())
-            else:
-                layer, field = key[1:].split(".")
-                setattr(self._layers_arr[int(layer)], field, q.data_ptr())
-        self._fp8_row_table = table
-        self._w.fp8_row_scales = ctypes.cast(table, ctypes.POINTER(c_vp))
-        self._cfg.use_fp8 = _FP8_ROWS
-        self._graphs.clear()
-        self._weights_version += 1
-        self._ws.clear()                  # the workspace grows by the fp8 activation buffer and its row scales
-        ops.ensure_gemm_workspace(self.device)
-        return self
-
     @staticmethod
     def _quantize_fp8_rows(w):
         """bf16 matrix [N, K] -> (e4m3 matrix, fp32 [N] scales): the per-row quantisation of enable_fp8("row") (and of a LoRA
-        re-merge under it).  Once per weight, so torch does it; the arithmetic is the activation quantiser's."""
+        re-merge under it): the scales stay on the device, one tensor per weight.  Once per weight, so torch does it; the
+        arithmetic is the activation quantiser's."""
         s = w.float().abs().amax(dim=1, keepdim=True).clamp(min=1e-12) / 448.0
         q = (w.float() / s).clamp(-448.0, 448.0).to(torch.float8_e4m3fn).contiguous()
         return q, s.reshape(-1).contiguous()
@@ -723,8 +625,8 @@ class CausalWanModel:
         if self._w is None:
             raise RuntimeError("load weights before load_lora()")
         if self._cfg.use_fp8:
-            raise RuntimeError("load_lora after enable_fp8() / enable_mxfp4() / enable_mxfp6() / set_linear_precision(): the bf16 weights are "
-                               "gone - load adapters first, then enable the mode")
+            raise RuntimeError(f"load_lora after {self._quantised_state()}: the bf16 weights are gone - load adapters first, then "
+                               "enable the mode")
         held = {}          # weight range -> [(adapter, it is a DoRA adapter there)]
         for other, ad in self._lora.items():
             for tg in ad["targets"].values():
@@ -822,22 +724,13 @@ class CausalWanModel:
                     lora.merge_dora(b_, o_, tg.A, tg.B, tg.factor, tg.dora, strength, self._lora_dora_ws)
                 else:
                     lora.merge_ex(b_, o_, [(tg.A, tg.B, s * tg.factor, d, s) for tg, s, d in on])
-            if mode in _MX_MODES:
-                # the quantiser of _enable_mx (and of the forward), into the existing code and scale tensors: the weight table and
-                # rtv_dit_weights.fp8_row_scales keep pointing at them
-                _MX_MODES[mode][2](out, codes=self._tensors[key], scales=self._mx_scales[key])
-            elif mode == _FP8_ROWS:
-                q, rs = self._quantize_fp8_rows(out)
-                self._tensors[key].copy_(q)
-                self._fp8_row_scales[key].copy_(rs)      # in place: rtv_dit_weights.fp8_row_scales keeps pointing at it
-            elif quantised:
-                q, s = self._quantize_fp8(out)
-                self._tensors[key].copy_(q)
-                if key in _FP8_TOP:
-                    self._fp8_scales[_FP8_TOP.index(key)] = s
-                else:
-                    layer, field = key[1:].split(".")
-                    self._fp8_scales[len(_FP8_TOP) + len(_FP8_LAYER) * int(layer) + _FP8_LAYER.index(field)] = s
+            if quantised:
+                # the mode's quantiser again, into the existing code and scale tensors: the weight table and
+                # rtv_dit_weights.fp8_row_scales keep pointing at them; a per-tensor scale is replaced in fp8_scales
+                store = _QUANT[mode].store
+                _, s = _QUANT[mode].quantize(out, self._tensors[key], getattr(self, store)[key] if store else None)
+                if not store:
+                    self._fp8_scales[self._linear_index[key]] = s
             requantised = requantised or quantised
             if key not in live:
                 del self._lora_base[key]
@@ -1036,11 +929,8 @@ class CausalWanModel:
         cp = self.context_parallel
         # (a one-rank group takes the plain forward unless the ContextParallel object insists: bench.py --cp-host-probe)
         use_cp = cp is not None and (cp.world > 1 or getattr(cp, "force_single_rank", False))
-        if cp is not None and self._cfg.use_fp8 == _MIXED:
-            raise RuntimeError("a per-Linear precision policy does not support context parallelism (set_linear_precision)")
-        if cp is not None and self._cfg.use_fp8 in _MX_MODES:
-            name = _MX_MODES[self._cfg.use_fp8][0]
-            raise RuntimeError(f"{name.upper()} Linears do not support context parallelism (enable_{name})")
+        if cp is not None and (self._cfg.use_fp8 == _MIXED or (self._cfg.use_fp8 and not _QUANT[self._cfg.use_fp8].sharded)):
+            raise RuntimeError(f"the Linears of {self._quantised_state()} do not support context parallelism")
         # `kv_cache_only` (a per-CALL argument, not in the reference signature: the session passes it for its KV-recompute pass,
         # whose output the reference discards as well, release_server.py:611-632): the forward stops behind the last layer's
         # K / V cache write; the returned tensor is zeros (not while the cross-attention caches are still to be filled: the last
@@ -1279,3 +1169,44 @@ class CausalWanModel:
         return self._forward_inference(*args, **kwargs)
 
     __call__ = forward
+
+
+# What the model knows about a quantised mode beyond precision_policy, which must import without the library:
+#   name      the public call that puts every Linear into the mode, and `args`, the arguments that select this mode of it
+#   quantize  (bf16 matrix, codes=None, scales=None) -> (codes, scales): new tensors, or - a LoRA re-merge - the given ones
+#             rewritten in place.  A per-tensor scale is a float and is returned either way
+#   store     the attribute that keeps the scale tensors by _tensors key; None: the scale is a float in _fp8_scales
+#   sharded   whether context-parallel forwards take the mode (the block-scaled ones share the code path but are untested)
+class _Quant(collections.namedtuple("_Quant", ["name", "args", "quantize", "store", "sharded"])):
+    @property
+    def call(self):
+        """The call as the refusals show it."""
+        return f"{self.name}({self.args})"
+
+
+def _torch_quantiser(static):
+    """CausalWanModel._quantize_fp8 / _quantize_fp8_rows (looked up at each call) with the signature of ops.quantize_mxfp4."""
+    def run(w, codes=None, scales=None):
+        q, s = getattr(CausalWanModel, static)(w)
+        if codes is None:
+            return q, s
+        codes.copy_(q)
+        if scales is not None:
+            scales.copy_(s)
+        return codes, s
+    return run
+
+
+def _mx(name, quantize, rotate):
+    """A block-scaled mode.  The rotated ones (include/rtv_hip_mx_rotate.h) quantise the weights with the rotated kernel at the
+    weight shift; the forward rotates the activations at the activation shift."""
+    if rotate:
+        quantize = functools.partial(quantize, rotate_shift=ops.MX_ROT_WEIGHT_SHIFT)
+    return _Quant(name, f"rotate={rotate}", quantize, "_mx_scales", False)
+
+
+_QUANT = {precision_policy.MODE_NAMES.index(mode): quant for mode, quant in {
+    "fp8": _Quant("enable_fp8", "'tensor'", _torch_quantiser("_quantize_fp8"), None, True),
+    "fp8_row": _Quant("enable_fp8", "'row'", _torch_quantiser("_quantize_fp8_rows"), "_fp8_row_scales", True),
+    "mxfp4": _mx("enable_mxfp4", ops.quantize_mxfp4, False), "mxfp6": _mx("enable_mxfp6", ops.quantize_mxfp6, False),
+    "mxfp4_rot": _mx("enable_mxfp4", ops.quantize_mxfp4, True), "mxfp6_rot": _mx("enable_mxfp6", ops.quantize_mxfp6, True)}.items()}

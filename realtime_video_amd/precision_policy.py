@@ -56,15 +56,18 @@ def resolve(policy, num_layers, widths=None):
             raise ValueError(f"precision policy: {key!r} names layer {int(m.group(1))} of a model with {num_layers} layers")
         modes[f"L{int(m.group(1))}.{m.group(2)}"] = modes.pop(key)      # ("L01.qkv" is "L1.qkv")
     default = modes.get("default", 0)
-    out = []
-    for name in linear_names(num_layers):
-        kind = name.split(".")[-1]
-        mode = modes.get(name, modes.get(kind, default))
-        if widths is not None and widths[kind] % K_MULTIPLE[mode]:
-            raise ValueError(f"precision policy: {name} has input width {widths[kind]}, {MODE_NAMES[mode]} needs a multiple of "
-                             f"{K_MULTIPLE[mode]}")
-        out.append(mode)
+    out = [modes.get(name, modes.get(name.split(".")[-1], default)) for name in linear_names(num_layers)]
+    if widths is not None:
+        check_widths(out, num_layers, widths, "precision policy")
     return out
+
+
+def check_widths(modes, num_layers, widths, who):
+    """ValueError, in the name of `who`, for the first Linear whose input width (`widths`: linear_widths()) its mode cannot take."""
+    for name, mode in zip(linear_names(num_layers), modes):
+        width = widths[name.split(".")[-1]]
+        if width % K_MULTIPLE[mode]:
+            raise ValueError(f"{who}: {name} has input width {width}, {MODE_NAMES[mode]} needs a multiple of {K_MULTIPLE[mode]}")
 
 
 def named(modes, num_layers):

@@ -76,6 +76,29 @@ def test_uniform_policy_equals_the_pure_mode_bit_for_bit(mode):
     assert not _same(outs, _pure_outputs("bf16"))
 
 
+@pytest.mark.parametrize("mode", list(PURE))
+def test_uniform_policy_prepares_the_state_of_the_pure_mode(mode):
+    """Test 1 compares outputs; this one the prepared state, without a forward: after the enable_* call and after the uniform policy
+    every Linear weight has the same dtype, shape and bits, the scale stores the same keys and bits, the per-tensor scales are equal,
+    and rtv_dit_config.use_fp8 is the mode's number and 7."""
+    from realtime_video_amd import precision_policy as pp
+    a, _ = _build(_weights())
+    PURE[mode](a)
+    b, _ = _build(_weights())
+    b.set_linear_precision({"default": mode})
+    torch.cuda.synchronize()
+    assert a._cfg.use_fp8 == pp.MODE_NAMES.index(mode) and b._cfg.use_fp8 == 7
+    for name in pp.linear_names(L):
+        x, y = a._tensors[name + "_w"], b._tensors[name + "_w"]
+        assert x.dtype == y.dtype != BF and x.shape == y.shape and torch.equal(x.view(torch.uint8), y.view(torch.uint8)), name
+    for store in ("_mx_scales", "_fp8_row_scales"):
+        sa, sb = getattr(a, store), getattr(b, store)
+        assert list(sa) == list(sb), store
+        assert all(sa[k].dtype == sb[k].dtype and sa[k].shape == sb[k].shape and torch.equal(sa[k], sb[k]) for k in sa), store
+    assert len(a._mx_scales) + len(a._fp8_row_scales) == (0 if mode == "fp8" else 6 + 8 * L)
+    assert list(a._fp8_scales) == list(b._fp8_scales) and (all(s > 0 for s in a._fp8_scales) if mode == "fp8" else not any(a._fp8_scales))
+
+
 # ----------------------------------------------------------------------------------------- 2. no leak into unselected Linears
 @pytest.mark.parametrize("mode", ["mxfp4", "mxfp6"])
 def test_unselected_linears_stay_bf16_bit_for_bit(mode):
