@@ -79,8 +79,8 @@ int rtv_attn_fwd_fp8(const void* q, const void* k8, const void* v8t, void* o, in
  * writes into its cache - behind the RoPE / cache kernel and the direct V GEMM, by the ring mapping of the write (two ranges when it
  * wraps), in the kv_only pass too - into shadow->k8[l] / v8t[l], then attends the key window of the step with rtv_attn_fwd_fp8.
  * Cross-attention and everything else are rtv_dit_forward's launches; rtv_dit_forward itself issues exactly what it issued before.
- * The sharded phase API has no fp8 form: a step with row_count < M or attn_kv_splits > 1 is an error here that says so, never a
- * bf16 run. */
+ * A step with row_count < M or attn_kv_splits > 1 is an error here that says so, never a bf16 run: sharded and split steps go
+ * through the phases of rtv_hip_attn_fp8_cp.h. */
 int rtv_dit_forward_attn_fp8(const rtv_dit_config* cfg, const rtv_dit_weights* w, const rtv_dit_step* step,
                              const rtv_attn_fp8_shadow* shadow, void* workspace, size_t workspace_bytes, rtv_stream_t stream);
 

@@ -149,6 +149,7 @@ class CausalWanModel:
         self._fp8_attn = None         # (k_scale, v_scale, epoch) while enable_fp8_attention() is on
         self._fp8_attn_epoch = 0      # bumps at every enable / disable: a shadow filled before it is refilled from the bf16 cache
         self._fp8_attn_amax = None    # float32 [num_layers, 2], allocated once
+        self._fp8_attn_cp = False           # enable_fp8_attention(context_parallel=True): sharded forwards run in fp8 instead of raising
         self._fp8_attn_smooth = False       # enable_fp8_attention(smooth_k=True): the K codes of the shadows are those of k - centre
         self._fp8_attn_center = None        # float32 [num_layers, H, 128], zero-filled, allocated once; fp8_attention_recenter() writes it
         self._fp8_attn_center_ws = None     # workspace of the mean kernel, allocated with the centre
@@ -455,7 +456,7 @@ class CausalWanModel:
             return _BF16
         return self._linear_modes[i] if self._cfg.use_fp8 == _MIXED else self._cfg.use_fp8
 
-    def enable_fp8_attention(self, k_scale=1.0, v_scale=1.0, smooth_k=False):
+    def enable_fp8_attention(self, k_scale=1.0, v_scale=1.0, smooth_k=False, context_parallel=False):
         """Opt-in: self-attention in the precision of the reference's SageAttention backend (wan/modules/sage.py: 8-bit Q K^T, fp8
         P V) on an OCP e4m3 shadow of the KV cache (include/rtv_hip_attn_fp8.h).  Independent of enable_fp8(), which concerns the
         Linears; cross-attention and the VAE stay as they are.  K / V codes are e4m3(x / scale) with one scale per tensor kind, Q is
@@ -482,7 +483,17 @@ class CausalWanModel:
         the shadows; GenerationSession does it once, behind its first block.  The centres outlive disable / enable.  Measured on
         synthetic keys and synthetic weights only: no real checkpoint was available.
 
-        Under context parallelism the forward raises: the sharded phases and the KV split have no fp8 kernels."""
+        Under context parallelism the forward raises unless context_parallel=True (opt-in; include/rtv_hip_attn_fp8_cp.h).  Then the
+        sharded phases run in fp8: behind each layer's exchange a rank quantises the block's rows into its shadow - the row exchange
+        keeps the full-head shadow described above, every rank quantising the gathered rows itself; the head exchange keeps one
+        dense num_heads / world-head shadow per local rank in the cache dict ("k8_hp", "v8t_hp"), filled from the rank's head slice
+        whether the cache holds kv_cache_heads() heads or all of them - and ContextParallel.attn_kv_splits > 1 selects the KV split
+        of the fp8 kernel.  With attn_kv_splits = 1 a sharded forward computes bit for bit what the unsharded one computes.  A
+        rolling cache under context parallelism shift-copies its rows; the shadows are then stale and the same forward refills them
+        whole before it runs.  smooth_k=True together with context_parallel=True is a ValueError: centres under sharding are not
+        built.  Not measured on more than one GPU."""
+        if smooth_k and context_parallel:
+            raise ValueError("enable_fp8_attention: smooth_k=True is not supported together with context_parallel=True")
         k_scale, v_scale = float(k_scale), float(v_scale)
         for s in (k_scale, v_scale):
             if not (math.isfinite(s) and s > 0):
@@ -490,6 +501,7 @@ class CausalWanModel:
         self._fp8_attn_epoch += 1
         self._fp8_attn = (k_scale, v_scale, self._fp8_attn_epoch)
         self._fp8_attn_smooth = bool(smooth_k)
+        self._fp8_attn_cp = bool(context_parallel)
         return self
 
     def disable_fp8_attention(self):
@@ -531,16 +543,19 @@ class CausalWanModel:
         return self
 
     def _fp8_attention_shadow(self, kv_cache, use_cp):
-        """The rtv_attn_fp8_shadow of this forward (None: bf16 attention) and what must stay alive with it."""
+        """The rtv_attn_fp8_shadow of this forward (None: bf16 attention) and what must stay alive with it.  Under the head exchange
+        of a context-parallel forward: a list, one shadow per local rank."""
         if self._fp8_attn is None:
             return None, None
-        if use_cp:
+        if use_cp and not self._fp8_attn_cp:
             raise RuntimeError("fp8 attention does not support context parallelism (sharded calls and the KV split have no fp8 kernels)")
         k_scale, v_scale, epoch = self._fp8_attn
         L = self.num_layers
         if self._fp8_attn_amax is None:
             self._fp8_attn_amax = torch.zeros(L, 2, dtype=torch.float32, device=kv_cache[0]["k"].device)
         rows = kv_cache[0]["k"].shape[1]
+        if use_cp and self.context_parallel.head_exchange(self.num_heads):
+            return self._fp8_attention_shadow_heads(kv_cache, rows)
         smooth = self._fp8_attn_smooth
         if smooth:
             k0 = kv_cache[0]["k"]
@@ -574,6 +589,40 @@ class CausalWanModel:
         if smooth:
             arrs.append((c_vp * L)(*[self._fp8_attn_center[l].data_ptr() for l in range(L)]))
         return sh, (sh, arrs)
+
+    def _fp8_attention_shadow_heads(self, kv_cache, rows):
+        """Head exchange: per layer and local rank one dense shadow of the num_heads / world heads the rank owns ("k8_hp" / "v8t_hp" of
+        the cache dict, allocated once), filled from the rank's head slice of the bf16 cache.  -> ([shadow per local rank], keep)."""
+        cp = self.context_parallel
+        k_scale, v_scale, epoch = self._fp8_attn
+        L, H, W = self.num_layers, self.num_heads, cp.world
+        hn = H // W
+        ranks = list(cp.local_ranks())
+        for l, c in enumerate(kv_cache):
+            Hc = c["k"].shape[2]
+            if c["k"].shape[0] != 1 or c["k"].shape[1] != rows or Hc not in (hn, H):
+                raise ValueError(f"fp8 attention: batch size 1, the same number of rows in every layer's KV cache, and {hn} (this rank's) or {H} heads")
+            hp = c.get("k8_hp")
+            if hp is None or len(hp) != len(ranks) or tuple(hp[0].shape[:2]) != (rows, hn) or hp[0].device != c["k"].device:
+                pairs = [ops.attn_fp8_shadow(rows, hn, c["k"].device) for _ in ranks]
+                c["k8_hp"], c["v8t_hp"] = [p[0] for p in pairs], [p[1] for p in pairs]
+                c["fp8_filled"] = None
+            state = (k_scale, v_scale, epoch, c["k"].data_ptr(), c["v"].data_ptr(), "heads", tuple(ranks), Hc)
+            if c.get("fp8_filled") != state:
+                for i, r in enumerate(ranks):
+                    h0 = 0 if Hc == hn else r * hn
+                    ops.attn_quantize_kv(c["k"][0][:, h0:h0 + hn], c["v"][0][:, h0:h0 + hn], c["k8_hp"][i], c["v8t_hp"][i], 0, rows, k_scale,
+                                         v_scale, amax=self._fp8_attn_amax[l])
+                c["fp8_filled"] = state
+        pp = ctypes.POINTER(c_vp)
+        amax = (c_vp * L)(*[self._fp8_attn_amax[l].data_ptr() for l in range(L)])
+        shs, arrs = [], [amax]
+        for i in range(len(ranks)):
+            a8 = (c_vp * L)(*[c["k8_hp"][i].data_ptr() for c in kv_cache])
+            av = (c_vp * L)(*[c["v8t_hp"][i].data_ptr() for c in kv_cache])
+            arrs += [a8, av]
+            shs.append(_Fp8Shadow(ctypes.cast(a8, pp), ctypes.cast(av, pp), rows, k_scale, v_scale, ctypes.cast(amax, pp)))
+        return shs, (shs, arrs)
 
     @staticmethod
     def _quantize_fp8(w):
@@ -881,6 +930,8 @@ class CausalWanModel:
                 for c in kv_cache:
                     for n in ("k", "v"):
                         c[n][:, s0:s0 + ro] = c[n][:, s0 + ev:s0 + ev + ro].clone()
+                    if "fp8_filled" in c:
+                        c["fp8_filled"] = None      # the e4m3 shadows no longer mirror the rows: the next look at them refills them whole
             for c in kv_cache:
                 c["global_end_index"] = current_end
                 c["local_end_index"] = local_end
@@ -966,9 +1017,14 @@ class CausalWanModel:
                                      "and one common row stride")
 
         fp8_shadow, fp8_keep = self._fp8_attention_shadow(kv_cache, use_cp)
-        # (the unsharded forward with the shadows as an argument; the phase API of the context-parallel path has no fp8 form)
-        forward = ("rtv_dit_forward",) if fp8_shadow is None else ("rtv_dit_forward_attn_fp8", ctypes.byref(fp8_shadow))
-        fp8_key = (self._fp8_attn[:2] + (kv_cache[0]["k8"].data_ptr(), kv_cache[-1]["v8t"].data_ptr())) if fp8_shadow is not None else None
+        # (the unsharded forward with the shadows as an argument; the context-parallel path has phases of its own, run_cp below)
+        forward = ("rtv_dit_forward",) if fp8_shadow is None or use_cp else ("rtv_dit_forward_attn_fp8", ctypes.byref(fp8_shadow))
+        if fp8_shadow is None:
+            fp8_key = None
+        elif isinstance(fp8_shadow, list):      # head exchange: one shadow per local rank
+            fp8_key = self._fp8_attn[:2] + ("heads", kv_cache[0]["k8_hp"][0].data_ptr(), kv_cache[-1]["v8t_hp"][-1].data_ptr())
+        else:
+            fp8_key = self._fp8_attn[:2] + (kv_cache[0]["k8"].data_ptr(), kv_cache[-1]["v8t"].data_ptr())
         if fp8_shadow is not None and self._fp8_attn_smooth:      # the centred entry point: the centre table behind the shadow
             forward = ("rtv_dit_forward_attn_fp8_centered", ctypes.byref(fp8_shadow), fp8_keep[1][3])
             fp8_key += (self._fp8_attn_center.data_ptr(),)
@@ -1007,6 +1063,8 @@ class CausalWanModel:
             ops.ensure_gemm_workspace(u.device)
         if use_cp:
             commit()          # the exchanges below address the (shifted) cache rows
+            if fp8_shadow is not None and any(c.get("fp8_filled") is None for c in kv_cache):
+                fp8_shadow, fp8_keep = self._fp8_attention_shadow(kv_cache, use_cp)      # a shift copy: refill, in place
         if not use_cp:
             graph_key = None
             if self.use_hip_graphs and not need_cross:
@@ -1058,7 +1116,7 @@ class CausalWanModel:
             if self.use_hip_graphs and not need_cross and not getattr(cp, "_gloo", False):
                 graph_key = ("cp", id(cp), bool(getattr(cp, "overlap", True)), cp.world, cp.head_exchange(self.num_heads), F, gh, gw, row0, lo, hi, start_frame, causal_block, kv_only,
                              text_rows, fold_k, int(self.gemm_tile_cfg), rs, self._weights_version, splits,
-                             kv_cache[0]["k"].data_ptr(), kv_cache[-1]["v"].data_ptr(), crossattn_cache[0]["k"].data_ptr())
+                             kv_cache[0]["k"].data_ptr(), kv_cache[-1]["v"].data_ptr(), crossattn_cache[0]["k"].data_ptr(), fp8_key)
                 ent = self._graphs.get(graph_key)
                 if isinstance(ent, dict):
                     ent["u"].copy_(u)
@@ -1074,6 +1132,13 @@ class CausalWanModel:
                 W, H = cp.world, self.num_heads
                 heads = cp.head_exchange(H)
                 keep = []
+                # fp8 attention (rtv_hip_attn_fp8_cp.h): one shadow per local rank - the head exchange's own, or the full-head one
+                fp8 = None if fp8_shadow is None else [ctypes.byref(s_) for s_ in
+                                                       (fp8_shadow if heads else [fp8_shadow] * len(cp.local_ranks()))]
+
+                def quantize_block(l, nheads):      # a pass that stops behind the exchange: the delivered rows into the shadows
+                    for (st, _), sh in zip(parts, fp8):
+                        _lib.call("rtv_dit_quantize_block_attn_fp8", cfg_p, ctypes.byref(st), l, nheads, sh, stream)
                 if heads:
                     # head exchange: every rank's step addresses the cache heads it owns (the whole cache when it was
                     # allocated with kv_cache_heads() heads, a head slice of a full-head cache otherwise)
@@ -1105,18 +1170,25 @@ class CausalWanModel:
                         pend = cp.gather_kv(kv_cache[l]["k"][0], kv_cache[l]["v"][0], row0, M, async_op=True)
                         if last_kv_only:
                             pend.wait()
+                            if fp8:
+                                quantize_block(l, H)
                             break
                         for st, wsa in parts:
                             _lib.call("rtv_dit_layer_proj", cfg_p, w_p, ctypes.byref(st), l, PROJ_Q, 0, null, null, *wsa)
                         pend.wait()
-                        for st, wsa in parts:
-                            _lib.call("rtv_dit_layer_rest", cfg_p, w_p, ctypes.byref(st), l, *wsa)
+                        for i, (st, wsa) in enumerate(parts):
+                            if fp8:
+                                _lib.call("rtv_dit_layer_rest_attn_fp8", cfg_p, w_p, ctypes.byref(st), l, fp8[i], *wsa)
+                            else:
+                                _lib.call("rtv_dit_layer_rest", cfg_p, w_p, ctypes.byref(st), l, *wsa)
                         continue
                     if last_kv_only:
                         for (st, wsa), (_, b) in zip(parts, bufs):
                             _lib.call("rtv_dit_layer_proj", cfg_p, w_p, ctypes.byref(st), l, PROJ_LN | PROJ_KV, W, null,
                                       c_vp(b["kv_send"].data_ptr()), *wsa)
                         cp.exchange_kv(bufs, kv_cache[l]["k"][0], kv_cache[l]["v"][0], row0, M)
+                        if fp8:
+                            quantize_block(l, hn)
                         break
                     for (st, wsa), (_, b) in zip(parts, bufs):
                         _lib.call("rtv_dit_layer_proj", cfg_p, w_p, ctypes.byref(st), l, PROJ_LN | PROJ_Q, W,
@@ -1127,9 +1199,13 @@ class CausalWanModel:
                                   c_vp(b["kv_send"].data_ptr()), *wsa)
                     pend_kv = cp.exchange_kv(bufs, kv_cache[l]["k"][0], kv_cache[l]["v"][0], row0, M, async_op=True)
                     wait_in_order(pend_q, pend_kv)      # one join with the communication stream (parallel.wait_in_order)
-                    for (st, wsa), (_, b) in zip(parts, bufs):
-                        _lib.call("rtv_dit_layer_attn_hp", cfg_p, w_p, ctypes.byref(st), l, W, c_vp(b["q_all"].data_ptr()),
-                                  c_vp(b["o_all"].data_ptr()), *wsa)
+                    for i, ((st, wsa), (_, b)) in enumerate(zip(parts, bufs)):
+                        if fp8:
+                            _lib.call("rtv_dit_layer_attn_hp_attn_fp8", cfg_p, w_p, ctypes.byref(st), l, W, c_vp(b["q_all"].data_ptr()),
+                                      c_vp(b["o_all"].data_ptr()), fp8[i], *wsa)
+                        else:
+                            _lib.call("rtv_dit_layer_attn_hp", cfg_p, w_p, ctypes.byref(st), l, W, c_vp(b["q_all"].data_ptr()),
+                                      c_vp(b["o_all"].data_ptr()), *wsa)
                     cp.exchange_o(bufs)
                     for (st, wsa), (_, b) in zip(parts, bufs):
                         _lib.call("rtv_dit_layer_rest_hp", cfg_p, w_p, ctypes.byref(st), l, W, c_vp(b["o_recv"].data_ptr()), *wsa)
@@ -1141,7 +1217,7 @@ class CausalWanModel:
                     _lib.call("rtv_dit_finish", cfg_p, ctypes.byref(parts[0][0]), c_vp(hrow.data_ptr()), stream)
 
             if graph_key is not None and self._graphs.get(graph_key) == "seen":
-                ent = {"u": u.clone(), "t": tt.clone(), "out": out, "keep": (kk_keep, kv_keep, ck_keep, cv_keep)}
+                ent = {"u": u.clone(), "t": tt.clone(), "out": out, "keep": (kk_keep, kv_keep, ck_keep, cv_keep, fp8_keep)}
                 u, tt = ent["u"], ent["t"]
                 g = torch.cuda.CUDAGraph()
                 if not hasattr(self, "_capture_stream"):

@@ -15,10 +15,12 @@
 //     * Q is quantised in the prologue, one scale per (row, head): the lane and its partner lane ^ 32 hold the row.
 #include <cmath>
 
+#include <string>
 #include <type_traits>
 
 #include "../../include/rtv_hip_attn_fp8.h"
 #include "../../include/rtv_hip_attn_fp8_center.h"
+#include "../../include/rtv_hip_attn_fp8_cp.h"
 #include "attn_common.h"
 #include "fp8_quant.h"
 
@@ -80,6 +82,12 @@ struct FwdParams {
   float v_scale;
   int causal_block, q_offset;
   int n_qtiles;
+};
+// KV split (rtv_hip_attn_fp8_cp.h): blockIdx.y = range s of kv_splits; the partials in the layout of attn_common.h's store_partial
+struct FwdParamsSplit : FwdParams {
+  int kv_splits;
+  float* part_o;    // [S][H][Lq][128] unnormalised fp32 O, without v_scale
+  float* part_ml;   // [S][H][Lq][2] = (m, l), m in the row's scaled log2 domain
 };
 }  // namespace af8
 
@@ -214,7 +222,11 @@ __global__ __launch_bounds__(ATT_D) void attn_kv_center_reduce_kernel(af8::Cente
   p.center[(size_t)h * ATT_D + d] = s / (float)(p.n0 + p.n1);
 }
 
-__global__ __launch_bounds__(af8::NW * 64) void attn_fwd_fp8_kernel(af8::FwdParams p) {
+// SPLIT: the workgroup (blockIdx.x as before, range s = blockIdx.y of S) works on the storage tiles [ntiles s / S, ntiles (s + 1) / S)
+// of its own tile list - split_tile_range's rule - and leaves (m, l, unnormalised O) through store_partial; attn_fp8_combine_kernel
+// merges.  An empty range loads nothing, touches no LDS and leaves (-1e30, 0, 0), as a row does whose keys in the range are all masked.
+template <bool SPLIT>
+__global__ __launch_bounds__(af8::NW * 64) void attn_fwd_fp8_kernel(std::conditional_t<SPLIT, af8::FwdParamsSplit, af8::FwdParams> p) {
   using namespace af8;
   // smem: K[2][8 KiB] | V^T[2][8 KiB]
   __shared__ __attribute__((aligned(16))) char smem[4 * TILE_BYTES];
@@ -258,6 +270,12 @@ __global__ __launch_bounds__(af8::NW * 64) void attn_fwd_fp8_kernel(af8::FwdPara
   const int ta1 = p.row1 >> 6, nt1 = p.n1 > 0 ? ((p.row1 + p.n1 - 1) >> 6) - ta1 + 1 : 0;
   const int ntiles = nt0 + nt1;
   auto tile_of = [&](int j) { return j < nt0 ? ta0 + j : ta1 + (j - nt0); };
+  int t_lo = 0, t_hi = ntiles;   // this workgroup's share of its tile list (workgroup-uniform)
+  if constexpr (SPLIT) {
+    t_lo = ntiles * (int)blockIdx.y / p.kv_splits;
+    t_hi = ntiles * ((int)blockIdx.y + 1) / p.kv_splits;
+  }
+  const bool work = !SPLIT || t_lo < t_hi;
 
   // ---- staging: one 16-byte chunk of K and one of V^T per thread and tile.  K rows beyond the cache (the last storage tile) are
   //      clamped: they are outside every window.  A v8t tile is whole by construction.
@@ -275,7 +293,7 @@ __global__ __launch_bounds__(af8::NW * 64) void attn_fwd_fp8_kernel(af8::FwdPara
     *(u32x4*)(k_wr + buf * TILE_BYTES) = kreg;
     *(u32x4*)(v_wr + buf * TILE_BYTES) = vreg;
   };
-  load_tile(0);
+  if (work) load_tile(t_lo);
 
   // ---- Q^T fragments (MFMA B operand): lane holds the codes of Q[q][64 st + 32 g .. + 32], st = 0, 1; the row's scale comes from
   //      the maximum over this lane's 64 values and those of lane ^ 32
@@ -340,7 +358,7 @@ __global__ __launch_bounds__(af8::NW * 64) void attn_fwd_fp8_kernel(af8::FwdPara
 
   auto tile = [&](const int j, auto bufc) {
     constexpr int buf = decltype(bufc)::value;
-    const bool has_next = (j + 1 < ntiles);
+    const bool has_next = (j + 1 < t_hi);
     if (has_next) load_tile(j + 1);  // in flight during the MFMAs below
 
     // ---------------- S^T = K . Q^T   (two independent accumulator chains)
@@ -441,15 +459,27 @@ __global__ __launch_bounds__(af8::NW * 64) void attn_fwd_fp8_kernel(af8::FwdPara
     __syncthreads();
   };
 
-  write_tile(0);
-  __syncthreads();
-  for (int j = 0; j < ntiles; j += 2) {
+  if (work) {
+    write_tile(0);
+    __syncthreads();
+  }
+  for (int j = t_lo; j < t_hi; j += 2) {
     tile(j, IntC<0>{});
-    if (j + 1 < ntiles) tile(j + 1, IntC<1>{});
+    if (j + 1 < t_hi) tile(j + 1, IntC<1>{});
   }
 
   // ---------------- epilogue: O = O^T * v_scale / l, lane owns row q and dims db*32 + 8*i + 4*g + {0..3}
   const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
+  if constexpr (SPLIT) {
+    AttnParams ap;   // what store_partial reads
+    ap.B = 1;
+    ap.H = p.H;
+    ap.Lq = p.Lq;
+    ap.part_o = p.part_o;
+    ap.part_ml = p.part_ml;
+    store_partial(ap, h, q_row, g, oacc, m_run, l_tot);
+    return;
+  }
   const float inv = p.v_scale / l_tot;
   if (q_row < p.Lq) {
     uint16_t* op = p.o + (size_t)q_row * p.o_rs + (size_t)h * ATT_D + 4 * g;
@@ -463,6 +493,40 @@ __global__ __launch_bounds__(af8::NW * 64) void attn_fwd_fp8_kernel(af8::FwdPara
         *(u32x2*)(op + db * 32 + i * 8) = w;
       }
   }
+}
+
+// Merge of the S partial results of a row (the rule of attn_combine_kernel, attn_fwd.hip, with the V scale): m = max m_s,
+// w_s = 2^(m_s - m), O = v_scale sum w_s O_s / sum w_s l_s, rounded once to bf16.  16 threads per row (8 dims each), 16 rows per
+// workgroup; the ranges in ascending order, no atomics.
+__global__ __launch_bounds__(256) void attn_fp8_combine_kernel(const float* __restrict__ part_o, const float* __restrict__ part_ml,
+                                                               uint16_t* __restrict__ o, int S, int H, int Lq, int64_t o_rs,
+                                                               float v_scale) {
+  const int64_t nrows = (int64_t)H * Lq;
+  const int64_t row = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
+  if (row >= nrows) return;
+  const int c8 = (threadIdx.x & 15) * 8;
+  float m = -INFINITY;
+  for (int s = 0; s < S; ++s) m = fmaxf(m, part_ml[((int64_t)s * nrows + row) * 2]);
+  float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  float l = 0.f;
+  for (int s = 0; s < S; ++s) {
+    const f32x2 ml = *(const f32x2*)(part_ml + ((int64_t)s * nrows + row) * 2);
+    const float w = __builtin_amdgcn_exp2f(ml[0] - m);
+    l += w * ml[1];
+    const float* po = part_o + ((int64_t)s * nrows + row) * ATT_D + c8;
+    const f32x4 a = *(const f32x4*)po, b2 = *(const f32x4*)(po + 4);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      acc[i] += w * a[i];
+      acc[4 + i] += w * b2[i];
+    }
+  }
+  const float inv = v_scale / l;
+  const int h = (int)(row / Lq), q = (int)(row - (int64_t)h * Lq);
+  u32x4 out;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) out[i] = pack_bf16x2(acc[2 * i] * inv, acc[2 * i + 1] * inv);
+  *(u32x4*)(o + (size_t)q * o_rs + (size_t)h * ATT_D + c8) = out;
 }
 
 static bool good_scale(float s) { return std::isfinite(s) && s > 0.f; }
@@ -557,23 +621,29 @@ extern "C" int rtv_attn_kv_center(const void* k, int64_t row_stride, int row0, i
   return check_launch("attn_kv_center");
 }
 
-extern "C" int rtv_attn_fwd_fp8(const void* q, const void* k8, const void* v8t, void* o, int Lq, int H, int cache_rows, int row0,
-                                int n0, int row1, int n1, int64_t q_row_stride, int64_t o_row_stride, float scale, float k_scale,
-                                float v_scale, int causal_block, int q_offset, rtv_stream_t stream) {
-  if (!q || !k8 || !v8t || !o) return set_error(-1, "attn_fwd_fp8: null pointer");
-  if (((uintptr_t)q | (uintptr_t)k8 | (uintptr_t)v8t | (uintptr_t)o) & 15)
-    return set_error(-1, "attn_fwd_fp8: base pointers must be 16-byte aligned");
-  if (Lq <= 0 || H <= 0 || n0 <= 0 || cache_rows <= 0) return set_error(-1, "attn_fwd_fp8: Lq, H, n0 and cache_rows must be positive");
-  if (n1 < 0) return set_error(-1, "attn_fwd_fp8: negative segment length");
-  if (causal_block < 0 || q_offset < 0) return set_error(-1, "attn_fwd_fp8: negative mask parameters");
-  if (causal_block > 0 && n1 > 0) return set_error(-1, "attn_fwd_fp8: the block-causal mask needs a one-segment window");
+// The checks and the launches of rtv_attn_fwd_fp8 (kv_splits == 1, no workspace) and of rtv_attn_fwd_fp8_split.
+static int attn_fwd_fp8_launch(const char* who, const void* q, const void* k8, const void* v8t, void* o, int Lq, int H, int cache_rows,
+                               int row0, int n0, int row1, int n1, int64_t q_row_stride, int64_t o_row_stride, float scale,
+                               float k_scale, float v_scale, int causal_block, int q_offset, int kv_splits, void* workspace,
+                               size_t workspace_bytes, rtv_stream_t stream) {
+  auto fail = [&](const char* what) { return set_error(-1, (std::string(who) + ": " + what).c_str()); };
+  if (!q || !k8 || !v8t || !o) return fail("null pointer");
+  if (((uintptr_t)q | (uintptr_t)k8 | (uintptr_t)v8t | (uintptr_t)o) & 15) return fail("base pointers must be 16-byte aligned");
+  if (Lq <= 0 || H <= 0 || n0 <= 0 || cache_rows <= 0) return fail("Lq, H, n0 and cache_rows must be positive");
+  if (n1 < 0) return fail("negative segment length");
+  if (causal_block < 0 || q_offset < 0) return fail("negative mask parameters");
+  if (causal_block > 0 && n1 > 0) return fail("the block-causal mask needs a one-segment window");
   if (row0 < 0 || (int64_t)row0 + n0 > cache_rows || (n1 > 0 && (row1 < 0 || (int64_t)row1 + n1 > cache_rows)))
-    return set_error(-1, "attn_fwd_fp8: key range outside [0, cache_rows)");
+    return fail("key range outside [0, cache_rows)");
   if (q_row_stride < (int64_t)H * ATT_D || o_row_stride < (int64_t)H * ATT_D || ((q_row_stride | o_row_stride) & 7))
-    return set_error(-1, "attn_fwd_fp8: row strides must be multiples of 8 elements and hold H heads");
+    return fail("row strides must be multiples of 8 elements and hold H heads");
   if (!good_scale(scale) || !good_scale(k_scale) || !good_scale(v_scale))
-    return set_error(-1, "attn_fwd_fp8: scale, k_scale and v_scale must be finite and positive");
-  af8::FwdParams p;
+    return fail("scale, k_scale and v_scale must be finite and positive");
+  if (kv_splits < 1 || kv_splits > 16) return fail("kv_splits must be 1..16");
+  // never more ranges than storage tiles in the window; one range = the plain launch
+  const int win_tiles = (((row0 + n0 - 1) >> 6) - (row0 >> 6) + 1) + (n1 > 0 ? ((row1 + n1 - 1) >> 6) - (row1 >> 6) + 1 : 0);
+  if (kv_splits > win_tiles) kv_splits = win_tiles;
+  af8::FwdParamsSplit p;
   p.q = (const uint16_t*)q;
   p.k8 = (const uint8_t*)k8;
   p.v8t = (const uint8_t*)v8t;
@@ -592,8 +662,42 @@ extern "C" int rtv_attn_fwd_fp8(const void* q, const void* k8, const void* v8t, 
   p.causal_block = causal_block;
   p.q_offset = q_offset;
   p.n_qtiles = (Lq + af8::QT - 1) / af8::QT;
+  p.kv_splits = kv_splits;
+  p.part_o = nullptr;
+  p.part_ml = nullptr;
+  if (kv_splits > 1) {
+    const size_t rows = (size_t)kv_splits * H * Lq;
+    if (!workspace || ((uintptr_t)workspace & 15) || workspace_bytes < rows * (ATT_D + 2) * sizeof(float))
+      return fail("split workspace missing, misaligned or too small (rtv_attn_split_workspace_bytes)");
+    p.part_o = (float*)workspace;
+    p.part_ml = p.part_o + rows * ATT_D;
+  }
   const int64_t lkv = (int64_t)n0 + n1;
   ProfScope prof(PROF_ATTN, (hipStream_t)stream, 4.0 * Lq * (double)lkv * ATT_D * H * (causal_block > 0 ? 0.5 : 1.0));
-  hipLaunchKernelGGL(attn_fwd_fp8_kernel, dim3(H * p.n_qtiles), dim3(af8::NW * 64), 0, (hipStream_t)stream, p);
-  return check_launch("attn_fwd_fp8");
+  if (kv_splits == 1) {
+    hipLaunchKernelGGL(attn_fwd_fp8_kernel<false>, dim3(H * p.n_qtiles), dim3(af8::NW * 64), 0, (hipStream_t)stream,
+                       (const af8::FwdParams&)p);
+    return check_launch(who);
+  }
+  hipLaunchKernelGGL(attn_fwd_fp8_kernel<true>, dim3(H * p.n_qtiles, kv_splits), dim3(af8::NW * 64), 0, (hipStream_t)stream, p);
+  if (int st = check_launch(who)) return st;
+  const int64_t nrows = (int64_t)H * Lq;
+  hipLaunchKernelGGL(attn_fp8_combine_kernel, dim3((unsigned)((nrows + 15) / 16)), dim3(256), 0, (hipStream_t)stream, p.part_o,
+                     p.part_ml, p.o, kv_splits, H, Lq, p.o_rs, v_scale);
+  return check_launch("attn_fp8_combine");
+}
+
+extern "C" int rtv_attn_fwd_fp8(const void* q, const void* k8, const void* v8t, void* o, int Lq, int H, int cache_rows, int row0,
+                                int n0, int row1, int n1, int64_t q_row_stride, int64_t o_row_stride, float scale, float k_scale,
+                                float v_scale, int causal_block, int q_offset, rtv_stream_t stream) {
+  return attn_fwd_fp8_launch("attn_fwd_fp8", q, k8, v8t, o, Lq, H, cache_rows, row0, n0, row1, n1, q_row_stride, o_row_stride, scale,
+                             k_scale, v_scale, causal_block, q_offset, 1, nullptr, 0, stream);
+}
+
+extern "C" int rtv_attn_fwd_fp8_split(const void* q, const void* k8, const void* v8t, void* o, int Lq, int H, int cache_rows,
+                                      int row0, int n0, int row1, int n1, int64_t q_row_stride, int64_t o_row_stride, float scale,
+                                      float k_scale, float v_scale, int causal_block, int q_offset, int kv_splits, void* workspace,
+                                      size_t workspace_bytes, rtv_stream_t stream) {
+  return attn_fwd_fp8_launch("attn_fwd_fp8_split", q, k8, v8t, o, Lq, H, cache_rows, row0, n0, row1, n1, q_row_stride, o_row_stride,
+                             scale, k_scale, v_scale, causal_block, q_offset, kv_splits, workspace, workspace_bytes, stream);
 }

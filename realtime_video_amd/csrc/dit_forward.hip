@@ -18,6 +18,7 @@
 
 #include "../../include/rtv_hip_attn_fp8.h"
 #include "../../include/rtv_hip_attn_fp8_center.h"
+#include "../../include/rtv_hip_attn_fp8_cp.h"
 #include "../../include/rtv_hip_mxfp4.h"
 #include "../../include/rtv_hip_mxfp6.h"
 #include "../../include/rtv_hip_mx_rotate.h"
@@ -160,7 +161,8 @@ struct Ctx {
   DitBuffers b;
   rtv_stream_t stream;
   int d, H, L, ffn, hd, F, gh, gw, fs, M, r0, rc, tc;
-  const rtv_attn_fp8_shadow* fp8;   // rtv_dit_forward_attn_fp8: self-attention on the e4m3 shadows; null in every other entry point
+  const rtv_attn_fp8_shadow* fp8;   // rtv_dit_forward_attn_fp8 and the sharded phases of rtv_hip_attn_fp8_cp.h: self-attention on the
+                                    // e4m3 shadows; null in every other entry point
   void* const* centers;             // rtv_dit_forward_attn_fp8_centered: per-layer K centres of the shadows; null in every other one
   const uint8_t* modes;  // use_fp8 == 7: the mode of each Linear (linear_modes, checked by make_ctx); null otherwise
   int fold_kh, fold_k;   // cross-attention V folded into the output projection: columns per head / in all; 0 = the unfolded path
@@ -545,13 +547,11 @@ static int dit_layer_proj(Ctx& c, int l, int parts, int world, void* q_send, voi
   return 0;
 }
 
-// fp8 attention: the physical cache rows this call has just written (the ring mapping of the write: sink rows as they are, ring
-// rows rotated, at most one wrap) go into the layer's e4m3 shadow.
-static int quantize_written_rows(Ctx& c, int l) {
-  const rtv_dit_step* st = c.st;
-  const rtv_attn_fp8_shadow* sh = c.fp8;
+// fp8 attention: the physical cache rows of the logical rows [a, a + n) of layer l (the ring mapping of the write: sink rows as
+// they are, ring rows rotated, at most one wrap) go into the layer's e4m3 shadow, `heads` heads of them.
+static int quantize_cache_rows(const rtv_dit_step* st, const rtv_attn_fp8_shadow* sh, void* const* centers, int l, int a, int n,
+                               int heads, rtv_stream_t stream) {
   if (!sh->k8[l] || !sh->v8t[l]) return set_error(-1, "dit: fp8 attention: a layer has no shadow");
-  int a = st->cache_row0 + c.r0, n = c.rc;
   const int S = st->ring_lo, R = st->ring_size;
   int seg[3][2], ns = 0;
   if (R <= 0) {
@@ -572,15 +572,20 @@ static int quantize_written_rows(Ctx& c, int l) {
   }
   void* amax = sh->amax ? sh->amax[l] : nullptr;
   for (int i = 0; i < ns; ++i) {
-    if (c.centers)
-      RTV_TRY(rtv_attn_quantize_kv_centered(st->kv_k[l], st->kv_v[l], st->kv_row_stride, seg[i][0], seg[i][1], c.H, sh->k8[l],
-                                            sh->v8t[l], sh->cache_rows, sh->k_scale, sh->v_scale, amax, (const float*)c.centers[l],
-                                            c.stream));
+    if (centers)
+      RTV_TRY(rtv_attn_quantize_kv_centered(st->kv_k[l], st->kv_v[l], st->kv_row_stride, seg[i][0], seg[i][1], heads, sh->k8[l],
+                                            sh->v8t[l], sh->cache_rows, sh->k_scale, sh->v_scale, amax, (const float*)centers[l],
+                                            stream));
     else
-      RTV_TRY(rtv_attn_quantize_kv(st->kv_k[l], st->kv_v[l], st->kv_row_stride, seg[i][0], seg[i][1], c.H, sh->k8[l], sh->v8t[l],
-                                   sh->cache_rows, sh->k_scale, sh->v_scale, amax, c.stream));
+      RTV_TRY(rtv_attn_quantize_kv(st->kv_k[l], st->kv_v[l], st->kv_row_stride, seg[i][0], seg[i][1], heads, sh->k8[l], sh->v8t[l],
+                                   sh->cache_rows, sh->k_scale, sh->v_scale, amax, stream));
   }
   return 0;
+}
+
+// ... the rows this call has just written
+static int quantize_written_rows(Ctx& c, int l) {
+  return quantize_cache_rows(c.st, c.fp8, c.centers, l, c.st->cache_row0 + c.r0, c.rc, c.H, c.stream);
 }
 
 static int dit_layer_qkv(Ctx& c, int l) { return dit_layer_proj(c, l, RTV_PROJ_LN | RTV_PROJ_Q | RTV_PROJ_KV, 0, nullptr, nullptr); }
@@ -627,6 +632,32 @@ static int sharded_self_attn(Ctx& c, const void* q, const void* k, const void* v
                           st->causal_block, qo, RTV_DTYPE_BF16, c.stream);
 }
 
+// The bounds check of sharded_self_attn for the fp8 split; the fp8 phases make it in front of their first launch as well.
+static int check_fp8_split(const Ctx& c, int rows, int heads) {
+  const int S = c.st->attn_kv_splits;
+  if (S > 1 && (S > c.cfg->max_attn_kv_splits || rtv_attn_split_workspace_bytes(1, rows, heads, S) > c.b.attn_part_bytes))
+    return set_error(-1, "dit: attn_kv_splits exceeds rtv_dit_config.max_attn_kv_splits / the partials do not fit the workspace "
+                         "(splits <= number of shards)");
+  return 0;
+}
+
+// Self-attention on the e4m3 shadow: one launch, or - a sharded phase whose step asks for it - the KV-split one, under the bounds
+// check of sharded_self_attn.
+static int fp8_self_attn(Ctx& c, int l, const void* q, void* o, int rows, int heads, int64_t q_rs, int64_t o_rs, int q_offset) {
+  const rtv_dit_step* st = c.st;
+  const rtv_attn_fp8_shadow* sh = c.fp8;
+  const float scale = 1.0f / sqrtf((float)c.hd);
+  const int S = st->attn_kv_splits;
+  const int qo = st->causal_block > 0 ? q_offset : 0;
+  const KeyWindow kw = key_window(st);
+  if (S <= 1)
+    return rtv_attn_fwd_fp8(q, sh->k8[l], sh->v8t[l], o, rows, heads, sh->cache_rows, kw.row0, kw.n0, kw.row1, kw.n1, q_rs, o_rs, scale,
+                            sh->k_scale, sh->v_scale, st->causal_block, qo, c.stream);
+  RTV_TRY(check_fp8_split(c, rows, heads));
+  return rtv_attn_fwd_fp8_split(q, sh->k8[l], sh->v8t[l], o, rows, heads, sh->cache_rows, kw.row0, kw.n0, kw.row1, kw.n1, q_rs, o_rs,
+                                scale, sh->k_scale, sh->v_scale, st->causal_block, qo, S, c.b.attn_part, c.b.attn_part_bytes, c.stream);
+}
+
 // ---- layer, part 2: attention over the cache window -> o-proj(+gate,+res) -> cross-attn -> FFN
 static int dit_layer_rest(Ctx& c, int l) {
   const rtv_dit_step* st = c.st;
@@ -641,10 +672,8 @@ static int dit_layer_rest(Ctx& c, int l) {
   uint16_t* vc = (uint16_t*)st->kv_v[l];
   // self attention (causal_model.py:386-390, :470-476)
   KeyWindow kw = key_window(st);
-  if (c.fp8) {   // (never sharded, never split: rtv_dit_forward_attn_fp8)
-    const rtv_attn_fp8_shadow* sh = c.fp8;
-    RTV_TRY(rtv_attn_fwd_fp8(b.q, sh->k8[l], sh->v8t[l], b.ao, rc, H, sh->cache_rows, kw.row0, kw.n0, kw.row1, kw.n1, d, d, scale,
-                             sh->k_scale, sh->v_scale, st->causal_block, st->causal_block > 0 ? q_offset : 0, stream));
+  if (c.fp8) {   // (rtv_dit_forward_attn_fp8: never sharded, never split; rtv_dit_layer_rest_attn_fp8: the local rows, maybe split)
+    RTV_TRY(fp8_self_attn(c, l, b.q, b.ao, rc, H, d, d, q_offset));
   } else if (rc < c.M) {   // token-sharded call: the query grid is rc / 256 tiles per head - optionally cut along the keys
     RTV_TRY(sharded_self_attn(c, b.q, kc + (size_t)kw.row0 * rs, vc + (size_t)kw.row0 * rs, b.ao, rc, kw.n0, kw.n1,
                               kw.row1 - kw.row0, H, d, rs, d, q_offset));
@@ -732,6 +761,10 @@ static int dit_layer_attn_hp(Ctx& c, int l, int world, const void* q_all, void* 
   const uint16_t* vc = (const uint16_t*)st->kv_v[l];
   KeyWindow kw = key_window(st);
   (void)Lkv;
+  if (c.fp8) {   // rtv_dit_layer_attn_hp_attn_fp8: the exchange has delivered the block's rows of this rank's heads
+    RTV_TRY(quantize_cache_rows(st, c.fp8, nullptr, l, st->cache_row0, c.M, hn, c.stream));
+    return fp8_self_attn(c, l, q_all, o_all, c.M, hn, gc, gc, q_offset);
+  }
   return sharded_self_attn(c, q_all, kc + (size_t)kw.row0 * rs, vc + (size_t)kw.row0 * rs, o_all, c.M, kw.n0, kw.n1,
                            kw.row1 - kw.row0, hn, gc, rs, gc, q_offset);
 }
@@ -832,8 +865,8 @@ static int dit_forward(const rtv_dit_config* cfg, const rtv_dit_weights* w, cons
   Ctx c;
   RTV_TRY(make_ctx(cfg, w, st, workspace, workspace_bytes, stream, &c));
   if (fp8) {
-    // the phase API takes no shadow, so a sharded call cannot reach the fp8 kernels; what is left to refuse is a sharded or split
-    // step handed to THIS entry point - never a bf16 run in its place
+    // sharded and split steps have phases of their own (rtv_hip_attn_fp8_cp.h); handed to THIS entry point they are refused -
+    // never a bf16 run in their place
     if (c.r0 != 0 || c.rc != c.M) return set_error(-1, "dit: fp8 attention does not support sharded calls (row_count < M)");
     if (st->attn_kv_splits > 1) return set_error(-1, "dit: fp8 attention does not support attn_kv_splits > 1");
     if (!fp8->k8 || !fp8->v8t || fp8->cache_rows <= 0)
@@ -875,6 +908,55 @@ extern "C" int rtv_dit_forward_attn_fp8_centered(const rtv_dit_config* cfg, cons
   if (!shadow) return set_error(-1, "dit: fp8 attention needs its shadow (rtv_attn_fp8_shadow)");
   if (!centers) return set_error(-1, "dit: centred fp8 attention needs its table of K centres");
   return dit_forward(cfg, w, st, shadow, centers, workspace, workspace_bytes, stream);
+}
+
+// ---- the sharded phases with the self-attention in fp8 (rtv_hip_attn_fp8_cp.h)
+static int check_shadow(const rtv_attn_fp8_shadow* shadow) {
+  if (!shadow) return set_error(-1, "dit: fp8 attention needs its shadow (rtv_attn_fp8_shadow)");
+  if (!shadow->k8 || !shadow->v8t || shadow->cache_rows <= 0)
+    return set_error(-1, "dit: fp8 attention needs the k8 / v8t shadow arrays and cache_rows");
+  return 0;
+}
+
+extern "C" int rtv_dit_quantize_block_attn_fp8(const rtv_dit_config* cfg, const rtv_dit_step* st, int layer, int heads,
+                                               const rtv_attn_fp8_shadow* shadow, rtv_stream_t stream) {
+  if (!cfg || !st) return set_error(-1, "dit: null argument");
+  RTV_TRY(check_shadow(shadow));
+  if (layer < 0 || layer >= cfg->num_layers) return set_error(-1, "dit: layer out of range");
+  if (heads <= 0 || heads > cfg->num_heads) return set_error(-1, "dit: fp8 attention: heads must be 1..num_heads");
+  const int64_t M = (int64_t)st->F * st->gh * st->gw;
+  if (st->F <= 0 || st->gh <= 0 || st->gw <= 0 || M > INT32_MAX) return set_error(-1, "dit: empty token grid");
+  if (!st->kv_k || !st->kv_v || !st->kv_k[layer] || !st->kv_v[layer]) return set_error(-1, "dit: null argument");
+  if (st->cache_row0 < 0 || st->ring_size < 0 || st->ring_lo < 0 || st->ring_shift < 0 ||
+      (st->ring_size > 0 && st->ring_shift >= st->ring_size) || (st->ring_size > 0 && st->cache_row0 + M > st->ring_lo + st->ring_size))
+    return set_error(-1, "dit: bad ring window (0 <= ring_shift < ring_size, kv_hi <= ring_lo + ring_size)");
+  return quantize_cache_rows(st, shadow, nullptr, layer, st->cache_row0, (int)M, heads, stream);
+}
+
+extern "C" int rtv_dit_layer_rest_attn_fp8(const rtv_dit_config* cfg, const rtv_dit_weights* w, const rtv_dit_step* st, int layer,
+                                           const rtv_attn_fp8_shadow* shadow, void* ws, size_t ws_bytes, rtv_stream_t stream) {
+  Ctx c;
+  RTV_TRY(make_ctx(cfg, w, st, ws, ws_bytes, stream, &c));
+  if (layer < 0 || layer >= c.L) return set_error(-1, "dit: layer out of range");
+  RTV_TRY(check_shadow(shadow));
+  c.fp8 = shadow;
+  RTV_TRY(check_fp8_split(c, c.rc, c.H));
+  RTV_TRY(quantize_cache_rows(st, shadow, nullptr, layer, st->cache_row0, c.M, c.H, stream));   // the gathered rows, every rank for itself
+  return dit_layer_rest(c, layer);
+}
+
+extern "C" int rtv_dit_layer_attn_hp_attn_fp8(const rtv_dit_config* cfg, const rtv_dit_weights* w, const rtv_dit_step* st, int layer,
+                                              int world, const void* q_all, void* o_all, const rtv_attn_fp8_shadow* shadow, void* ws,
+                                              size_t ws_bytes, rtv_stream_t stream) {
+  Ctx c;
+  RTV_TRY(make_ctx(cfg, w, st, ws, ws_bytes, stream, &c));
+  if (layer < 0 || layer >= c.L) return set_error(-1, "dit: layer out of range");
+  if (!q_all || !o_all) return set_error(-1, "dit: exchange buffers required");
+  RTV_TRY(check_shadow(shadow));
+  c.fp8 = shadow;
+  RTV_TRY(hp_check(c, world));
+  RTV_TRY(check_fp8_split(c, c.M, c.H / world));
+  return dit_layer_attn_hp(c, layer, world, q_all, o_all);
 }
 
 extern "C" int rtv_dit_lab_capture_self_attn(void* q_copy, void* o_copy) {

@@ -310,10 +310,14 @@ def attn_quantize_kv(k_cache, v_cache, k8, v8t, row0=0, rows=None, k_scale=1.0, 
     return k8, v8t
 
 
-def attn_fwd_fp8(q, k8, v8t, seg0, seg1=(0, 0), out=None, scale=None, k_scale=1.0, v_scale=1.0, causal_block=0, q_offset=0):
+def attn_fwd_fp8(q, k8, v8t, seg0, seg1=(0, 0), out=None, scale=None, k_scale=1.0, v_scale=1.0, causal_block=0, q_offset=0, kv_splits=1,
+                 workspace=None):
     """fp8 attention of q [Lq, H, 128] bf16 over the key window seg0 + seg1 (each (first physical row, rows)) of a shadow
-    (rtv_attn_fwd_fp8).  causal_block > 0: the block-causal prefix rule of attn_fwd, one range only."""
-    _gpu(q, out)
+    (rtv_attn_fwd_fp8).  causal_block > 0: the block-causal prefix rule of attn_fwd, one range only.
+    kv_splits > 1, or a workspace: the window's storage tiles cut into kv_splits ranges, one workgroup per (head, query tile, range),
+    merged by a second kernel (rtv_attn_fwd_fp8_split, include/rtv_hip_attn_fp8_cp.h).  workspace: float32 tensor of at least
+    rtv_attn_split_workspace_bytes(1, Lq, H, kv_splits) bytes (allocated when None)."""
+    _gpu(q, out, workspace)
     cache_rows, H = _check_shadow(k8, v8t, "attn_fwd_fp8")
     if q.dtype != torch.bfloat16 or q.dim() != 3 or q.shape[1] != H or q.shape[2] != 128 or q.stride(2) != 1 or q.stride(1) != 128:
         raise ValueError("attn_fwd_fp8: q must be bf16 [Lq, H, 128] with dense [H, 128] inner dims, H as in k8")
@@ -324,8 +328,18 @@ def attn_fwd_fp8(q, k8, v8t, seg0, seg1=(0, 0), out=None, scale=None, k_scale=1.
     if scale is None:
         scale = 1.0 / math.sqrt(128)
     (r0, n0), (r1, n1) = seg0, seg1
-    _lib.call("rtv_attn_fwd_fp8", _ptr(q), _ptr(k8), _ptr(v8t), _ptr(out), q.shape[0], H, cache_rows, int(r0), int(n0), int(r1), int(n1),
-              q.stride(0), out.stride(0), float(scale), float(k_scale), float(v_scale), int(causal_block), int(q_offset), _stream())
+    if int(kv_splits) == 1 and workspace is None:
+        _lib.call("rtv_attn_fwd_fp8", _ptr(q), _ptr(k8), _ptr(v8t), _ptr(out), q.shape[0], H, cache_rows, int(r0), int(n0), int(r1), int(n1),
+                  q.stride(0), out.stride(0), float(scale), float(k_scale), float(v_scale), int(causal_block), int(q_offset), _stream())
+        return out
+    if workspace is None:
+        need = _lib.load().rtv_attn_split_workspace_bytes(1, q.shape[0], H, int(kv_splits))
+        workspace = torch.empty(max(need, 16) // 4, dtype=torch.float32, device=q.device)
+    elif workspace.dtype != torch.float32 or not workspace.is_contiguous():
+        raise ValueError("attn_fwd_fp8: workspace must be a dense float32 tensor")
+    _lib.call("rtv_attn_fwd_fp8_split", _ptr(q), _ptr(k8), _ptr(v8t), _ptr(out), q.shape[0], H, cache_rows, int(r0), int(n0), int(r1), int(n1),
+              q.stride(0), out.stride(0), float(scale), float(k_scale), float(v_scale), int(causal_block), int(q_offset), int(kv_splits),
+              _ptr(workspace), workspace.numel() * 4, _stream())
     return out
 
 

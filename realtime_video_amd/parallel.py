@@ -17,6 +17,11 @@ Two exchange patterns around self-attention (`ContextParallel(exchange=...)`):
             holds only those heads) and a second one turns the output back: 4*(M/w)*d*(w-1)/w elements per rank and
             layer, i.e. w/2 times less xGMI traffic and 1/w of the cache memory.  Needs H % w == 0.
 "auto" (default) picks "heads" whenever the head count divides.
+
+fp8 self-attention (CausalWanModel.enable_fp8_attention(context_parallel=True), include/rtv_hip_attn_fp8_cp.h) rides on the same
+exchanges, which keep moving bf16 rows: behind an exchange every rank quantises the block's rows into its e4m3 shadow itself - all
+heads under "rows", the num_heads / world heads it owns under "heads" (one dense shadow per local rank) - and `attn_kv_splits` then
+selects the KV split of the fp8 kernel.  The shadow bytes are never exchanged.
 """
 import torch
 import torch.distributed as dist
@@ -54,7 +59,9 @@ def attn_kv_splits_for(world, num_heads, q_tiles=19, cus=None):
     """How many key ranges a context-parallel rank's self-attention launch should be cut into (ContextParallel(attn_kv_splits=)).
     One rank's launch has num_heads x q_tiles / world workgroups (either exchange), one per CU at a time: rounds of `cus`.  S
     ranges make S x as many workgroups of 1/S the length, + ~6 % per extra range for the merge kernel and the per-workgroup
-    prologue (profiles/r03_attn_kv_split_ab.log).  14B (40 heads): 2 / 4 / 2 ranges at 2 / 4 / 8 ranks; 1 rank: 1."""
+    prologue (profiles/r03_attn_kv_split_ab.log).  14B (40 heads): 2 / 4 / 2 ranges at 2 / 4 / 8 ranks; 1 rank: 1.
+    The 6 % is a figure of the bf16 kernels; the fp8 split (rtv_attn_fwd_fp8_split) takes the same plan, measured beside S = 1 in
+    profiles/r22_attn_fp8_cp.json."""
     if world <= 1:
         return 1
     if cus is None:     # the device's real CU count (the same number the GEMM dispatch and plan_split_k use), 256 without a GPU
