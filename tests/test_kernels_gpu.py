@@ -448,7 +448,9 @@ def test_quantize_fp8_matches_torch_e4m3(ops):
     x = (_randn(1000, 512, seed=5) * 3).contiguous()
     q, s = ops.quantize_fp8(x)
     _, xq, _, sx, _ = _fp8_linear_ref(x, x[:8], None)
-    assert abs(float(s) - float(sx)) <= 1e-7 * float(sx)
+    inv448 = torch.tensor(1.0) / torch.tensor(448.0)                         # the restatement's scale, evaluated on the host
+    rs = x.cpu().float().abs().max().clamp(min=1e-12) * inv448
+    assert float(sx) == float(rs) and torch.equal(s.cpu().view(torch.int32), rs.reshape(1).view(torch.int32))
     assert torch.equal(q.view(torch.uint8), xq.view(torch.uint8))          # same rounding (RNE), same saturation
     z, sz = ops.quantize_fp8(torch.zeros(16, 128, dtype=torch.bfloat16, device=DEV))
     assert float(z.float().abs().max()) == 0 and float(sz) > 0
