@@ -92,6 +92,12 @@ class _SelfAttnHandle:
         self.fused_projections = True
 
 
+def kv_cache_rows(cache):
+    """Rows of one layer's KV cache dict, of either kind: the bf16 cache {"k", "v", ...} (with or without its e4m3 shadow) or the
+    compact e4m3-only one {"k8", "v8t", "rows", ...} of enable_fp8_attention(bf16_cache=False)."""
+    return cache["k"].shape[1] if "k" in cache else int(cache["rows"])
+
+
 def cache_row_map(cache, sink_tokens=None):
     """Physical cache row of every LIVE logical row [0, local_end_index) of one kv_cache entry.  The rolling cache is kept as a
     ring (no eviction copies): logical row r >= ring_lo lives at ring_lo + (r - ring_lo + ring_start) % ring_size.  For
@@ -150,6 +156,7 @@ class CausalWanModel:
         self._fp8_attn_epoch = 0      # bumps at every enable / disable: a shadow filled before it is refilled from the bf16 cache
         self._fp8_attn_amax = None    # float32 [num_layers, 2], allocated once
         self._fp8_attn_cp = False           # enable_fp8_attention(context_parallel=True): sharded forwards run in fp8 instead of raising
+        self._fp8_attn_only = False         # enable_fp8_attention(bf16_cache=False): the e4m3 arrays are the whole KV cache
         self._fp8_attn_smooth = False       # enable_fp8_attention(smooth_k=True): the K codes of the shadows are those of k - centre
         self._fp8_attn_center = None        # float32 [num_layers, H, 128], zero-filled, allocated once; fp8_attention_recenter() writes it
         self._fp8_attn_center_ws = None     # workspace of the mean kernel, allocated with the centre
@@ -456,7 +463,7 @@ class CausalWanModel:
             return _BF16
         return self._linear_modes[i] if self._cfg.use_fp8 == _MIXED else self._cfg.use_fp8
 
-    def enable_fp8_attention(self, k_scale=1.0, v_scale=1.0, smooth_k=False, context_parallel=False):
+    def enable_fp8_attention(self, k_scale=1.0, v_scale=1.0, smooth_k=False, context_parallel=False, bf16_cache=True):
         """Opt-in: self-attention in the precision of the reference's SageAttention backend (wan/modules/sage.py: 8-bit Q K^T, fp8
         P V) on an OCP e4m3 shadow of the KV cache (include/rtv_hip_attn_fp8.h).  Independent of enable_fp8(), which concerns the
         Linears; cross-attention and the VAE stay as they are.  K / V codes are e4m3(x / scale) with one scale per tensor kind, Q is
@@ -491,9 +498,24 @@ class CausalWanModel:
         of the fp8 kernel.  With attn_kv_splits = 1 a sharded forward computes bit for bit what the unsharded one computes.  A
         rolling cache under context parallelism shift-copies its rows; the shadows are then stale and the same forward refills them
         whole before it runs.  smooth_k=True together with context_parallel=True is a ValueError: centres under sharding are not
-        built.  Not measured on more than one GPU."""
+        built.  Not measured on more than one GPU.
+
+        bf16_cache=False (opt-in; include/rtv_hip_attn_fp8_only.h): the two e4m3 arrays are the whole KV cache - a third of the
+        bytes the shadow mode keeps per row, half of the bf16 cache's.  The cache dicts are the compact ones of
+        new_fp8_kv_cache() ({"k8", "v8t", "rows", indices}, no "k" / "v"; CausalInferencePipeline allocates them by itself when
+        the model is in the mode), a block's K and V exist in bf16 only in the forward's projection buffer, and the codes, the
+        maxima and every output equal the shadow mode's bit for bit.  Each of the following is refused, never run in bf16 or on
+        a shadow: smooth_k=True (recentring reads the bf16 K cache) and context_parallel=True or a model with context_parallel
+        set (ValueError here); a dict with "k" / "v" handed to the model in this mode, a compact dict handed to it outside the
+        mode - after disable_fp8_attention() too -, and new scales on a cache that holds rows, whose codes cannot be derived again:
+        reset the cache first (RuntimeError from the forward, before its first launch, the cache indices untouched).  Converting a
+        live bf16 cache into a compact one is not built."""
         if smooth_k and context_parallel:
             raise ValueError("enable_fp8_attention: smooth_k=True is not supported together with context_parallel=True")
+        if not bf16_cache and smooth_k:
+            raise ValueError("enable_fp8_attention: smooth_k=True needs the bf16 KV cache (bf16_cache=False keeps none to take the centres from)")
+        if not bf16_cache and (context_parallel or self.context_parallel is not None):
+            raise ValueError("enable_fp8_attention: bf16_cache=False does not support context parallelism")
         k_scale, v_scale = float(k_scale), float(v_scale)
         for s in (k_scale, v_scale):
             if not (math.isfinite(s) and s > 0):
@@ -502,13 +524,24 @@ class CausalWanModel:
         self._fp8_attn = (k_scale, v_scale, self._fp8_attn_epoch)
         self._fp8_attn_smooth = bool(smooth_k)
         self._fp8_attn_cp = bool(context_parallel)
+        self._fp8_attn_only = not bf16_cache
         return self
+
+    def new_fp8_kv_cache(self, rows, device):
+        """The KV cache of enable_fp8_attention(bf16_cache=False): per layer the two e4m3 arrays of include/rtv_hip_attn_fp8.h
+        (zero-filled; rows outside the attention window are masked by the kernel) and the indices - no "k" / "v" entries."""
+        caches = []
+        for _ in range(self.num_layers):
+            k8, v8t = ops.attn_fp8_shadow(int(rows), self.num_heads, device)
+            caches.append({"k8": k8, "v8t": v8t, "rows": int(rows), "global_end_index": 0, "local_end_index": 0})
+        return caches
 
     def disable_fp8_attention(self):
         """Back to bf16 self-attention: every launch is the one a model that never enabled the mode issues.  The shadows stay in the
         cache dicts and are refilled from the bf16 cache when the mode comes back."""
         self._fp8_attn_epoch += 1
         self._fp8_attn = None
+        self._fp8_attn_only = False
         return self
 
     def fp8_attention_amax(self):
@@ -542,6 +575,47 @@ class CausalWanModel:
         self._fp8_attn_center_epoch += 1
         return self
 
+    def _fp8_attention_only(self):
+        return self._fp8_attn is not None and self._fp8_attn_only
+
+    def _check_kv_cache_kind(self, kv_cache, use_cp):
+        """The refusals of the e4m3-only cache that concern the dicts: made by the forward before anything else looks at them."""
+        compact = ["k" not in c and "v" not in c for c in kv_cache]
+        if not self._fp8_attention_only():
+            if any(compact):
+                raise RuntimeError("this KV cache is an e4m3-only one (new_fp8_kv_cache): it needs enable_fp8_attention(bf16_cache=False)")
+            return
+        if use_cp or self.context_parallel is not None:
+            raise RuntimeError("enable_fp8_attention(bf16_cache=False) does not support context parallelism")
+        if not all(compact):
+            raise RuntimeError("enable_fp8_attention(bf16_cache=False) needs the compact KV cache of new_fp8_kv_cache(): "
+                               "this one has \"k\" / \"v\" entries")
+        rows, scales = kv_cache_rows(kv_cache[0]), self._fp8_attn[:2]
+        for c in kv_cache:
+            if kv_cache_rows(c) != rows or tuple(c["k8"].shape) != (rows, self.num_heads, 128) \
+                    or tuple(c["v8t"].shape) != ((rows + 63) // 64, self.num_heads, 128, 64) \
+                    or not (c["k8"].is_cuda and c["k8"].is_contiguous() and c["v8t"].is_contiguous()) \
+                    or c["k8"].dtype != torch.uint8 or c["v8t"].dtype != torch.uint8 or c["v8t"].device != c["k8"].device:
+                raise ValueError("fp8 attention: every layer's compact KV cache must be the k8 / v8t pair of new_fp8_kv_cache(rows) "
+                                 "with the same number of rows")
+            if int(c["local_end_index"]) > 0 and c.get("fp8_scales", scales) != scales:
+                raise RuntimeError(f"fp8 attention: this e4m3-only KV cache holds rows quantised with k_scale, v_scale = {c['fp8_scales']}; "
+                                   "their codes cannot be derived again for other scales: reset the cache first")
+
+    def _fp8_attention_only_shadow(self, kv_cache):
+        """_fp8_attention_shadow for the e4m3-only cache (checked by _check_kv_cache_kind): nothing to allocate but the maxima,
+        nothing to fill."""
+        k_scale, v_scale, _ = self._fp8_attn
+        L = self.num_layers
+        if self._fp8_attn_amax is None:
+            self._fp8_attn_amax = torch.zeros(L, 2, dtype=torch.float32, device=kv_cache[0]["k8"].device)
+        arrs = [(c_vp * L)(*[t_.data_ptr() for t_ in ts]) for ts in ([c["k8"] for c in kv_cache], [c["v8t"] for c in kv_cache],
+                                                                     [self._fp8_attn_amax[l] for l in range(L)])]
+        pp = ctypes.POINTER(c_vp)
+        sh = _Fp8Shadow(ctypes.cast(arrs[0], pp), ctypes.cast(arrs[1], pp), kv_cache_rows(kv_cache[0]), k_scale, v_scale,
+                        ctypes.cast(arrs[2], pp))
+        return sh, (sh, arrs)
+
     def _fp8_attention_shadow(self, kv_cache, use_cp):
         """The rtv_attn_fp8_shadow of this forward (None: bf16 attention) and what must stay alive with it.  Under the head exchange
         of a context-parallel forward: a list, one shadow per local rank."""
@@ -553,7 +627,7 @@ class CausalWanModel:
         L = self.num_layers
         if self._fp8_attn_amax is None:
             self._fp8_attn_amax = torch.zeros(L, 2, dtype=torch.float32, device=kv_cache[0]["k"].device)
-        rows = kv_cache[0]["k"].shape[1]
+        rows = kv_cache_rows(kv_cache[0])
         if use_cp and self.context_parallel.head_exchange(self.num_heads):
             return self._fp8_attention_shadow_heads(kv_cache, rows)
         smooth = self._fp8_attn_smooth
@@ -879,7 +953,7 @@ class CausalWanModel:
         ranges of the window (rtv_attn_fwd_win) - zero copies.  `ring=False` (context-parallel exchanges, which move
         contiguous row blocks) keeps the reference's shift copy."""
         c0 = kv_cache[0]
-        kv_size = c0["k"].shape[1]
+        kv_size = kv_cache_rows(c0)
         if self.block_mask is not None:  # KV-recompute pass over clean context frames: rows [0, num_new), unrotated
             if num_new > kv_size:
                 raise RuntimeError(f"KV cache window [0, {num_new}) outside cache of {kv_size} rows")
@@ -1006,17 +1080,28 @@ class CausalWanModel:
             for c in crossattn_cache:
                 if "vo" not in c:
                     c["vo"] = torch.zeros(self.dim * _cross_fold_max_cols(self.num_heads), dtype=torch.bfloat16, device=u.device)
+        self._check_kv_cache_kind(kv_cache, use_cp)
+        fp8_only = self._fp8_attention_only()      # the dicts hold k8 / v8t and nothing in bf16 (include/rtv_hip_attn_fp8_only.h)
         row0, lo, hi, start_frame, causal_block, (ring_lo, ring_size, ring_shift), commit = \
             self._cache_window(kv_cache, M, current_start, fs, ring=not use_cp)
         L = self.num_layers
-        rs = kv_cache[0]["k"].stride(1)
-        for c in kv_cache:
+        rs = self.dim if fp8_only else kv_cache[0]["k"].stride(1)      # (the e4m3-only forward does not read the step's stride)
+        for c in ([] if fp8_only else kv_cache):
             for n in ("k", "v"):
                 if c[n].stride(3) != 1 or c[n].stride(2) != c[n].shape[3] or c[n].stride(1) != rs:
                     raise ValueError("KV cache tensors must be [B, kv_size, H, 128] views with dense [H, 128] rows "
                                      "and one common row stride")
 
-        fp8_shadow, fp8_keep = self._fp8_attention_shadow(kv_cache, use_cp)
+        if fp8_only:
+            fp8_shadow, fp8_keep = self._fp8_attention_only_shadow(kv_cache)
+            commit_indices, scales = commit, self._fp8_attn[:2]
+
+            def commit():
+                commit_indices()
+                for c in kv_cache:
+                    c["fp8_scales"] = scales      # what the codes in the cache were made with: they cannot be made again
+        else:
+            fp8_shadow, fp8_keep = self._fp8_attention_shadow(kv_cache, use_cp)
         # (the unsharded forward with the shadows as an argument; the context-parallel path has phases of its own, run_cp below)
         forward = ("rtv_dit_forward",) if fp8_shadow is None or use_cp else ("rtv_dit_forward_attn_fp8", ctypes.byref(fp8_shadow))
         if fp8_shadow is None:
@@ -1025,6 +1110,9 @@ class CausalWanModel:
             fp8_key = self._fp8_attn[:2] + ("heads", kv_cache[0]["k8_hp"][0].data_ptr(), kv_cache[-1]["v8t_hp"][-1].data_ptr())
         else:
             fp8_key = self._fp8_attn[:2] + (kv_cache[0]["k8"].data_ptr(), kv_cache[-1]["v8t"].data_ptr())
+        if fp8_only:      # the same struct, the entry point that never looks for a bf16 cache; part of the graph key like the scales
+            forward = ("rtv_dit_forward_attn_fp8_only", ctypes.byref(fp8_shadow))
+            fp8_key = ("only",) + fp8_key
         if fp8_shadow is not None and self._fp8_attn_smooth:      # the centred entry point: the centre table behind the shadow
             forward = ("rtv_dit_forward_attn_fp8_centered", ctypes.byref(fp8_shadow), fp8_keep[1][3])
             fp8_key += (self._fp8_attn_center.data_ptr(),)
@@ -1033,8 +1121,9 @@ class CausalWanModel:
             arr = (c_vp * L)(*[t_.data_ptr() for t_ in tensors])
             return arr, ctypes.cast(arr, ctypes.POINTER(c_vp))
 
-        kk_keep, kk = ptr_array([c["k"] for c in kv_cache])
-        kv_keep, kv = ptr_array([c["v"] for c in kv_cache])
+        kk_keep, kk = (None, None) if fp8_only else ptr_array([c["k"] for c in kv_cache])      # (None: a null kv_k / kv_v table)
+        kv_keep, kv = (None, None) if fp8_only else ptr_array([c["v"] for c in kv_cache])
+        kv_ids = (0, 0) if fp8_only else (kv_cache[0]["k"].data_ptr(), kv_cache[-1]["v"].data_ptr())      # fp8_key names the e4m3 arrays
         ck_keep, ck = ptr_array([c["k"] for c in crossattn_cache])
         cv_list = [c["v"] for c in crossattn_cache] + ([c["vo"] for c in crossattn_cache] if fold_k else [])
         cv_keep = (c_vp * len(cv_list))(*[t_.data_ptr() for t_ in cv_list])      # folded: ca_v[L + l] = the folded weight of layer l
@@ -1073,7 +1162,7 @@ class CausalWanModel:
                 # the latent / timestep / output live in static buffers.  The first sighting of a key runs eagerly.
                 graph_key = (F, gh, gw, row0, lo, hi, start_frame, causal_block, ring_lo, ring_size, ring_shift, kv_only, text_rows, fold_k,
                              int(self.gemm_tile_cfg), rs, self._weights_version,
-                             kv_cache[0]["k"].data_ptr(), kv_cache[-1]["v"].data_ptr(), crossattn_cache[0]["k"].data_ptr(), fp8_key)
+                             *kv_ids, crossattn_cache[0]["k"].data_ptr(), fp8_key)
                 ent = self._graphs.get(graph_key)
                 if isinstance(ent, dict):
                     ent["u"].copy_(u)
@@ -1116,7 +1205,7 @@ class CausalWanModel:
             if self.use_hip_graphs and not need_cross and not getattr(cp, "_gloo", False):
                 graph_key = ("cp", id(cp), bool(getattr(cp, "overlap", True)), cp.world, cp.head_exchange(self.num_heads), F, gh, gw, row0, lo, hi, start_frame, causal_block, kv_only,
                              text_rows, fold_k, int(self.gemm_tile_cfg), rs, self._weights_version, splits,
-                             kv_cache[0]["k"].data_ptr(), kv_cache[-1]["v"].data_ptr(), crossattn_cache[0]["k"].data_ptr(), fp8_key)
+                             *kv_ids, crossattn_cache[0]["k"].data_ptr(), fp8_key)
                 ent = self._graphs.get(graph_key)
                 if isinstance(ent, dict):
                     ent["u"].copy_(u)

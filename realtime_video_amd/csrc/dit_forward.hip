@@ -19,6 +19,7 @@
 #include "../../include/rtv_hip_attn_fp8.h"
 #include "../../include/rtv_hip_attn_fp8_center.h"
 #include "../../include/rtv_hip_attn_fp8_cp.h"
+#include "../../include/rtv_hip_attn_fp8_only.h"
 #include "../../include/rtv_hip_mxfp4.h"
 #include "../../include/rtv_hip_mxfp6.h"
 #include "../../include/rtv_hip_mx_rotate.h"
@@ -164,6 +165,7 @@ struct Ctx {
   const rtv_attn_fp8_shadow* fp8;   // rtv_dit_forward_attn_fp8 and the sharded phases of rtv_hip_attn_fp8_cp.h: self-attention on the
                                     // e4m3 shadows; null in every other entry point
   void* const* centers;             // rtv_dit_forward_attn_fp8_centered: per-layer K centres of the shadows; null in every other one
+  bool fp8_only;                    // rtv_dit_forward_attn_fp8_only: the shadows ARE the cache - st->kv_k / kv_v / kv_row_stride are not read
   const uint8_t* modes;  // use_fp8 == 7: the mode of each Linear (linear_modes, checked by make_ctx); null otherwise
   int fold_kh, fold_k;   // cross-attention V folded into the output projection: columns per head / in all; 0 = the unfolded path
                          // (then st->ca_v[L + l] is layer l's folded weight, rtv_dit_step.ca_vo_ld)
@@ -208,6 +210,7 @@ static int make_ctx(const rtv_dit_config* cfg, const rtv_dit_weights* w, const r
   c->st = st;
   c->fp8 = nullptr;
   c->centers = nullptr;
+  c->fp8_only = false;
   c->stream = stream;
   c->d = cfg->dim;
   c->H = cfg->num_heads;
@@ -455,6 +458,7 @@ static int dit_begin(Ctx& c) {
 
 static int hp_check(Ctx& c, int world);
 static int quantize_written_rows(Ctx& c, int l);
+static int write_fp8_only_rows(Ctx& c, int l, bool q);
 
 // ---- layer, part 1: LN+modulate -> QKV -> RMSNorm(q,k)+RoPE -> local K/V rows into the cache (or the exchange buffers).
 // `parts` selects what this call does, so that the host can put a collective between the two projections and let it run
@@ -486,7 +490,7 @@ static int dit_layer_proj(Ctx& c, int l, int parts, int world, void* q_send, voi
     // (rope_parts | 4).  (One launch with a second output matrix was built first: three more kernel arguments, or one more epilogue
     // instantiation, cost the ping-pong kernel 3-4 % on the ffn-in shape - more than the copy.)
     void* v_dst = nullptr;
-    if (kv && !kv_send && g_direct_v.load(std::memory_order_relaxed) && st->kv_v[l] && !(st->kv_row_stride & 7)) {
+    if (kv && !kv_send && !c.fp8_only && g_direct_v.load(std::memory_order_relaxed) && st->kv_v[l] && !(st->kv_row_stride & 7)) {
       int r0 = st->cache_row0 + c.r0;
       const int S = st->ring_lo, R = st->ring_size;
       bool one_range = true;
@@ -511,7 +515,7 @@ static int dit_layer_proj(Ctx& c, int l, int parts, int world, void* q_send, voi
         RTV_TRY(qk_norm_rope_check(2 * gc, 0, c.rc, d, c.H, c.F, c.gh, c.gw, st->start_frame, c.r0, gc, (int64_t)c.rc * gc,
                                    (int64_t)c.rc * 2 * gc, 0, 0, 0, rp));
       } else {
-        RTV_TRY(qk_norm_rope_check(st->kv_row_stride, st->cache_row0, c.rc, d, c.H, c.F, c.gh, c.gw, st->start_frame, c.r0, 0, 0, 0,
+        RTV_TRY(qk_norm_rope_check(c.fp8_only ? d : st->kv_row_stride, st->cache_row0, c.rc, d, c.H, c.F, c.gh, c.gw, st->start_frame, c.r0, 0, 0, 0,
                                    st->ring_lo, st->ring_size, st->ring_shift, rp));
       }
     }
@@ -540,6 +544,7 @@ static int dit_layer_proj(Ctx& c, int l, int parts, int world, void* q_send, voi
                                c.cfg->eps, lw.norm_q_w, lw.norm_k_w, c.w->rope_cs, c.F, c.gh, c.gw, st->start_frame, c.r0, gc,
                                (int64_t)c.rc * gc, (int64_t)c.rc * 2 * gc, 0, 0, 0, rope_parts, c.stream);
   }
+  if (c.fp8_only) return write_fp8_only_rows(c, l, q);   // (never with exchange buffers: the mode refuses sharded steps)
   RTV_TRY(qk_norm_rope_launch(b.qkv, b.q, st->kv_k[l], st->kv_v[l], st->kv_row_stride, st->cache_row0, c.rc, d, c.H, c.cfg->eps,
                               lw.norm_q_w, lw.norm_k_w, c.w->rope_cs, c.F, c.gh, c.gw, st->start_frame, c.r0, 0, 0, 0, st->ring_lo,
                               st->ring_size, st->ring_shift, rope_parts, c.stream));
@@ -547,13 +552,11 @@ static int dit_layer_proj(Ctx& c, int l, int parts, int world, void* q_send, voi
   return 0;
 }
 
-// fp8 attention: the physical cache rows of the logical rows [a, a + n) of layer l (the ring mapping of the write: sink rows as
-// they are, ring rows rotated, at most one wrap) go into the layer's e4m3 shadow, `heads` heads of them.
-static int quantize_cache_rows(const rtv_dit_step* st, const rtv_attn_fp8_shadow* sh, void* const* centers, int l, int a, int n,
-                               int heads, rtv_stream_t stream) {
-  if (!sh->k8[l] || !sh->v8t[l]) return set_error(-1, "dit: fp8 attention: a layer has no shadow");
+// The physical cache rows of the logical rows [a, a + n) by the ring mapping of the write: sink rows as they are, ring rows rotated,
+// at most one wrap.  -> the number of segments (first physical row, rows) in seg, in the order of the logical rows; -1: refused.
+static int cut_written_rows(const rtv_dit_step* st, int a, int n, int seg[3][2]) {
   const int S = st->ring_lo, R = st->ring_size;
-  int seg[3][2], ns = 0;
+  int ns = 0;
   if (R <= 0) {
     seg[ns][0] = a, seg[ns++][1] = n;
   } else {
@@ -570,6 +573,17 @@ static int quantize_cache_rows(const rtv_dit_step* st, const rtv_attn_fp8_shadow
       if (n > first) seg[ns][0] = S, seg[ns++][1] = n - first;
     }
   }
+  return ns;
+}
+
+// fp8 attention: the physical cache rows of the logical rows [a, a + n) of layer l go into the layer's e4m3 shadow, `heads` heads
+// of them.
+static int quantize_cache_rows(const rtv_dit_step* st, const rtv_attn_fp8_shadow* sh, void* const* centers, int l, int a, int n,
+                               int heads, rtv_stream_t stream) {
+  if (!sh->k8[l] || !sh->v8t[l]) return set_error(-1, "dit: fp8 attention: a layer has no shadow");
+  int seg[3][2];
+  const int ns = cut_written_rows(st, a, n, seg);
+  if (ns < 0) return ns;
   void* amax = sh->amax ? sh->amax[l] : nullptr;
   for (int i = 0; i < ns; ++i) {
     if (centers)
@@ -586,6 +600,28 @@ static int quantize_cache_rows(const rtv_dit_step* st, const rtv_attn_fp8_shadow
 // ... the rows this call has just written
 static int quantize_written_rows(Ctx& c, int l) {
   return quantize_cache_rows(c.st, c.fp8, c.centers, l, c.st->cache_row0 + c.r0, c.rc, c.H, c.stream);
+}
+
+// The e4m3-only cache (rtv_hip_attn_fp8_only.h): the block's q rows into b.q and its K rows into k8 in one launch, then its V rows
+// from the V third of the projection buffer into v8t, one launch per physical segment.
+static int write_fp8_only_rows(Ctx& c, int l, bool q) {
+  const rtv_dit_layer_weights& lw = c.w->layers[l];
+  const rtv_dit_step* st = c.st;
+  const rtv_attn_fp8_shadow* sh = c.fp8;
+  const int d = c.d;
+  void* amax = sh->amax ? sh->amax[l] : nullptr;
+  int seg[3][2];
+  const int ns = cut_written_rows(st, st->cache_row0 + c.r0, c.rc, seg);
+  if (ns < 0) return ns;
+  RTV_TRY(rtv_qk_norm_rope_k8(c.b.qkv, q ? c.b.q : nullptr, sh->k8[l], sh->cache_rows, sh->k_scale, amax, st->cache_row0, c.rc, d, c.H,
+                              c.cfg->eps, lw.norm_q_w, lw.norm_k_w, c.w->rope_cs, c.F, c.gh, c.gw, st->start_frame, c.r0, st->ring_lo,
+                              st->ring_size, st->ring_shift, c.stream));
+  const uint16_t* v_src = c.b.qkv + 2 * d;
+  for (int i = 0; i < ns; ++i) {
+    RTV_TRY(rtv_attn_quantize_v_rows(v_src, 3 * d, seg[i][1], c.H, sh->v8t[l], sh->cache_rows, seg[i][0], sh->v_scale, amax, c.stream));
+    v_src += (size_t)seg[i][1] * 3 * d;
+  }
+  return 0;
 }
 
 static int dit_layer_qkv(Ctx& c, int l) { return dit_layer_proj(c, l, RTV_PROJ_LN | RTV_PROJ_Q | RTV_PROJ_KV, 0, nullptr, nullptr); }
@@ -668,8 +704,8 @@ static int dit_layer_rest(Ctx& c, int l) {
   const int64_t rs = st->kv_row_stride;
   const int Lkv = st->kv_hi - st->kv_lo;
   const int q_offset = st->cache_row0 - st->kv_lo + r0;  // position of local query row 0 inside the window
-  uint16_t* kc = (uint16_t*)st->kv_k[l];
-  uint16_t* vc = (uint16_t*)st->kv_v[l];
+  uint16_t* kc = c.fp8_only ? nullptr : (uint16_t*)st->kv_k[l];
+  uint16_t* vc = c.fp8_only ? nullptr : (uint16_t*)st->kv_v[l];
   // self attention (causal_model.py:386-390, :470-476)
   KeyWindow kw = key_window(st);
   if (c.fp8) {   // (rtv_dit_forward_attn_fp8: never sharded, never split; rtv_dit_layer_rest_attn_fp8: the local rows, maybe split)
@@ -858,10 +894,28 @@ extern "C" int rtv_dit_finish(const rtv_dit_config* cfg, const rtv_dit_step* st,
   return rtv_unpatchify(head_rows, st->out, cfg->out_dim, st->F, st->gh, st->gw, stream);
 }
 
+// The e4m3-only cache: what its kernels and the attention launch would refuse layer by layer is refused here, in front of the first
+// launch of the forward (nothing else holds the rows: a forward that fails half-way must not have overwritten codes).
+static int check_fp8_only(const Ctx& c, const rtv_attn_fp8_shadow* sh) {
+  const rtv_dit_step* st = c.st;
+  for (int l = 0; l < c.L; ++l) {
+    if (!sh->k8[l] || !sh->v8t[l]) return set_error(-1, "dit: fp8 attention: a layer has no shadow");
+    if (((uintptr_t)sh->k8[l] | (uintptr_t)sh->v8t[l]) & 15) return set_error(-1, "dit: fp8 attention: k8 and v8t must be 16-byte aligned");
+    if (sh->amax && ((uintptr_t)sh->amax[l] & 3)) return set_error(-1, "dit: fp8 attention: amax must be 4-byte aligned");
+  }
+  if (!(std::isfinite(sh->k_scale) && sh->k_scale > 0.f && std::isfinite(sh->v_scale) && sh->v_scale > 0.f))
+    return set_error(-1, "dit: fp8 attention: scales must be finite and positive");
+  // (make_ctx: the written rows lie inside the window, and the window inside the ring when there is one)
+  const int64_t end = st->ring_size > 0 ? (int64_t)st->ring_lo + st->ring_size : (int64_t)st->kv_hi;
+  if (end > sh->cache_rows) return set_error(-1, "dit: fp8 attention: the attention window lies outside [0, cache_rows)");
+  int seg[3][2];
+  return cut_written_rows(st, st->cache_row0, c.M, seg) < 0 ? -1 : 0;
+}
+
 // The unsharded composition; fp8 != null: self-attention on the e4m3 shadows (rtv_dit_forward_attn_fp8), centers != null: whose K
-// codes are centred (rtv_dit_forward_attn_fp8_centered).
+// codes are centred (rtv_dit_forward_attn_fp8_centered); fp8_only: whose shadows are the whole cache (rtv_dit_forward_attn_fp8_only).
 static int dit_forward(const rtv_dit_config* cfg, const rtv_dit_weights* w, const rtv_dit_step* st, const rtv_attn_fp8_shadow* fp8,
-                       void* const* centers, void* workspace, size_t workspace_bytes, rtv_stream_t stream) {
+                       void* const* centers, bool fp8_only, void* workspace, size_t workspace_bytes, rtv_stream_t stream) {
   Ctx c;
   RTV_TRY(make_ctx(cfg, w, st, workspace, workspace_bytes, stream, &c));
   if (fp8) {
@@ -874,8 +928,10 @@ static int dit_forward(const rtv_dit_config* cfg, const rtv_dit_weights* w, cons
     if (centers)
       for (int l = 0; l < c.L; ++l)
         if (!centers[l]) return set_error(-1, "dit: fp8 attention: a layer has no K centre");
+    if (fp8_only) RTV_TRY(check_fp8_only(c, fp8));
     c.fp8 = fp8;
     c.centers = centers;
+    c.fp8_only = fp8_only;
   }
   if (c.r0 != 0 || c.rc != c.M)
     return set_error(-1, "dit_forward: sharded row ranges need the phase API (rtv_dit_begin/layer_qkv/layer_rest/head/finish)");
@@ -892,14 +948,14 @@ static int dit_forward(const rtv_dit_config* cfg, const rtv_dit_weights* w, cons
 
 extern "C" int rtv_dit_forward(const rtv_dit_config* cfg, const rtv_dit_weights* w, const rtv_dit_step* st,
                                void* workspace, size_t workspace_bytes, rtv_stream_t stream) {
-  return dit_forward(cfg, w, st, nullptr, nullptr, workspace, workspace_bytes, stream);
+  return dit_forward(cfg, w, st, nullptr, nullptr, false, workspace, workspace_bytes, stream);
 }
 
 extern "C" int rtv_dit_forward_attn_fp8(const rtv_dit_config* cfg, const rtv_dit_weights* w, const rtv_dit_step* st,
                                         const rtv_attn_fp8_shadow* shadow, void* workspace, size_t workspace_bytes,
                                         rtv_stream_t stream) {
   if (!shadow) return set_error(-1, "dit: fp8 attention needs its shadow (rtv_attn_fp8_shadow)");
-  return dit_forward(cfg, w, st, shadow, nullptr, workspace, workspace_bytes, stream);
+  return dit_forward(cfg, w, st, shadow, nullptr, false, workspace, workspace_bytes, stream);
 }
 
 extern "C" int rtv_dit_forward_attn_fp8_centered(const rtv_dit_config* cfg, const rtv_dit_weights* w, const rtv_dit_step* st,
@@ -907,7 +963,14 @@ extern "C" int rtv_dit_forward_attn_fp8_centered(const rtv_dit_config* cfg, cons
                                                  size_t workspace_bytes, rtv_stream_t stream) {
   if (!shadow) return set_error(-1, "dit: fp8 attention needs its shadow (rtv_attn_fp8_shadow)");
   if (!centers) return set_error(-1, "dit: centred fp8 attention needs its table of K centres");
-  return dit_forward(cfg, w, st, shadow, centers, workspace, workspace_bytes, stream);
+  return dit_forward(cfg, w, st, shadow, centers, false, workspace, workspace_bytes, stream);
+}
+
+extern "C" int rtv_dit_forward_attn_fp8_only(const rtv_dit_config* cfg, const rtv_dit_weights* w, const rtv_dit_step* st,
+                                             const rtv_attn_fp8_shadow* shadow, void* workspace, size_t workspace_bytes,
+                                             rtv_stream_t stream) {
+  if (!shadow) return set_error(-1, "dit: fp8 attention needs its shadow (rtv_attn_fp8_shadow)");
+  return dit_forward(cfg, w, st, shadow, nullptr, true, workspace, workspace_bytes, stream);
 }
 
 // ---- the sharded phases with the self-attention in fp8 (rtv_hip_attn_fp8_cp.h)

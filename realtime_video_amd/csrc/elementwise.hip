@@ -4,6 +4,7 @@
 // (8 x bf16) vector.
 // bf16 rounding points follow the reference's eager chains (cited per kernel in include/rtv_hip.h).
 #include "ln_row.h"
+#include "rope_row.h"
 #include "rtv_common.h"
 #include "rtv_internal.h"
 
@@ -65,19 +66,6 @@ __global__ __launch_bounds__(EW_THREADS) void rmsnorm_kernel(const bf16_t* __res
 // RMSNorm were rebuilt with one WAVE per row (all of a lane's chunks in registers, DPP sums, no LDS, no barrier) and came out 5-10 %
 // SLOWER than the one-workgroup-per-row kernels above, stand-alone and inside the forward (20.8 vs 18.7 ms per block): those stay.
 // The RoPE / cache kernel (3x the bytes per row, two independent norms) does gain from the wave form: 81 -> 64 us.
-// Make the compiler forget what it knows about a register-resident chunk: the row kernels unpack their raw bf16 chunks once per
-// pass; without this the unpacked floats of the first pass are kept (CSE) for the later ones - 8 registers per chunk instead of 4 -
-// and the kernels spill or lose occupancy.
-__device__ __forceinline__ void launder(u32x4& v) {
-  uint32_t a = v[0], b = v[1], c = v[2], e = v[3];
-  asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(e));
-  v[0] = a;
-  v[1] = b;
-  v[2] = c;
-  v[3] = e;
-}
-
-constexpr int ROWS_PER_WG = 4;
 
 // ------------------------------------------------------------------ RMSNorm(q,k) + RoPE + KV-cache write
 struct RopeArgs {
@@ -103,16 +91,6 @@ struct RopeArgs {
   int parts;   // bit 0: process q, bit 1: process k and v (the split projection of the context-parallel overlap; 3 = all);
                // bit 2 (with bit 1): V is in the cache already (written there by the projection GEMM, r05) - no copy
 };
-
-// rotate the 4 complex pairs of one 8-element chunk by the (cos, sin) values in w[0..4)
-__device__ __forceinline__ void rope8(float* x, const float2* w) {
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    const float a = x[2 * t], b = x[2 * t + 1];
-    x[2 * t] = a * w[t].x - b * w[t].y;
-    x[2 * t + 1] = a * w[t].y + b * w[t].x;
-  }
-}
 
 // LANE_CS: head_dim divides 512 (always on the DiT path: 128), so the column of a lane's chunks inside a head - ((lane + 64 i) * 8)
 // % hd - does not depend on i: the four (cos, sin) pairs a lane rotates with are the SAME for all of its chunks of q and of k; they
@@ -337,15 +315,6 @@ __global__ __launch_bounds__(EW_THREADS) void qk_norm_rope_cache_block_kernel(Ro
     }
   }
 }
-
-// chunks per lane for a row of d elements: the smallest compiled CPL with d <= CPL * 512
-#define RTV_ROW_DISPATCH(d, CALL)      \
-  do {                                  \
-    if ((d) <= 1024) { CALL(2); }       \
-    else if ((d) <= 2048) { CALL(4); }  \
-    else if ((d) <= 5120) { CALL(10); } \
-    else { CALL(16); }                  \
-  } while (0)
 
 // ------------------------------------------------------------------ small per-forward tables
 __global__ void modulation_table_kernel(const bf16_t* __restrict__ mod, const bf16_t* __restrict__ e0,

@@ -343,6 +343,34 @@ def attn_fwd_fp8(q, k8, v8t, seg0, seg1=(0, 0), out=None, scale=None, k_scale=1.
     return out
 
 
+def qk_norm_rope_k8(qkv, k8, cache_row0, num_heads, wq, wk, rope_cs, grid, start_frame, eps=1e-6, q_out=None, row_offset=0,
+                    ring=(0, 0, 0), k_scale=1.0, amax=None, want_q=True):
+    """qk_norm_rope_cache with the K rows stored as e4m3 codes in k8 [cache_rows, H, 128] and no V role (rtv_qk_norm_rope_k8,
+    include/rtv_hip_attn_fp8_only.h).  amax: optional float32 [2], [0] follows |k|.  want_q=False: no q role (the kv_only pass).
+    A thin wrapper: the entry point itself refuses what it documents."""
+    _gpu(qkv, k8, wq, wk, rope_cs, q_out, amax)
+    M, d3 = qkv.shape
+    d = d3 // 3
+    F, gh, gw = grid
+    if q_out is None and want_q:
+        q_out = torch.empty((M, d), dtype=qkv.dtype, device=qkv.device)
+    _lib.call("rtv_qk_norm_rope_k8", _ptr(qkv), _ptr(q_out) if want_q else None, _ptr(k8), k8.shape[0], float(k_scale), _ptr(amax),
+              int(cache_row0), M, d, int(num_heads), float(eps), _ptr(wq), _ptr(wk), _ptr(rope_cs), int(F), int(gh), int(gw),
+              int(start_frame), int(row_offset), int(ring[0]), int(ring[1]), int(ring[2]), _stream())
+    return q_out
+
+
+def attn_quantize_v_rows(v_src, v8t, cache_rows, dst_row0, v_scale=1.0, amax=None):
+    """Quantise the bf16 rows v_src [rows, H, 128] (any row stride: the V third of a projection buffer is fine) into the physical rows
+    [dst_row0, dst_row0 + rows) of v8t (rtv_attn_quantize_v_rows, include/rtv_hip_attn_fp8_only.h).  amax: optional float32 [2], [1]
+    follows |v|.  A thin wrapper: the entry point itself refuses what it documents."""
+    _gpu(v_src, v8t, amax)
+    rows, H = v_src.shape[0], v_src.shape[1]
+    _lib.call("rtv_attn_quantize_v_rows", _ptr(v_src), v_src.stride(0), rows, H, _ptr(v8t), int(cache_rows), int(dst_row0), float(v_scale),
+              _ptr(amax), _stream())
+    return v8t
+
+
 # --------------------------------------------------------------------------------------- GEMM
 _gemm_ws = {}
 

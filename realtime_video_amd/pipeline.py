@@ -8,7 +8,9 @@ list-of-dicts contract (:305-311, :333-338):
 
 MI355X layout: every layer's K and V live in ONE arena allocation ([L, 2, B, kv_size, H, 128], sized for
 288 GB HBM: the full 32760-token cache of the 14B model is 26.8 GB); the dict entries are views, so a
-reset is a single memset and the native forward receives plain base pointers.
+reset is a single memset and the native forward receives plain base pointers.  With the model in
+`enable_fp8_attention(bf16_cache=False)` there is no arena: kv_cache1[i] is the compact dict of
+`CausalWanModel.new_fp8_kv_cache` ({"k8", "v8t", "rows", the two indices}; 13.4 GB at 14B).
 """
 import types
 
@@ -50,7 +52,26 @@ class CausalInferencePipeline:
         model = self.generator.model
         heads = model.kv_cache_heads() if hasattr(model, "kv_cache_heads") else cfg.num_heads
         shape = [batch_size, kv_cache_size, heads, cfg.dim // cfg.num_heads]
-        if self.kv_cache1 and list(self.kv_cache1[0]["k"].shape) == shape and self.kv_cache1[0]["k"].dtype == dtype:
+        if getattr(model, "_fp8_attention_only", lambda: False)():
+            # enable_fp8_attention(bf16_cache=False): the compact dicts of new_fp8_kv_cache - two e4m3 arrays per layer and no bf16
+            # arena.  A reset is the index reset below (rows outside the window are masked by the attention kernel).
+            if batch_size != 1:
+                raise NotImplementedError("the e4m3-only KV cache is built for batch size 1 (the streaming server path)")
+            c0 = self.kv_cache1[0] if self.kv_cache1 else {}
+            if "k" not in c0 and c0.get("rows") == kv_cache_size:
+                for c in self.kv_cache1:
+                    if getattr(self, "zero_on_reset", True):
+                        c["k8"].zero_()
+                        c["v8t"].zero_()
+                    c["global_end_index"] = 0
+                    c["local_end_index"] = 0
+                return
+            self._kv_arena = None
+            self.kv_cache1 = model.new_fp8_kv_cache(kv_cache_size, device)
+            self.k_shape = self.v_shape = shape
+            return
+        if self.kv_cache1 and "k" in self.kv_cache1[0] and list(self.kv_cache1[0]["k"].shape) == shape \
+                and self.kv_cache1[0]["k"].dtype == dtype:
             # Reset.  The reference zero_()s all L x 2 tensors (causal_inference.py:296-303; 7.7 GB of HBM writes per block
             # at 14B).  The forward only ever reads rows [.., local_end_index) and writes every row of that
             # window first, so with `zero_on_reset = False` (set by GenerationSession) only the indices are reset.
