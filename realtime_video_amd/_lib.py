@@ -12,7 +12,8 @@ include/rtv_hip_attn_fp8_cp.h (ATTN_FP8_CP_PROTOTYPES), and the e4m3-only KV cac
 include/rtv_hip_attn_fp8_only.h (ATTN_FP8_ONLY_PROTOTYPES), and the MXFP4 Linears, include/rtv_hip_mxfp4.h (MXFP4_PROTOTYPES), and the MXFP6
 Linears, include/rtv_hip_mxfp6.h (MXFP6_PROTOTYPES), and the block Hadamard rotation in front of both quantisers,
 include/rtv_hip_mx_rotate.h (MX_ROTATE_PROTOTYPES), and the unit entry points of the text encoder's kernels,
-include/rtv_hip_t5_units.h (T5_UNITS_PROTOTYPES).
+include/rtv_hip_t5_units.h (T5_UNITS_PROTOTYPES), and the text encoder on e4m3 weights with its skinny-M weight-only GEMM,
+include/rtv_hip_t5_w8.h (T5_W8_STRUCTS / T5_W8_PROTOTYPES).
 
 The product path has no CPU / eager fallback: if the library is missing or a kernel reports an
 error, a RuntimeError is raised (the reference's attention()/pipeline API reports errors as Python
@@ -152,6 +153,10 @@ MX_ROTATE_HEADER = "rtv_hip_mx_rotate.h"   # the rotated MXFP4 / MXFP6 quantiser
 MX_ROTATE_PROTOTYPES = parse_header(_read(MX_ROTATE_HEADER), dict(STRUCTS))
 T5_UNITS_HEADER = "rtv_hip_t5_units.h"   # one launcher per kernel of the text encoder, for its unit tests: no struct of its own
 T5_UNITS_PROTOTYPES = parse_header(_read(T5_UNITS_HEADER), dict(STRUCTS))
+T5_W8_HEADER = "rtv_hip_t5_w8.h"   # the text encoder on e4m3 weights: its two weight structs stay out of STRUCTS
+T5_W8_STRUCTS = dict(STRUCTS)
+T5_W8_PROTOTYPES = parse_header(_read(T5_W8_HEADER), T5_W8_STRUCTS)
+T5_W8_STRUCTS = {k: v for k, v in T5_W8_STRUCTS.items() if k not in STRUCTS}
 MX_ROT_ACT_SHIFT, MX_ROT_WEIGHT_SHIFT, MX_ROT_MAX_SHIFT = (
     int(re.search(rf"^#define\s+RTV_MX_ROT_{n}_SHIFT\s+(\d+)", _read(MX_ROTATE_HEADER), flags=re.M).group(1)) for n in ("ACT", "WEIGHT", "MAX"))
 LORA_MAX_ADAPTERS, LORA_MAX_RANK = (int(re.search(rf"^#define\s+RTV_LORA_MAX_{n}\s+(\d+)", _read(LORA_HEADER), flags=re.M).group(1))
@@ -194,7 +199,7 @@ def load():
             f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C realtime_video_amd/csrc`). There is no CPU fallback for the HIP path.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(IO_PROTOTYPES.items()) + list(JPEG_PROTOTYPES.items()) + list(JPEGDEC_PROTOTYPES.items()) + list(LORA_PROTOTYPES.items()) + list(LORA_EXT_PROTOTYPES.items()) + list(CROSS_FOLD_PROTOTYPES.items()) + list(FP8_ROWS_PROTOTYPES.items()) + list(ATTN_FP8_PROTOTYPES.items()) + list(ATTN_FP8_CENTER_PROTOTYPES.items()) + list(ATTN_FP8_CP_PROTOTYPES.items()) + list(ATTN_FP8_ONLY_PROTOTYPES.items()) + list(MXFP4_PROTOTYPES.items()) + list(MXFP6_PROTOTYPES.items()) + list(MX_ROTATE_PROTOTYPES.items()) + list(T5_UNITS_PROTOTYPES.items()):
+    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(IO_PROTOTYPES.items()) + list(JPEG_PROTOTYPES.items()) + list(JPEGDEC_PROTOTYPES.items()) + list(LORA_PROTOTYPES.items()) + list(LORA_EXT_PROTOTYPES.items()) + list(CROSS_FOLD_PROTOTYPES.items()) + list(FP8_ROWS_PROTOTYPES.items()) + list(ATTN_FP8_PROTOTYPES.items()) + list(ATTN_FP8_CENTER_PROTOTYPES.items()) + list(ATTN_FP8_CP_PROTOTYPES.items()) + list(ATTN_FP8_ONLY_PROTOTYPES.items()) + list(MXFP4_PROTOTYPES.items()) + list(MXFP6_PROTOTYPES.items()) + list(MX_ROTATE_PROTOTYPES.items()) + list(T5_UNITS_PROTOTYPES.items()) + list(T5_W8_PROTOTYPES.items()):
         fn = getattr(lib, name, None)
         if fn is None:
             # RTV_LIB_PATH = an older build of the same C ABI (A/B measurements): entry points added since are simply absent

@@ -8,6 +8,8 @@
 // Precision: the reference holds this model in float32 with bf16-representable weights (bf16 checkpoint, wan_wrapper.py:24-33).
 // Here the residual stream and every normalisation / softmax / gating stay float32; the linears run on the bf16 MFMA GEMM of
 // gemm.hip (fp32 accumulation) with their inputs rounded to bf16 - weights are exact, activations see one rounding per linear.
+// rtv_t5_encode_w8 (include/rtv_hip_t5_w8.h) is the same layer loop with the five linears on e4m3 weight codes and per-row scales
+// (gemm_w8.hip): same activations, same rounding points, the weights rounded to e4m3 once when the mode is enabled.
 //
 // Attention (head_dim 64, <= 512 tokens, 64 heads): one wave per (head, 32 queries), no LDS.  S^T = K . Q^T with K rows read
 // straight from the q|k buffer as the MFMA A operand; O^T += V^T . P^T with P^T = the lane's own S^T registers and V^T read
@@ -17,6 +19,7 @@
 #include "rtv_common.h"
 #include "rtv_internal.h"
 #include "../../include/rtv_hip_t5_units.h"
+#include "../../include/rtv_hip_t5_w8.h"
 
 namespace rtv {
 
@@ -334,6 +337,82 @@ extern "C" int rtv_t5_attention(const void* qk, const void* vt, void* o, const v
   return t5_launch_attention(qk, vt, o, bias, rows, valid, num_heads, max_len, (hipStream_t)stream);
 }
 
+namespace {
+
+// The five Linears of a layer, as the two encoders launch them: the bf16 one on rtv_gemm (V^T = W_v . n^T), the e4m3-weight one on
+// rtv_gemm_w8 (V^T by its transposed store).  t5_encode_body is everything else, shared.
+struct T5LinearsBf16 {
+  typedef rtv_t5_layer_weights Layer;
+  int rows, d, da, dff;
+  rtv_stream_t s;
+  int qk(const Layer& lw, const T5Buffers& b) const { return t5_gemm(b.xn, d, lw.qk_w, d, b.qk, 2 * da, rows, 2 * da, d, s); }            // q | k
+  int v(const Layer& lw, const T5Buffers& b) const { return t5_gemm(lw.v_w, d, b.xn, d, b.vt, rows, da, rows, d, s); }                    // V^T = W_v . n^T
+  int o(const Layer& lw, const T5Buffers& b) const { return t5_gemm(b.ao, da, lw.o_w, da, b.tmp, d, rows, d, da, s); }
+  int gate_fc1(const Layer& lw, const T5Buffers& b) const { return t5_gemm(b.xn, d, lw.gate_fc1_w, d, b.gf, 2 * dff, rows, 2 * dff, d, s); }  // gate | fc1
+  int fc2(const Layer& lw, const T5Buffers& b) const { return t5_gemm(b.h, dff, lw.fc2_w, dff, b.tmp, d, rows, d, dff, s); }
+};
+
+struct T5LinearsW8 {
+  typedef rtv_t5_layer_weights_w8 Layer;
+  int rows, d, da, dff;
+  rtv_stream_t s;
+  void* ws;
+  size_t ws_bytes;
+  int run(const void* a, const void* codes, const void* scales, void* c, int ldc, int transpose, int N, int K) const {
+    return rtv_gemm_w8(a, K, codes, K, (const float*)scales, c, ldc, transpose, rows, N, K, ws, ws_bytes, s);
+  }
+  int qk(const Layer& lw, const T5Buffers& b) const { return run(b.xn, lw.qk_q, lw.qk_s, b.qk, 2 * da, 0, 2 * da, d); }
+  int v(const Layer& lw, const T5Buffers& b) const { return run(b.xn, lw.v_q, lw.v_s, b.vt, rows, 1, da, d); }
+  int o(const Layer& lw, const T5Buffers& b) const { return run(b.ao, lw.o_q, lw.o_s, b.tmp, d, 0, d, da); }
+  int gate_fc1(const Layer& lw, const T5Buffers& b) const { return run(b.xn, lw.gate_fc1_q, lw.gate_fc1_s, b.gf, 2 * dff, 0, 2 * dff, d); }
+  int fc2(const Layer& lw, const T5Buffers& b) const { return run(b.h, lw.fc2_q, lw.fc2_s, b.tmp, d, 0, d, dff); }
+};
+
+// largest K-split workspace of the five Linears at `rows` rows
+static size_t t5_w8_gemm_bytes(const rtv_t5_config* c, int rows) {
+  const int shapes[5][2] = {{2 * c->dim_attn, c->dim}, {c->dim_attn, c->dim}, {c->dim, c->dim_attn}, {2 * c->dim_ffn, c->dim},
+                            {c->dim, c->dim_ffn}};
+  size_t most = 0;
+  for (auto& nk : shapes) {
+    const size_t b = rtv_gemm_w8_workspace_bytes(rows, nk[0], nk[1]);
+    most = b > most ? b : most;
+  }
+  return most;
+}
+
+template <class Linears>
+static int t5_encode_body(const rtv_t5_config* cfg, const typename Linears::Layer* layers, const void* token_embedding,
+                          const void* final_norm_w, int max_len, const int* ids, int seq_len, int out_rows, const T5Buffers& b,
+                          const Linears& lin, void* out, hipStream_t st) {
+  const int d = cfg->dim, H = cfg->num_heads, dff = cfg->dim_ffn, rows = lin.rows;
+  const size_t n8 = (size_t)rows * d / 8;
+
+  T5_TRY(t5_launch_embed(ids, token_embedding, b.x, rows, seq_len, d, cfg->vocab, st));
+  for (int l = 0; l < cfg->num_layers; ++l) {
+    const typename Linears::Layer& lw = layers[l];
+    T5_TRY(t5_launch_rmsnorm(b.x, lw.norm1_w, b.xn, rows, d, cfg->eps, false, st));
+    T5_TRY(lin.qk(lw, b));
+    T5_TRY(lin.v(lw, b));
+    T5_TRY(t5_launch_attention(b.qk, b.vt, b.ao, lw.pos_bias, rows, seq_len, H, max_len, st));
+    T5_TRY(lin.o(lw, b));
+    T5_TRY(t5_launch_add(b.x, b.tmp, n8, st));
+    T5_TRY(t5_launch_rmsnorm(b.x, lw.norm2_w, b.xn, rows, d, cfg->eps, false, st));
+    T5_TRY(lin.gate_fc1(lw, b));
+    T5_TRY(t5_launch_geglu(b.gf, b.h, rows, dff, st));
+    T5_TRY(lin.fc2(lw, b));
+    T5_TRY(t5_launch_add(b.x, b.tmp, n8, st));
+  }
+  // final norm on the prompt's rows; padding rows of the output are zero (wan_wrapper.py:52-53)
+  T5_TRY(t5_launch_rmsnorm(b.x, final_norm_w, out, seq_len, d, cfg->eps, true, st));
+  if (out_rows > seq_len) {
+    hipError_t e = hipMemsetAsync((float*)out + (size_t)seq_len * d, 0, (size_t)(out_rows - seq_len) * d * 4, st);
+    if (e != hipSuccess) return set_error(e, "t5_encode: hipMemsetAsync");
+  }
+  return 0;
+}
+
+}  // namespace
+
 extern "C" int rtv_t5_encode(const rtv_t5_config* cfg, const rtv_t5_weights* w, const int* ids, int seq_len, int out_rows,
                              void* workspace, size_t workspace_bytes, void* out, rtv_stream_t stream) {
   if (!cfg || !w || !ids || !workspace || !out) return set_error(-1, "t5_encode: null argument");
@@ -348,29 +427,33 @@ extern "C" int rtv_t5_encode(const rtv_t5_config* cfg, const rtv_t5_weights* w, 
   bool ok = true;
   t5_carve(cfg, rows, (char*)workspace, workspace_bytes, &b, &ok);
   if (!ok) return set_error(-1, "t5_encode: workspace too small (see rtv_t5_workspace_bytes)");
-  hipStream_t st = (hipStream_t)stream;
-  const size_t n8 = (size_t)rows * d / 8;
+  return t5_encode_body(cfg, w->layers, w->token_embedding, w->final_norm_w, w->max_len, ids, seq_len, out_rows, b,
+                        T5LinearsBf16{rows, d, da, dff, stream}, out, (hipStream_t)stream);
+}
 
-  T5_TRY(t5_launch_embed(ids, w->token_embedding, b.x, rows, seq_len, d, cfg->vocab, st));
-  for (int l = 0; l < cfg->num_layers; ++l) {
-    const rtv_t5_layer_weights& lw = w->layers[l];
-    T5_TRY(t5_launch_rmsnorm(b.x, lw.norm1_w, b.xn, rows, d, cfg->eps, false, st));
-    T5_TRY(t5_gemm(b.xn, d, lw.qk_w, d, b.qk, 2 * da, rows, 2 * da, d, stream));        // q | k
-    T5_TRY(t5_gemm(lw.v_w, d, b.xn, d, b.vt, rows, da, rows, d, stream));                // V^T = W_v . n^T
-    T5_TRY(t5_launch_attention(b.qk, b.vt, b.ao, lw.pos_bias, rows, seq_len, H, w->max_len, st));
-    T5_TRY(t5_gemm(b.ao, da, lw.o_w, da, b.tmp, d, rows, d, da, stream));
-    T5_TRY(t5_launch_add(b.x, b.tmp, n8, st));
-    T5_TRY(t5_launch_rmsnorm(b.x, lw.norm2_w, b.xn, rows, d, cfg->eps, false, st));
-    T5_TRY(t5_gemm(b.xn, d, lw.gate_fc1_w, d, b.gf, 2 * dff, rows, 2 * dff, d, stream));  // gate | fc1
-    T5_TRY(t5_launch_geglu(b.gf, b.h, rows, dff, st));
-    T5_TRY(t5_gemm(b.h, dff, lw.fc2_w, dff, b.tmp, d, rows, d, dff, stream));
-    T5_TRY(t5_launch_add(b.x, b.tmp, n8, st));
-  }
-  // final norm on the prompt's rows; padding rows of the output are zero (wan_wrapper.py:52-53)
-  T5_TRY(t5_launch_rmsnorm(b.x, w->final_norm_w, out, seq_len, d, cfg->eps, true, st));
-  if (out_rows > seq_len) {
-    hipError_t e = hipMemsetAsync((float*)out + (size_t)seq_len * d, 0, (size_t)(out_rows - seq_len) * d * 4, st);
-    if (e != hipSuccess) return set_error(e, "t5_encode: hipMemsetAsync");
-  }
-  return 0;
+extern "C" size_t rtv_t5_w8_workspace_bytes(const rtv_t5_config* cfg, int seq_len) {
+  if (!cfg || seq_len <= 0) return 0;
+  const int rows = t5_rows(seq_len);
+  const size_t buffers = (t5_carve(cfg, rows, nullptr, 0, nullptr, nullptr) + 255) & ~(size_t)255;
+  return buffers + t5_w8_gemm_bytes(cfg, rows) + 256;
+}
+
+extern "C" int rtv_t5_encode_w8(const rtv_t5_config* cfg, const rtv_t5_weights_w8* w, const int* ids, int seq_len, int out_rows,
+                                void* workspace, size_t workspace_bytes, void* out, rtv_stream_t stream) {
+  if (!cfg || !w || !ids || !workspace || !out) return set_error(-1, "t5_encode_w8: null argument");
+  const int d = cfg->dim, da = cfg->dim_attn, dff = cfg->dim_ffn, H = cfg->num_heads;
+  if (H <= 0 || da != H * 64) return set_error(-1, "t5_encode_w8: head_dim must be 64 (dim_attn = 64 * num_heads)");
+  if (d % 128 || dff % 128 || da % 128) return set_error(-1, "t5_encode_w8: dim, dim_attn, dim_ffn must be multiples of 128");
+  if (seq_len <= 0 || seq_len > w->max_len || out_rows < seq_len)
+    return set_error(-1, "t5_encode_w8: need 0 < seq_len <= max_len (the bias tables' length) and out_rows >= seq_len");
+  if (((uintptr_t)workspace) & 255) return set_error(-1, "t5_encode_w8: workspace must be 256-byte aligned");
+  const int rows = t5_rows(seq_len);
+  T5Buffers b;
+  bool ok = true;
+  const size_t buffers = (t5_carve(cfg, rows, (char*)workspace, workspace_bytes, &b, &ok) + 255) & ~(size_t)255;
+  const size_t gemm_bytes = t5_w8_gemm_bytes(cfg, rows);
+  if (!ok || buffers + gemm_bytes > workspace_bytes)
+    return set_error(-1, "t5_encode_w8: workspace too small (see rtv_t5_w8_workspace_bytes)");
+  return t5_encode_body(cfg, w->layers, w->token_embedding, w->final_norm_w, w->max_len, ids, seq_len, out_rows, b,
+                        T5LinearsW8{rows, d, da, dff, stream, (char*)workspace + buffers, gemm_bytes}, out, (hipStream_t)stream);
 }

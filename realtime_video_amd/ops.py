@@ -531,6 +531,28 @@ def gemm_fp8_rows(a_q, a_scales, w_q, w_scales, bias=None, act=ACT_NONE, gate=No
     return out
 
 
+def gemm_w8(a, w_q, w_scales, out=None, transpose_out=False, workspace=None):
+    """Weight-only fp8 GEMM at prompt length (include/rtv_hip_t5_w8.h): out bf16 = bf16((a @ value(w_q)^T)[m, n] * w_scales[n])
+    for bf16 rows a [M, K] and e4m3 codes w_q [N, K]; out is [M, N], or [N, M] with transpose_out.  The K-split slabs live in
+    `workspace` (a uint8 tensor; allocated per call when None)."""
+    _gpu(a, w_q, w_scales, out, workspace)
+    if a.dtype != torch.bfloat16 or w_q.dtype != torch.float8_e4m3fn or w_scales.dtype != torch.float32:
+        raise TypeError("gemm_w8 expects bf16 rows, float8_e4m3fn codes and fp32 scales")
+    M, K = a.shape
+    N = w_q.shape[0]
+    if w_q.shape[1] != K or a.stride(1) != 1 or w_q.stride(1) != 1 or w_scales.shape != (N,) or not w_scales.is_contiguous():
+        raise ValueError("gemm_w8 shape / stride mismatch")
+    if out is None:
+        out = torch.empty((N, M) if transpose_out else (M, N), dtype=torch.bfloat16, device=a.device)
+    need = _lib.load().rtv_gemm_w8_workspace_bytes(M, N, K)
+    if workspace is None and need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=a.device)
+    _lib.call("rtv_gemm_w8", _ptr(a), a.stride(0), _ptr(w_q), w_q.stride(0), _ptr(w_scales), _ptr(out), out.stride(0),
+              int(bool(transpose_out)), M, N, K, _ptr(workspace), ctypes.c_size_t(workspace.numel() if workspace is not None else 0),
+              _stream())
+    return out
+
+
 # ------------------------------------------------------- block-scaled paths (include/rtv_hip_mxfp4.h, include/rtv_hip_mxfp6.h)
 class _MxFormat(collections.namedtuple("_MxFormat", "name group_elems group_bytes scale_align k_multiple min_codes")):
     """A block-scaled format: `group_elems` codes fill `group_bytes` bytes, a row's scales are padded to `scale_align` bytes, the

@@ -1,6 +1,7 @@
 """Mirror of the reference's `WanTextEncoder` (utils/wan_wrapper.py:20-56): UMT5-XXL encoder (wan/modules/t5.py:267-313,
 config :456-469) from prompts to `{"prompt_embeds": [B, 512, 4096]}` with the padding rows zeroed, backed by the native
-`rtv_t5_encode` (include/rtv_hip.h; realtime_video_amd/csrc/t5_encoder.hip).  Runs once per prompt and once per prompt
+`rtv_t5_encode` (include/rtv_hip.h; realtime_video_amd/csrc/t5_encoder.hip), or after `enable_fp8_weights()` by
+`rtv_t5_encode_w8` on e4m3 weights (include/rtv_hip_t5_w8.h; realtime_video_amd/csrc/gemm_w8.hip).  Runs once per prompt and once per prompt
 transition (release_server.py:402-404 / interpolate_prompt_embeds), never inside the block loop.
 
 State-dict keys are the reference's (`models_t5_umt5-xxl-enc-bf16.safetensors`, wan_wrapper.py:30-33):
@@ -28,6 +29,9 @@ UMT5_XXL = dict(vocab=256384, dim=4096, dim_attn=4096, dim_ffn=10240, num_heads=
 _T5Cfg = _lib.STRUCTS["rtv_t5_config"]
 _T5Layer = _lib.STRUCTS["rtv_t5_layer_weights"]
 _T5Weights = _lib.STRUCTS["rtv_t5_weights"]
+_T5LayerW8 = _lib.T5_W8_STRUCTS["rtv_t5_layer_weights_w8"]
+_T5WeightsW8 = _lib.T5_W8_STRUCTS["rtv_t5_weights_w8"]
+_LINEARS = ("qk", "v", "o", "gate_fc1", "fc2")      # the five matrices of a layer as load_state_dict keeps them
 
 
 def relative_position_bucket(rel_pos, num_buckets=32, max_dist=128):
@@ -56,6 +60,7 @@ class WanTextEncoder:
         self._t = {}
         self._w = None
         self._ws = None
+        self._fp8 = False
         if isinstance(tokenizer, str):
             from transformers import AutoTokenizer
             hf = AutoTokenizer.from_pretrained(tokenizer)
@@ -117,7 +122,55 @@ class WanTextEncoder:
         self._t = t
         self._cfg = _T5Cfg(c["vocab"], c["dim"], c["dim_attn"], c["dim_ffn"], H, L, 1e-6)
         self._w = _T5Weights(t["token_embedding"].data_ptr(), t["final_norm"].data_ptr(), self._layers, self.text_len)
+        self._fp8 = False            # a fresh state dict is bf16 again (enable_fp8_weights is called after loading)
         return self
+
+    def enable_fp8_weights(self):
+        """Opt-in e4m3 weight storage (include/rtv_hip_t5_w8.h): the five matrices of every layer are quantised on the device by
+        rtv_quantize_fp8_rows (one scale per output channel; q | k and gate | fc1 stay concatenated), their bf16 copies are
+        dropped, and encode_ids runs rtv_t5_encode_w8: bf16 activations on the weight-only fp8 GEMM.  The embedding table, the
+        norm weights and the bias tables stay as they are.  Call it after load_state_dict / init_random_weights; a second call
+        does nothing; a later load_state_dict returns to bf16."""
+        if self._w is None:
+            raise RuntimeError("weights not loaded")
+        if self.device.type != "cuda":
+            raise RuntimeError("the text encoder runs on the GPU only (no CPU fallback)")
+        if self._fp8:
+            return self
+        t = self._t
+        stream = c_vp(torch.cuda.current_stream().cuda_stream)
+        layers = (_T5LayerW8 * self.cfg["num_layers"])()
+        for i in range(self.cfg["num_layers"]):
+            p = f"blocks.{i}"
+            lw = layers[i]
+            for name in _LINEARS:
+                w = t.pop(f"{p}.{name}")
+                n, k = w.shape
+                codes = torch.empty((n, k), dtype=torch.uint8, device=self.device)
+                scales = torch.empty((n,), dtype=torch.float32, device=self.device)
+                _lib.call("rtv_quantize_fp8_rows", c_vp(w.data_ptr()), k, n, k, c_vp(codes.data_ptr()), k,
+                          c_vp(scales.data_ptr()), stream)
+                t[f"{p}.{name}.codes"], t[f"{p}.{name}.scales"] = codes, scales
+                setattr(lw, name + "_q", codes.data_ptr())
+                setattr(lw, name + "_s", scales.data_ptr())
+                del w                # stream-ordered: the caching allocator reuses the block behind the quantiser on this stream
+            for f, k in (("norm1_w", ".norm1"), ("norm2_w", ".norm2"), ("pos_bias", ".pos_bias")):
+                setattr(lw, f, t[p + k].data_ptr())
+        self._layers = layers
+        self._w = _T5WeightsW8(t["token_embedding"].data_ptr(), t["final_norm"].data_ptr(), layers, self.text_len)
+        self._fp8 = True
+        return self
+
+    def weight_bytes(self):
+        """Resident bytes of the weights: {"linears": the five matrices of every layer (with their scales in the e4m3 mode),
+        "embedding": the token table, "other": norm weights and bias tables, "total": their sum}."""
+        out = {"linears": 0, "embedding": 0, "other": 0}
+        for name, v in self._t.items():
+            kind = ("embedding" if name == "token_embedding" else
+                    "linears" if name.split(".")[-1] in _LINEARS + ("codes", "scales") else "other")
+            out[kind] += v.numel() * v.element_size()
+        out["total"] = sum(out.values())
+        return out
 
     def init_random_weights(self, seed=0):
         """Random weights of this architecture generated on the GPU (there is no checkpoint offline), init_weights' scales
@@ -163,12 +216,13 @@ class WanTextEncoder:
                 continue
             if not bool(mask[b, :n].all()):
                 raise ValueError("attention masks must be prefixes (tokens first, padding after)")
-            need = _lib.load().rtv_t5_workspace_bytes(ctypes.byref(self._cfg), n)
+            entry = "rtv_t5_encode_w8" if self._fp8 else "rtv_t5_encode"
+            need = getattr(_lib.load(), "rtv_t5_w8_workspace_bytes" if self._fp8 else "rtv_t5_workspace_bytes")(ctypes.byref(self._cfg), n)
             if self._ws is None or self._ws.numel() < need + 256:
                 self._ws = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
             ws_ptr = (self._ws.data_ptr() + 255) & ~255
             row = ids[b, :n].to(device=self.device, dtype=torch.int32).contiguous()
-            _lib.call("rtv_t5_encode", ctypes.byref(self._cfg), ctypes.byref(self._w), c_vp(row.data_ptr()), n, L,
+            _lib.call(entry, ctypes.byref(self._cfg), ctypes.byref(self._w), c_vp(row.data_ptr()), n, L,
                       c_vp(ws_ptr), ctypes.c_size_t(self._ws.numel() - (ws_ptr - self._ws.data_ptr())),
                       c_vp(out[b].data_ptr()), stream)
         return {"prompt_embeds": out}
