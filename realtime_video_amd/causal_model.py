@@ -161,6 +161,8 @@ class CausalWanModel:
         self._fp8_attn_center = None        # float32 [num_layers, H, 128], zero-filled, allocated once; fp8_attention_recenter() writes it
         self._fp8_attn_center_ws = None     # workspace of the mean kernel, allocated with the centre
         self._fp8_attn_center_epoch = 0     # bumps at every recentre: part of a shadow's "fp8_filled" state, like the scales
+        self._fp8_attn_center_new = None    # smooth_k="codes": the second centre buffer a recentre computes into, allocated with the first
+        self._fp8_attn_prev = None          # the (k_scale, v_scale, epoch, smooth_k) an enable call replaced: convert_kv_cache_to_fp8
         self.lora_version = 0         # bumps when a merge changes ck / cv / co (weight or bias) or cnorm_k_w: crossattn_cache entries carry the one they were made with
 
     # ------------------------------------------------------------------ nn.Module-ish conveniences
@@ -508,21 +510,40 @@ class CausalWanModel:
         a shadow: smooth_k=True (recentring reads the bf16 K cache) and context_parallel=True or a model with context_parallel
         set (ValueError here); a dict with "k" / "v" handed to the model in this mode, a compact dict handed to it outside the
         mode - after disable_fp8_attention() too -, and new scales on a cache that holds rows, whose codes cannot be derived again:
-        reset the cache first (RuntimeError from the forward, before its first launch, the cache indices untouched).  Converting a
-        live bf16 cache into a compact one is not built."""
+        reset the cache first (RuntimeError from the forward, before its first launch, the cache indices untouched).
+        convert_kv_cache_to_fp8() turns a live bf16 cache into a compact one.
+
+        bf16_cache=False, smooth_k="codes" (opt-in; include/rtv_hip_attn_fp8_only_center.h): K smoothing on the compact cache.  A
+        fresh K row is centred in registers by the kernel that writes its codes; fp8_attention_recenter(kv_cache) takes the centres
+        from the codes themselves (the column means of the dequantised keys) and moves the rows already cached to them in place,
+        which costs those rows a second e4m3 rounding - every row written afterwards is rounded once, under the new centre;
+        fp8_attention_set_centers() installs given centres.  The first forward allocates two centre buffers [num_layers, H, 128]
+        and the mean workspace, zero-filled, and nothing later; until the first recentre the mode is the plain compact mode bit
+        for bit.  The compact dicts record the centres their rows were written under ("fp8_center", as "fp8_scales" records the
+        scales): a forward that finds rows under other centres raises RuntimeError before its first launch.  "codes" with
+        bf16_cache=True or under context parallelism is a ValueError; smooth_k=True stays what it was - centres from the bf16
+        cache - and stays a ValueError with bf16_cache=False."""
+        if smooth_k not in (False, True, "codes"):
+            raise ValueError("enable_fp8_attention: smooth_k is False, True or \"codes\"")
+        codes = isinstance(smooth_k, str)
         if smooth_k and context_parallel:
-            raise ValueError("enable_fp8_attention: smooth_k=True is not supported together with context_parallel=True")
-        if not bf16_cache and smooth_k:
-            raise ValueError("enable_fp8_attention: smooth_k=True needs the bf16 KV cache (bf16_cache=False keeps none to take the centres from)")
+            raise ValueError(f"enable_fp8_attention: smooth_k={smooth_k!r} is not supported together with context_parallel=True")
+        if codes and bf16_cache:
+            raise ValueError("enable_fp8_attention: smooth_k=\"codes\" takes the centres from the codes of the compact cache: it needs "
+                             "bf16_cache=False (with the bf16 cache kept, smooth_k=True)")
+        if not bf16_cache and smooth_k and not codes:
+            raise ValueError("enable_fp8_attention: smooth_k=True needs the bf16 KV cache (bf16_cache=False keeps none to take the centres from; "
+                             "smooth_k=\"codes\" takes them from the codes)")
         if not bf16_cache and (context_parallel or self.context_parallel is not None):
             raise ValueError("enable_fp8_attention: bf16_cache=False does not support context parallelism")
         k_scale, v_scale = float(k_scale), float(v_scale)
         for s in (k_scale, v_scale):
             if not (math.isfinite(s) and s > 0):
                 raise ValueError("enable_fp8_attention: scales must be finite and positive")
+        self._fp8_attn_prev = None if self._fp8_attn is None else self._fp8_attn + (self._fp8_attn_smooth,)
         self._fp8_attn_epoch += 1
         self._fp8_attn = (k_scale, v_scale, self._fp8_attn_epoch)
-        self._fp8_attn_smooth = bool(smooth_k)
+        self._fp8_attn_smooth = "codes" if codes else bool(smooth_k)
         self._fp8_attn_cp = bool(context_parallel)
         self._fp8_attn_only = not bf16_cache
         return self
@@ -540,7 +561,7 @@ class CausalWanModel:
         """Back to bf16 self-attention: every launch is the one a model that never enabled the mode issues.  The shadows stay in the
         cache dicts and are refilled from the bf16 cache when the mode comes back."""
         self._fp8_attn_epoch += 1
-        self._fp8_attn = None
+        self._fp8_attn = self._fp8_attn_prev = None
         self._fp8_attn_only = False
         return self
 
@@ -555,9 +576,13 @@ class CausalWanModel:
         """smooth_k=True: set every layer's K centre to the fp32 column means of the physical rows [0, min(local_end_index, rows)) of
         its bf16 K cache (ops.attn_kv_center) and mark the shadows stale: the next forward refills each of them with one centred
         quantiser call, as after a scale change.  Writes the centre buffer in place and allocates nothing.  The window moving on
-        afterwards is not an error - any fixed centre is exact -, only a slightly less good centre."""
+        afterwards is not an error - any fixed centre is exact -, only a slightly less good centre.
+        On the compact dicts of smooth_k="codes" there is no bf16 K cache: the centres come from the codes and the rows move to
+        them in place (_fp8_attention_recenter_codes)."""
         if self._fp8_attn is None or not self._fp8_attn_smooth:
-            raise RuntimeError("fp8_attention_recenter needs enable_fp8_attention(smooth_k=True)")
+            raise RuntimeError("fp8_attention_recenter needs enable_fp8_attention(smooth_k=True) or, on the compact cache, smooth_k=\"codes\"")
+        if self._fp8_attention_only():
+            return self._fp8_attention_recenter_codes(kv_cache)
         if self._fp8_attn_center is None:
             raise RuntimeError("fp8 attention has not run yet: the centres are allocated by the first forward")
         if len(kv_cache) != self.num_layers:
@@ -577,6 +602,154 @@ class CausalWanModel:
 
     def _fp8_attention_only(self):
         return self._fp8_attn is not None and self._fp8_attn_only
+
+    def _fp8_attention_codes(self):
+        """enable_fp8_attention(bf16_cache=False, smooth_k="codes") is on."""
+        return self._fp8_attention_only() and self._fp8_attn_smooth == "codes"
+
+    def _fp8_center_stamp(self):
+        """What a compact dict records as "fp8_center" when rows are written into it: None in the plain compact mode, else this
+        model and the epoch of its centres."""
+        return (id(self), self._fp8_attn_center_epoch) if self._fp8_attention_codes() else None
+
+    def _fp8_alloc_centers(self, H, device, rows=0):
+        """The centre buffers of both smoothing modes, zero-filled, and the mean kernel's workspace for a cache of `rows` rows: made by
+        the first forward (or by fp8_attention_set_centers() in front of it), kept from then on."""
+        if self._fp8_attn_center is None or tuple(self._fp8_attn_center.shape[1:]) != (H, 128) or self._fp8_attn_center.device != device:
+            self._fp8_attn_center = torch.zeros(self.num_layers, H, 128, dtype=torch.float32, device=device)
+            self._fp8_attn_center_new = self._fp8_attn_center_ws = None
+            self._fp8_attn_center_epoch += 1          # (zeros again: rows coded under the centres dropped are under others now)
+        if self._fp8_attn_smooth == "codes" and self._fp8_attn_center_new is None:
+            self._fp8_attn_center_new = torch.zeros_like(self._fp8_attn_center)
+        need = ops.attn_kv_center_workspace_bytes(rows, H) if rows > 0 else 0
+        if rows > 0 and (self._fp8_attn_center_ws is None or self._fp8_attn_center_ws.numel() * 4 < need):      # (a larger cache than any before)
+            self._fp8_attn_center_ws = torch.empty(max(need, 16) // 4, dtype=torch.float32, device=device)
+
+    def _fp8_compact_rows(self, kv_cache, what):
+        """The checks of the two calls that move the rows of compact dicts to other centres -> rows held per layer."""
+        if len(kv_cache) != self.num_layers:
+            raise ValueError(f"{what}: one KV cache entry per layer")
+        stamp, held = self._fp8_center_stamp(), []
+        for c in kv_cache:
+            if "k" in c or "v" in c or "k8" not in c:
+                raise RuntimeError(f"{what}: enable_fp8_attention(bf16_cache=False) needs the compact KV cache of new_fp8_kv_cache()")
+            if tuple(c["k8"].shape[1:]) != (self.num_heads, 128):
+                raise ValueError(f"{what}: the compact cache must hold the model's {self.num_heads} heads")
+            n = min(int(c["local_end_index"]), kv_cache_rows(c))
+            if n > 0 and c.get("fp8_center") != stamp:
+                raise RuntimeError(f"{what}: this e4m3-only KV cache holds rows coded under other K centres than the model's: reset the cache first")
+            held.append(max(n, 0))
+        return held
+
+    def _fp8_attention_recenter_codes(self, kv_cache):
+        """fp8_attention_recenter on compact dicts (smooth_k="codes"): per layer that holds rows, the new centre from the codes
+        (ops.attn_k8_center, into the second buffer), the rows moved to it in place (ops.attn_k8_recenter), the second buffer copied
+        into the first.  Allocates nothing; captured hipGraphs keep their addresses."""
+        if not self._fp8_attention_codes():
+            raise RuntimeError("fp8_attention_recenter on the compact cache needs enable_fp8_attention(bf16_cache=False, smooth_k=\"codes\") "
+                               "(smooth_k=True takes the centres from a bf16 cache)")
+        if self._fp8_attn_center_new is None or self._fp8_attn_center_ws is None:
+            raise RuntimeError("fp8 attention has not run yet: the centres are allocated by the first forward")
+        held = self._fp8_compact_rows(kv_cache, "fp8_attention_recenter")
+        if not any(held):
+            raise RuntimeError("fp8_attention_recenter: the KV cache is empty")
+        for c, n in zip(kv_cache, held):
+            if ops.attn_kv_center_workspace_bytes(n, self.num_heads) > self._fp8_attn_center_ws.numel() * 4:
+                raise RuntimeError("fp8_attention_recenter: this cache is larger than the one the workspace was allocated for")
+        k_scale = self._fp8_attn[0]
+        old, new = self._fp8_attn_center, self._fp8_attn_center_new
+        for l, (c, n) in enumerate(zip(kv_cache, held)):
+            if n > 0:
+                ops.attn_k8_center(c["k8"], (0, n), k_scale=k_scale, c_old=old[l], out=new[l], workspace=self._fp8_attn_center_ws)
+                ops.attn_k8_recenter(c["k8"], old[l], new[l], 0, n, k_scale, amax=self._fp8_attn_amax[l])
+                old[l].copy_(new[l])
+        self._fp8_attn_center_epoch += 1
+        for c in kv_cache:
+            c["fp8_center"] = self._fp8_center_stamp()
+        return self
+
+    def fp8_attention_set_centers(self, centers, kv_cache=None):
+        """Install given K centres, float32 [num_layers, H, 128] - any fixed centre is exact, so centres measured elsewhere (another
+        session, an offline pass over a checkpoint's keys) serve as well as fp8_attention_recenter()'s.  Copies them into the model's
+        buffer in place (allocating it when no forward has yet).  smooth_k=True: the shadows refill at the next forward, as after a
+        recentre.  smooth_k="codes": the rows of the compact dicts `kv_cache` move to the new centres in place
+        (ops.attn_k8_recenter: a second rounding for them); any other compact cache that holds rows is refused by its next forward."""
+        if self._fp8_attn is None or not self._fp8_attn_smooth:
+            raise RuntimeError("fp8_attention_set_centers needs enable_fp8_attention(smooth_k=True) or smooth_k=\"codes\"")
+        if not torch.is_tensor(centers) or centers.dtype != torch.float32 or centers.dim() != 3 or centers.shape[0] != self.num_layers \
+                or centers.shape[2] != 128 or not centers.is_cuda:
+            raise ValueError("fp8_attention_set_centers: centers must be a float32 GPU tensor [num_layers, H, 128]")
+        codes = self._fp8_attention_codes()
+        if self._fp8_attn_center is not None and tuple(centers.shape) != tuple(self._fp8_attn_center.shape):
+            raise ValueError("fp8_attention_set_centers: centers must have the heads the model's centres were allocated for")
+        if codes and centers.shape[1] != self.num_heads:
+            raise ValueError(f"fp8_attention_set_centers: the compact cache holds the model's {self.num_heads} heads")
+        held = self._fp8_compact_rows(kv_cache, "fp8_attention_set_centers") if codes and kv_cache is not None else []
+        if any(held) and self._fp8_attn_amax is None:
+            raise RuntimeError("fp8 attention has not run yet")
+        self._fp8_alloc_centers(centers.shape[1], centers.device)
+        if codes:
+            k_scale = self._fp8_attn[0]
+            old, new = self._fp8_attn_center, self._fp8_attn_center_new
+            new.copy_(centers)
+            for l, n in enumerate(held):
+                if n > 0:
+                    ops.attn_k8_recenter(kv_cache[l]["k8"], old[l], new[l], 0, n, k_scale, amax=self._fp8_attn_amax[l])
+            old.copy_(new)
+        else:
+            self._fp8_attn_center.copy_(centers)
+        self._fp8_attn_center_epoch += 1
+        for c in (kv_cache or []) if codes else []:
+            c["fp8_center"] = self._fp8_center_stamp()
+        return self
+
+    def convert_kv_cache_to_fp8(self, kv_cache):
+        """Turn the bf16 KV cache dicts of a running stream into the compact ones of enable_fp8_attention(bf16_cache=False), in place,
+        with the model already in that mode: "k" / "v" are dropped (the caller frees what else refers to their storage:
+        CausalInferencePipeline.convert_kv_cache_to_fp8 drops its arena), "k8" / "v8t" stay.  A shadow that is current - filled and
+        kept by the shadow mode this enable call replaced, same scales, same centres - is taken over as it is; otherwise one
+        ops.attn_quantize_kv call per layer codes the whole cache, centred under smooth_k="codes".  The indices stay: the next
+        forward goes on where the stream was."""
+        if not self._fp8_attention_only():
+            raise RuntimeError("convert_kv_cache_to_fp8 needs enable_fp8_attention(bf16_cache=False)")
+        if self.context_parallel is not None:
+            raise RuntimeError("enable_fp8_attention(bf16_cache=False) does not support context parallelism")
+        if len(kv_cache) != self.num_layers:
+            raise ValueError("convert_kv_cache_to_fp8: one KV cache entry per layer")
+        for c in kv_cache:
+            if "k" not in c or "v" not in c:
+                raise ValueError("convert_kv_cache_to_fp8: this KV cache is a compact one already")
+            k, v = c["k"], c["v"]
+            if k.shape[0] != 1 or tuple(k.shape[2:]) != (self.num_heads, 128) or k.shape != v.shape or k.shape[1] != kv_cache[0]["k"].shape[1]:
+                raise ValueError(f"convert_kv_cache_to_fp8: batch size 1, the model's {self.num_heads} heads and the same number of rows in every layer")
+        k_scale, v_scale, _ = self._fp8_attn
+        codes = self._fp8_attention_codes()
+        device, rows = kv_cache[0]["k"].device, kv_cache[0]["k"].shape[1]
+        if self._fp8_attn_amax is None:
+            self._fp8_attn_amax = torch.zeros(self.num_layers, 2, dtype=torch.float32, device=device)
+        if codes:
+            self._fp8_alloc_centers(self.num_heads, device, rows)
+        # the "fp8_filled" state _fp8_attention_shadow leaves on a dict whose shadow it has kept current
+        prev = self._fp8_attn_prev
+        current = None
+        if prev is not None and prev[:2] == (k_scale, v_scale) and prev[3] is (True if codes else False):
+            current = prev[:3]
+        for l, c in enumerate(kv_cache):
+            state = (current or ()) + (c["k"].data_ptr(), c["v"].data_ptr())
+            if codes:
+                state += (self._fp8_attn_center_epoch, self._fp8_attn_center.data_ptr())
+            if current is None or "k8" not in c or c.get("fp8_filled") != state or tuple(c["k8"].shape) != (rows, self.num_heads, 128):
+                if "k8" not in c or tuple(c["k8"].shape) != (rows, self.num_heads, 128) or c["k8"].device != device:
+                    c["k8"], c["v8t"] = ops.attn_fp8_shadow(rows, self.num_heads, device)
+                ops.attn_quantize_kv(c["k"][0], c["v"][0], c["k8"], c["v8t"], 0, rows, k_scale, v_scale, amax=self._fp8_attn_amax[l],
+                                     center=self._fp8_attn_center[l] if codes else None)
+        for c in kv_cache:
+            for name in ("k", "v", "fp8_filled", "k8_hp", "v8t_hp"):
+                c.pop(name, None)
+            c["rows"] = rows
+            c["fp8_scales"] = (k_scale, v_scale)
+            c["fp8_center"] = self._fp8_center_stamp()
+        return kv_cache
 
     def _check_kv_cache_kind(self, kv_cache, use_cp):
         """The refusals of the e4m3-only cache that concern the dicts: made by the forward before anything else looks at them."""
@@ -601,6 +774,10 @@ class CausalWanModel:
             if int(c["local_end_index"]) > 0 and c.get("fp8_scales", scales) != scales:
                 raise RuntimeError(f"fp8 attention: this e4m3-only KV cache holds rows quantised with k_scale, v_scale = {c['fp8_scales']}; "
                                    "their codes cannot be derived again for other scales: reset the cache first")
+            if int(c["local_end_index"]) > 0 and c.get("fp8_center") != self._fp8_center_stamp():
+                raise RuntimeError("fp8 attention: this e4m3-only KV cache holds rows coded under other K centres than the model's has now "
+                                   "(fp8_attention_recenter / fp8_attention_set_centers move the rows of the caches they are given): "
+                                   "reset the cache first")
 
     def _fp8_attention_only_shadow(self, kv_cache):
         """_fp8_attention_shadow for the e4m3-only cache (checked by _check_kv_cache_kind): nothing to allocate but the maxima,
@@ -614,6 +791,9 @@ class CausalWanModel:
         pp = ctypes.POINTER(c_vp)
         sh = _Fp8Shadow(ctypes.cast(arrs[0], pp), ctypes.cast(arrs[1], pp), kv_cache_rows(kv_cache[0]), k_scale, v_scale,
                         ctypes.cast(arrs[2], pp))
+        if self._fp8_attention_codes():      # the centre table behind the shadow, as _fp8_attention_shadow leaves it
+            self._fp8_alloc_centers(self.num_heads, kv_cache[0]["k8"].device, kv_cache_rows(kv_cache[0]))
+            arrs.append((c_vp * L)(*[self._fp8_attn_center[l].data_ptr() for l in range(L)]))
         return sh, (sh, arrs)
 
     def _fp8_attention_shadow(self, kv_cache, use_cp):
@@ -1094,12 +1274,13 @@ class CausalWanModel:
 
         if fp8_only:
             fp8_shadow, fp8_keep = self._fp8_attention_only_shadow(kv_cache)
-            commit_indices, scales = commit, self._fp8_attn[:2]
+            commit_indices, scales, center_stamp = commit, self._fp8_attn[:2], self._fp8_center_stamp()
 
             def commit():
                 commit_indices()
                 for c in kv_cache:
                     c["fp8_scales"] = scales      # what the codes in the cache were made with: they cannot be made again
+                    c["fp8_center"] = center_stamp
         else:
             fp8_shadow, fp8_keep = self._fp8_attention_shadow(kv_cache, use_cp)
         # (the unsharded forward with the shadows as an argument; the context-parallel path has phases of its own, run_cp below)
@@ -1113,7 +1294,10 @@ class CausalWanModel:
         if fp8_only:      # the same struct, the entry point that never looks for a bf16 cache; part of the graph key like the scales
             forward = ("rtv_dit_forward_attn_fp8_only", ctypes.byref(fp8_shadow))
             fp8_key = ("only",) + fp8_key
-        if fp8_shadow is not None and self._fp8_attn_smooth:      # the centred entry point: the centre table behind the shadow
+        if fp8_only and self._fp8_attention_codes():      # ... with the K rows centred as they are written
+            forward = ("rtv_dit_forward_attn_fp8_only_centered", ctypes.byref(fp8_shadow), fp8_keep[1][3])
+            fp8_key = ("only", "codes") + fp8_key[1:] + (self._fp8_attn_center.data_ptr(),)
+        if fp8_shadow is not None and self._fp8_attn_smooth and not fp8_only:      # the centred entry point: the centre table behind the shadow
             forward = ("rtv_dit_forward_attn_fp8_centered", ctypes.byref(fp8_shadow), fp8_keep[1][3])
             fp8_key += (self._fp8_attn_center.data_ptr(),)
 

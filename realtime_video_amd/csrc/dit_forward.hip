@@ -18,6 +18,7 @@
 
 #include "../../include/rtv_hip_attn_fp8.h"
 #include "../../include/rtv_hip_attn_fp8_center.h"
+#include "../../include/rtv_hip_attn_fp8_only_center.h"
 #include "../../include/rtv_hip_attn_fp8_cp.h"
 #include "../../include/rtv_hip_attn_fp8_only.h"
 #include "../../include/rtv_hip_mxfp4.h"
@@ -613,9 +614,14 @@ static int write_fp8_only_rows(Ctx& c, int l, bool q) {
   int seg[3][2];
   const int ns = cut_written_rows(st, st->cache_row0 + c.r0, c.rc, seg);
   if (ns < 0) return ns;
-  RTV_TRY(rtv_qk_norm_rope_k8(c.b.qkv, q ? c.b.q : nullptr, sh->k8[l], sh->cache_rows, sh->k_scale, amax, st->cache_row0, c.rc, d, c.H,
-                              c.cfg->eps, lw.norm_q_w, lw.norm_k_w, c.w->rope_cs, c.F, c.gh, c.gw, st->start_frame, c.r0, st->ring_lo,
-                              st->ring_size, st->ring_shift, c.stream));
+  if (c.centers)   // rtv_dit_forward_attn_fp8_only_centered: the K codes of k - centre
+    RTV_TRY(rtv_qk_norm_rope_k8_centered(c.b.qkv, q ? c.b.q : nullptr, sh->k8[l], sh->cache_rows, sh->k_scale, amax, st->cache_row0, c.rc,
+                                         d, c.H, c.cfg->eps, lw.norm_q_w, lw.norm_k_w, c.w->rope_cs, c.F, c.gh, c.gw, st->start_frame,
+                                         c.r0, st->ring_lo, st->ring_size, st->ring_shift, (const float*)c.centers[l], c.stream));
+  else
+    RTV_TRY(rtv_qk_norm_rope_k8(c.b.qkv, q ? c.b.q : nullptr, sh->k8[l], sh->cache_rows, sh->k_scale, amax, st->cache_row0, c.rc, d, c.H,
+                                c.cfg->eps, lw.norm_q_w, lw.norm_k_w, c.w->rope_cs, c.F, c.gh, c.gw, st->start_frame, c.r0, st->ring_lo,
+                                st->ring_size, st->ring_shift, c.stream));
   const uint16_t* v_src = c.b.qkv + 2 * d;
   for (int i = 0; i < ns; ++i) {
     RTV_TRY(rtv_attn_quantize_v_rows(v_src, 3 * d, seg[i][1], c.H, sh->v8t[l], sh->cache_rows, seg[i][0], sh->v_scale, amax, c.stream));
@@ -913,7 +919,8 @@ static int check_fp8_only(const Ctx& c, const rtv_attn_fp8_shadow* sh) {
 }
 
 // The unsharded composition; fp8 != null: self-attention on the e4m3 shadows (rtv_dit_forward_attn_fp8), centers != null: whose K
-// codes are centred (rtv_dit_forward_attn_fp8_centered); fp8_only: whose shadows are the whole cache (rtv_dit_forward_attn_fp8_only).
+// codes are centred (rtv_dit_forward_attn_fp8_centered); fp8_only: whose shadows are the whole cache (rtv_dit_forward_attn_fp8_only;
+// with centers: rtv_dit_forward_attn_fp8_only_centered).
 static int dit_forward(const rtv_dit_config* cfg, const rtv_dit_weights* w, const rtv_dit_step* st, const rtv_attn_fp8_shadow* fp8,
                        void* const* centers, bool fp8_only, void* workspace, size_t workspace_bytes, rtv_stream_t stream) {
   Ctx c;
@@ -926,8 +933,11 @@ static int dit_forward(const rtv_dit_config* cfg, const rtv_dit_weights* w, cons
     if (!fp8->k8 || !fp8->v8t || fp8->cache_rows <= 0)
       return set_error(-1, "dit: fp8 attention needs the k8 / v8t shadow arrays and cache_rows");
     if (centers)
-      for (int l = 0; l < c.L; ++l)
+      for (int l = 0; l < c.L; ++l) {
         if (!centers[l]) return set_error(-1, "dit: fp8 attention: a layer has no K centre");
+        // (the shadow mode's quantiser makes this check layer by layer; the compact cache has nothing to derive its rows from again)
+        if (fp8_only && ((uintptr_t)centers[l] & 15)) return set_error(-1, "dit: fp8 attention: a K centre must be 16-byte aligned");
+      }
     if (fp8_only) RTV_TRY(check_fp8_only(c, fp8));
     c.fp8 = fp8;
     c.centers = centers;
@@ -971,6 +981,14 @@ extern "C" int rtv_dit_forward_attn_fp8_only(const rtv_dit_config* cfg, const rt
                                              rtv_stream_t stream) {
   if (!shadow) return set_error(-1, "dit: fp8 attention needs its shadow (rtv_attn_fp8_shadow)");
   return dit_forward(cfg, w, st, shadow, nullptr, true, workspace, workspace_bytes, stream);
+}
+
+extern "C" int rtv_dit_forward_attn_fp8_only_centered(const rtv_dit_config* cfg, const rtv_dit_weights* w, const rtv_dit_step* st,
+                                                      const rtv_attn_fp8_shadow* shadow, void* const* centers, void* workspace,
+                                                      size_t workspace_bytes, rtv_stream_t stream) {
+  if (!shadow) return set_error(-1, "dit: fp8 attention needs its shadow (rtv_attn_fp8_shadow)");
+  if (!centers) return set_error(-1, "dit: centred fp8 attention needs its table of K centres");
+  return dit_forward(cfg, w, st, shadow, centers, true, workspace, workspace_bytes, stream);
 }
 
 // ---- the sharded phases with the self-attention in fp8 (rtv_hip_attn_fp8_cp.h)

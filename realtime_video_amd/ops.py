@@ -360,6 +360,71 @@ def qk_norm_rope_k8(qkv, k8, cache_row0, num_heads, wq, wk, rope_cs, grid, start
     return q_out
 
 
+def qk_norm_rope_k8_centered(qkv, k8, cache_row0, num_heads, wq, wk, rope_cs, grid, start_frame, center, eps=1e-6, q_out=None,
+                             row_offset=0, ring=(0, 0, 0), k_scale=1.0, amax=None, want_q=True):
+    """qk_norm_rope_k8 with the K codes of k - center, center float32 [H, 128]; amax[0] follows |k - center|
+    (rtv_qk_norm_rope_k8_centered, include/rtv_hip_attn_fp8_only_center.h).  A thin wrapper: the entry point itself refuses what it
+    documents."""
+    _gpu(qkv, k8, wq, wk, rope_cs, q_out, amax, center)
+    M, d3 = qkv.shape
+    d = d3 // 3
+    F, gh, gw = grid
+    if q_out is None and want_q:
+        q_out = torch.empty((M, d), dtype=qkv.dtype, device=qkv.device)
+    _lib.call("rtv_qk_norm_rope_k8_centered", _ptr(qkv), _ptr(q_out) if want_q else None, _ptr(k8), k8.shape[0], float(k_scale), _ptr(amax),
+              int(cache_row0), M, d, int(num_heads), float(eps), _ptr(wq), _ptr(wk), _ptr(rope_cs), int(F), int(gh), int(gw),
+              int(start_frame), int(row_offset), int(ring[0]), int(ring[1]), int(ring[2]), _ptr(center), _stream())
+    return q_out
+
+
+def _check_k8(k8, what):
+    _gpu(k8)
+    if k8.dtype != torch.uint8 or k8.dim() != 3 or k8.shape[2] != 128 or not k8.is_contiguous():
+        raise ValueError(f"{what}: k8 must be a dense uint8 tensor [rows, H, 128]")
+    return k8.shape[0], k8.shape[1]
+
+
+def attn_k8_center(k8, seg0, seg1=(0, 0), k_scale=1.0, c_old=None, out=None, workspace=None):
+    """The centre of a compact cache taken from its codes: c_old + the fp32 column means [H, 128] of code * k_scale over the window
+    seg0 + seg1 (each (first physical row, rows)) of k8 [rows, H, 128] (rtv_attn_k8_center,
+    include/rtv_hip_attn_fp8_only_center.h).  c_old: the centre the codes stand under (None: zeros).  Deterministic: the same input
+    gives the same bits.  workspace as for attn_kv_center."""
+    _gpu(c_old, out, workspace)
+    cache_rows, H = _check_k8(k8, "attn_k8_center")
+    (r0, n0), (r1, n1) = seg0, seg1
+    if c_old is None:
+        c_old = torch.zeros((H, 128), dtype=torch.float32, device=k8.device)
+    if out is None:
+        out = torch.empty((H, 128), dtype=torch.float32, device=k8.device)
+    _check_center(c_old, H, "attn_k8_center")
+    _check_center(out, H, "attn_k8_center")
+    need = attn_kv_center_workspace_bytes(n0 + n1, H)
+    if workspace is None:
+        workspace = torch.empty(max(need, 16) // 4, dtype=torch.float32, device=k8.device)
+    elif workspace.dtype != torch.float32 or not workspace.is_contiguous():
+        raise ValueError("attn_k8_center: workspace must be a dense float32 tensor")
+    _lib.call("rtv_attn_k8_center", _ptr(k8), cache_rows, int(r0), int(n0), int(r1), int(n1), H, float(k_scale), _ptr(c_old), _ptr(out),
+              _ptr(workspace), workspace.numel() * 4, _stream())
+    return out
+
+
+def attn_k8_recenter(k8, c_old, c_new, row0=0, rows=None, k_scale=1.0, amax=None):
+    """Move the rows [row0, row0 + rows) of k8 [rows, H, 128] from the centre c_old to the centre c_new (float32 [H, 128]), in place:
+    code' = e4m3((code * k_scale + (c_old - c_new)) / k_scale) (rtv_attn_k8_recenter, whose header states the arithmetic).  amax:
+    optional float32 [2], [0] is raised to the largest |code * k_scale + (c_old - c_new)|."""
+    _gpu(c_old, c_new, amax)
+    cache_rows, H = _check_k8(k8, "attn_k8_recenter")
+    _check_center(c_old, H, "attn_k8_recenter")
+    _check_center(c_new, H, "attn_k8_recenter")
+    if amax is not None and (amax.dtype != torch.float32 or amax.numel() != 2 or not amax.is_contiguous()):
+        raise ValueError("attn_k8_recenter: amax must be a dense float32 tensor of 2 elements")
+    if rows is None:
+        rows = cache_rows - row0
+    _lib.call("rtv_attn_k8_recenter", _ptr(k8), cache_rows, int(row0), int(rows), H, float(k_scale), _ptr(c_old), _ptr(c_new), _ptr(amax),
+              _stream())
+    return k8
+
+
 def attn_quantize_v_rows(v_src, v8t, cache_rows, dst_row0, v_scale=1.0, amax=None):
     """Quantise the bf16 rows v_src [rows, H, 128] (any row stride: the V third of a projection buffer is fine) into the physical rows
     [dst_row0, dst_row0 + rows) of v8t (rtv_attn_quantize_v_rows, include/rtv_hip_attn_fp8_only.h).  amax: optional float32 [2], [1]

@@ -45,6 +45,15 @@ class CausalInferencePipeline:
             self.generator.model.num_frame_per_block = self.num_frame_per_block
 
     # ------------------------------------------------------------------ KV-cache manager
+    def convert_kv_cache_to_fp8(self):
+        """CausalWanModel.convert_kv_cache_to_fp8 on kv_cache1, with the model already in enable_fp8_attention(bf16_cache=False): the
+        dicts of a running stream become compact ones in place and the bf16 arena is freed; the stream goes on at its indices."""
+        if not self.kv_cache1:
+            raise RuntimeError("convert_kv_cache_to_fp8: no KV cache has been allocated yet")
+        self.generator.model.convert_kv_cache_to_fp8(self.kv_cache1)
+        self._kv_arena = None
+        return self.kv_cache1
+
     def _initialize_kv_cache(self, batch_size, dtype, device):
         """causal_inference.py:279-314."""
         kv_cache_size = self.local_attn_size * self.frame_seq_length if self.local_attn_size != -1 else 32760
