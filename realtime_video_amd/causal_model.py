@@ -13,13 +13,13 @@ Surface used by the reference's callers and reproduced here:
 import collections
 import ctypes
 import functools
-import math
 import os
 import types
 
 import torch
 
 from . import _lib, lora, ops, precision_policy
+from .fp8_attention import Fp8Attention, kv_cache_rows      # noqa: F401  (kv_cache_rows stays importable from here)
 from .rope import rope_cos_sin_table
 
 c_vp = ctypes.c_void_p
@@ -31,7 +31,6 @@ _Cfg = _lib.STRUCTS["rtv_dit_config"]
 _LayerW = _lib.STRUCTS["rtv_dit_layer_weights"]
 _Weights = _lib.STRUCTS["rtv_dit_weights"]
 _Step = _lib.STRUCTS["rtv_dit_step"]
-_Fp8Shadow = _lib.ATTN_FP8_STRUCTS["rtv_attn_fp8_shadow"]
 _LAYER_FIELDS = tuple(n for n, _ in _LayerW._fields_)
 _TOP_FIELDS = tuple(n for n, t in _Weights._fields_ if t is c_vp)      # the device tensors; `layers` / `fp8_scales` are host arrays
 
@@ -92,12 +91,6 @@ class _SelfAttnHandle:
         self.fused_projections = True
 
 
-def kv_cache_rows(cache):
-    """Rows of one layer's KV cache dict, of either kind: the bf16 cache {"k", "v", ...} (with or without its e4m3 shadow) or the
-    compact e4m3-only one {"k8", "v8t", "rows", ...} of enable_fp8_attention(bf16_cache=False)."""
-    return cache["k"].shape[1] if "k" in cache else int(cache["rows"])
-
-
 def cache_row_map(cache, sink_tokens=None):
     """Physical cache row of every LIVE logical row [0, local_end_index) of one kv_cache entry.  The rolling cache is kept as a
     ring (no eviction copies): logical row r >= ring_lo lives at ring_lo + (r - ring_lo + ring_start) % ring_size.  For
@@ -152,17 +145,7 @@ class CausalWanModel:
         self._lora = {}               # name -> {"scale": float, "targets": {target: lora.Target with A / B on the device}}, in load order
         self._lora_base = {}          # _tensors key -> bf16 copy of the tensor as loaded; kept outside _tensors / parameters()
         self._lora_dora_ws = None     # the DoRA merge's row-norm partials, sized once for the largest Linear
-        self._fp8_attn = None         # (k_scale, v_scale, epoch) while enable_fp8_attention() is on
-        self._fp8_attn_epoch = 0      # bumps at every enable / disable: a shadow filled before it is refilled from the bf16 cache
-        self._fp8_attn_amax = None    # float32 [num_layers, 2], allocated once
-        self._fp8_attn_cp = False           # enable_fp8_attention(context_parallel=True): sharded forwards run in fp8 instead of raising
-        self._fp8_attn_only = False         # enable_fp8_attention(bf16_cache=False): the e4m3 arrays are the whole KV cache
-        self._fp8_attn_smooth = False       # enable_fp8_attention(smooth_k=True): the K codes of the shadows are those of k - centre
-        self._fp8_attn_center = None        # float32 [num_layers, H, 128], zero-filled, allocated once; fp8_attention_recenter() writes it
-        self._fp8_attn_center_ws = None     # workspace of the mean kernel, allocated with the centre
-        self._fp8_attn_center_epoch = 0     # bumps at every recentre: part of a shadow's "fp8_filled" state, like the scales
-        self._fp8_attn_center_new = None    # smooth_k="codes": the second centre buffer a recentre computes into, allocated with the first
-        self._fp8_attn_prev = None          # the (k_scale, v_scale, epoch, smooth_k) an enable call replaced: convert_kv_cache_to_fp8
+        self._fp8_attention = Fp8Attention(self)      # everything enable_fp8_attention() keeps (fp8_attention.py)
         self.lora_version = 0         # bumps when a merge changes ck / cv / co (weight or bias) or cnorm_k_w: crossattn_cache entries carry the one they were made with
 
     # ------------------------------------------------------------------ nn.Module-ish conveniences
@@ -523,54 +506,24 @@ class CausalWanModel:
         scales): a forward that finds rows under other centres raises RuntimeError before its first launch.  "codes" with
         bf16_cache=True or under context parallelism is a ValueError; smooth_k=True stays what it was - centres from the bf16
         cache - and stays a ValueError with bf16_cache=False."""
-        if smooth_k not in (False, True, "codes"):
-            raise ValueError("enable_fp8_attention: smooth_k is False, True or \"codes\"")
-        codes = isinstance(smooth_k, str)
-        if smooth_k and context_parallel:
-            raise ValueError(f"enable_fp8_attention: smooth_k={smooth_k!r} is not supported together with context_parallel=True")
-        if codes and bf16_cache:
-            raise ValueError("enable_fp8_attention: smooth_k=\"codes\" takes the centres from the codes of the compact cache: it needs "
-                             "bf16_cache=False (with the bf16 cache kept, smooth_k=True)")
-        if not bf16_cache and smooth_k and not codes:
-            raise ValueError("enable_fp8_attention: smooth_k=True needs the bf16 KV cache (bf16_cache=False keeps none to take the centres from; "
-                             "smooth_k=\"codes\" takes them from the codes)")
-        if not bf16_cache and (context_parallel or self.context_parallel is not None):
-            raise ValueError("enable_fp8_attention: bf16_cache=False does not support context parallelism")
-        k_scale, v_scale = float(k_scale), float(v_scale)
-        for s in (k_scale, v_scale):
-            if not (math.isfinite(s) and s > 0):
-                raise ValueError("enable_fp8_attention: scales must be finite and positive")
-        self._fp8_attn_prev = None if self._fp8_attn is None else self._fp8_attn + (self._fp8_attn_smooth,)
-        self._fp8_attn_epoch += 1
-        self._fp8_attn = (k_scale, v_scale, self._fp8_attn_epoch)
-        self._fp8_attn_smooth = "codes" if codes else bool(smooth_k)
-        self._fp8_attn_cp = bool(context_parallel)
-        self._fp8_attn_only = not bf16_cache
+        self._fp8_attention.enable(k_scale, v_scale, smooth_k, context_parallel, bf16_cache)
         return self
 
     def new_fp8_kv_cache(self, rows, device):
         """The KV cache of enable_fp8_attention(bf16_cache=False): per layer the two e4m3 arrays of include/rtv_hip_attn_fp8.h
         (zero-filled; rows outside the attention window are masked by the kernel) and the indices - no "k" / "v" entries."""
-        caches = []
-        for _ in range(self.num_layers):
-            k8, v8t = ops.attn_fp8_shadow(int(rows), self.num_heads, device)
-            caches.append({"k8": k8, "v8t": v8t, "rows": int(rows), "global_end_index": 0, "local_end_index": 0})
-        return caches
+        return self._fp8_attention.new_kv_cache(rows, device)
 
     def disable_fp8_attention(self):
         """Back to bf16 self-attention: every launch is the one a model that never enabled the mode issues.  The shadows stay in the
         cache dicts and are refilled from the bf16 cache when the mode comes back."""
-        self._fp8_attn_epoch += 1
-        self._fp8_attn = self._fp8_attn_prev = None
-        self._fp8_attn_only = False
+        self._fp8_attention.disable()
         return self
 
     def fp8_attention_amax(self):
         """float32 [num_layers, 2]: the largest |k| and |v| (raw bf16 values) quantised into a shadow since the mode first ran.
         With smooth_k=True the K column follows |k - c| under the centre of the time - the value that saturates at 448 * k_scale."""
-        if self._fp8_attn_amax is None:
-            raise RuntimeError("fp8 attention has not run yet")
-        return self._fp8_attn_amax
+        return self._fp8_attention.amax_table()
 
     def fp8_attention_recenter(self, kv_cache):
         """smooth_k=True: set every layer's K centre to the fp32 column means of the physical rows [0, min(local_end_index, rows)) of
@@ -578,94 +531,8 @@ class CausalWanModel:
         quantiser call, as after a scale change.  Writes the centre buffer in place and allocates nothing.  The window moving on
         afterwards is not an error - any fixed centre is exact -, only a slightly less good centre.
         On the compact dicts of smooth_k="codes" there is no bf16 K cache: the centres come from the codes and the rows move to
-        them in place (_fp8_attention_recenter_codes)."""
-        if self._fp8_attn is None or not self._fp8_attn_smooth:
-            raise RuntimeError("fp8_attention_recenter needs enable_fp8_attention(smooth_k=True) or, on the compact cache, smooth_k=\"codes\"")
-        if self._fp8_attention_only():
-            return self._fp8_attention_recenter_codes(kv_cache)
-        if self._fp8_attn_center is None:
-            raise RuntimeError("fp8 attention has not run yet: the centres are allocated by the first forward")
-        if len(kv_cache) != self.num_layers:
-            raise ValueError("fp8_attention_recenter: one KV cache entry per layer")
-        for l, c in enumerate(kv_cache):
-            k = c["k"]
-            if k.shape[0] != 1 or tuple(k.shape[2:]) != tuple(self._fp8_attn_center.shape[1:]):
-                raise ValueError("fp8_attention_recenter: batch size 1 and the heads the centres were allocated for")
-            n = min(int(c["local_end_index"]), k.shape[1])
-            if n <= 0:
-                raise RuntimeError("fp8_attention_recenter: the KV cache is empty")
-            if ops.attn_kv_center_workspace_bytes(n, k.shape[2]) > self._fp8_attn_center_ws.numel() * 4:
-                raise RuntimeError("fp8_attention_recenter: this cache is larger than the one the workspace was allocated for")
-            ops.attn_kv_center(k[0], (0, n), out=self._fp8_attn_center[l], workspace=self._fp8_attn_center_ws)
-        self._fp8_attn_center_epoch += 1
-        return self
-
-    def _fp8_attention_only(self):
-        return self._fp8_attn is not None and self._fp8_attn_only
-
-    def _fp8_attention_codes(self):
-        """enable_fp8_attention(bf16_cache=False, smooth_k="codes") is on."""
-        return self._fp8_attention_only() and self._fp8_attn_smooth == "codes"
-
-    def _fp8_center_stamp(self):
-        """What a compact dict records as "fp8_center" when rows are written into it: None in the plain compact mode, else this
-        model and the epoch of its centres."""
-        return (id(self), self._fp8_attn_center_epoch) if self._fp8_attention_codes() else None
-
-    def _fp8_alloc_centers(self, H, device, rows=0):
-        """The centre buffers of both smoothing modes, zero-filled, and the mean kernel's workspace for a cache of `rows` rows: made by
-        the first forward (or by fp8_attention_set_centers() in front of it), kept from then on."""
-        if self._fp8_attn_center is None or tuple(self._fp8_attn_center.shape[1:]) != (H, 128) or self._fp8_attn_center.device != device:
-            self._fp8_attn_center = torch.zeros(self.num_layers, H, 128, dtype=torch.float32, device=device)
-            self._fp8_attn_center_new = self._fp8_attn_center_ws = None
-            self._fp8_attn_center_epoch += 1          # (zeros again: rows coded under the centres dropped are under others now)
-        if self._fp8_attn_smooth == "codes" and self._fp8_attn_center_new is None:
-            self._fp8_attn_center_new = torch.zeros_like(self._fp8_attn_center)
-        need = ops.attn_kv_center_workspace_bytes(rows, H) if rows > 0 else 0
-        if rows > 0 and (self._fp8_attn_center_ws is None or self._fp8_attn_center_ws.numel() * 4 < need):      # (a larger cache than any before)
-            self._fp8_attn_center_ws = torch.empty(max(need, 16) // 4, dtype=torch.float32, device=device)
-
-    def _fp8_compact_rows(self, kv_cache, what):
-        """The checks of the two calls that move the rows of compact dicts to other centres -> rows held per layer."""
-        if len(kv_cache) != self.num_layers:
-            raise ValueError(f"{what}: one KV cache entry per layer")
-        stamp, held = self._fp8_center_stamp(), []
-        for c in kv_cache:
-            if "k" in c or "v" in c or "k8" not in c:
-                raise RuntimeError(f"{what}: enable_fp8_attention(bf16_cache=False) needs the compact KV cache of new_fp8_kv_cache()")
-            if tuple(c["k8"].shape[1:]) != (self.num_heads, 128):
-                raise ValueError(f"{what}: the compact cache must hold the model's {self.num_heads} heads")
-            n = min(int(c["local_end_index"]), kv_cache_rows(c))
-            if n > 0 and c.get("fp8_center") != stamp:
-                raise RuntimeError(f"{what}: this e4m3-only KV cache holds rows coded under other K centres than the model's: reset the cache first")
-            held.append(max(n, 0))
-        return held
-
-    def _fp8_attention_recenter_codes(self, kv_cache):
-        """fp8_attention_recenter on compact dicts (smooth_k="codes"): per layer that holds rows, the new centre from the codes
-        (ops.attn_k8_center, into the second buffer), the rows moved to it in place (ops.attn_k8_recenter), the second buffer copied
-        into the first.  Allocates nothing; captured hipGraphs keep their addresses."""
-        if not self._fp8_attention_codes():
-            raise RuntimeError("fp8_attention_recenter on the compact cache needs enable_fp8_attention(bf16_cache=False, smooth_k=\"codes\") "
-                               "(smooth_k=True takes the centres from a bf16 cache)")
-        if self._fp8_attn_center_new is None or self._fp8_attn_center_ws is None:
-            raise RuntimeError("fp8 attention has not run yet: the centres are allocated by the first forward")
-        held = self._fp8_compact_rows(kv_cache, "fp8_attention_recenter")
-        if not any(held):
-            raise RuntimeError("fp8_attention_recenter: the KV cache is empty")
-        for c, n in zip(kv_cache, held):
-            if ops.attn_kv_center_workspace_bytes(n, self.num_heads) > self._fp8_attn_center_ws.numel() * 4:
-                raise RuntimeError("fp8_attention_recenter: this cache is larger than the one the workspace was allocated for")
-        k_scale = self._fp8_attn[0]
-        old, new = self._fp8_attn_center, self._fp8_attn_center_new
-        for l, (c, n) in enumerate(zip(kv_cache, held)):
-            if n > 0:
-                ops.attn_k8_center(c["k8"], (0, n), k_scale=k_scale, c_old=old[l], out=new[l], workspace=self._fp8_attn_center_ws)
-                ops.attn_k8_recenter(c["k8"], old[l], new[l], 0, n, k_scale, amax=self._fp8_attn_amax[l])
-                old[l].copy_(new[l])
-        self._fp8_attn_center_epoch += 1
-        for c in kv_cache:
-            c["fp8_center"] = self._fp8_center_stamp()
+        them in place."""
+        self._fp8_attention.recenter(kv_cache)
         return self
 
     def fp8_attention_set_centers(self, centers, kv_cache=None):
@@ -674,33 +541,7 @@ class CausalWanModel:
         buffer in place (allocating it when no forward has yet).  smooth_k=True: the shadows refill at the next forward, as after a
         recentre.  smooth_k="codes": the rows of the compact dicts `kv_cache` move to the new centres in place
         (ops.attn_k8_recenter: a second rounding for them); any other compact cache that holds rows is refused by its next forward."""
-        if self._fp8_attn is None or not self._fp8_attn_smooth:
-            raise RuntimeError("fp8_attention_set_centers needs enable_fp8_attention(smooth_k=True) or smooth_k=\"codes\"")
-        if not torch.is_tensor(centers) or centers.dtype != torch.float32 or centers.dim() != 3 or centers.shape[0] != self.num_layers \
-                or centers.shape[2] != 128 or not centers.is_cuda:
-            raise ValueError("fp8_attention_set_centers: centers must be a float32 GPU tensor [num_layers, H, 128]")
-        codes = self._fp8_attention_codes()
-        if self._fp8_attn_center is not None and tuple(centers.shape) != tuple(self._fp8_attn_center.shape):
-            raise ValueError("fp8_attention_set_centers: centers must have the heads the model's centres were allocated for")
-        if codes and centers.shape[1] != self.num_heads:
-            raise ValueError(f"fp8_attention_set_centers: the compact cache holds the model's {self.num_heads} heads")
-        held = self._fp8_compact_rows(kv_cache, "fp8_attention_set_centers") if codes and kv_cache is not None else []
-        if any(held) and self._fp8_attn_amax is None:
-            raise RuntimeError("fp8 attention has not run yet")
-        self._fp8_alloc_centers(centers.shape[1], centers.device)
-        if codes:
-            k_scale = self._fp8_attn[0]
-            old, new = self._fp8_attn_center, self._fp8_attn_center_new
-            new.copy_(centers)
-            for l, n in enumerate(held):
-                if n > 0:
-                    ops.attn_k8_recenter(kv_cache[l]["k8"], old[l], new[l], 0, n, k_scale, amax=self._fp8_attn_amax[l])
-            old.copy_(new)
-        else:
-            self._fp8_attn_center.copy_(centers)
-        self._fp8_attn_center_epoch += 1
-        for c in (kv_cache or []) if codes else []:
-            c["fp8_center"] = self._fp8_center_stamp()
+        self._fp8_attention.set_centers(centers, kv_cache)
         return self
 
     def convert_kv_cache_to_fp8(self, kv_cache):
@@ -710,173 +551,7 @@ class CausalWanModel:
         kept by the shadow mode this enable call replaced, same scales, same centres - is taken over as it is; otherwise one
         ops.attn_quantize_kv call per layer codes the whole cache, centred under smooth_k="codes".  The indices stay: the next
         forward goes on where the stream was."""
-        if not self._fp8_attention_only():
-            raise RuntimeError("convert_kv_cache_to_fp8 needs enable_fp8_attention(bf16_cache=False)")
-        if self.context_parallel is not None:
-            raise RuntimeError("enable_fp8_attention(bf16_cache=False) does not support context parallelism")
-        if len(kv_cache) != self.num_layers:
-            raise ValueError("convert_kv_cache_to_fp8: one KV cache entry per layer")
-        for c in kv_cache:
-            if "k" not in c or "v" not in c:
-                raise ValueError("convert_kv_cache_to_fp8: this KV cache is a compact one already")
-            k, v = c["k"], c["v"]
-            if k.shape[0] != 1 or tuple(k.shape[2:]) != (self.num_heads, 128) or k.shape != v.shape or k.shape[1] != kv_cache[0]["k"].shape[1]:
-                raise ValueError(f"convert_kv_cache_to_fp8: batch size 1, the model's {self.num_heads} heads and the same number of rows in every layer")
-        k_scale, v_scale, _ = self._fp8_attn
-        codes = self._fp8_attention_codes()
-        device, rows = kv_cache[0]["k"].device, kv_cache[0]["k"].shape[1]
-        if self._fp8_attn_amax is None:
-            self._fp8_attn_amax = torch.zeros(self.num_layers, 2, dtype=torch.float32, device=device)
-        if codes:
-            self._fp8_alloc_centers(self.num_heads, device, rows)
-        # the "fp8_filled" state _fp8_attention_shadow leaves on a dict whose shadow it has kept current
-        prev = self._fp8_attn_prev
-        current = None
-        if prev is not None and prev[:2] == (k_scale, v_scale) and prev[3] is (True if codes else False):
-            current = prev[:3]
-        for l, c in enumerate(kv_cache):
-            state = (current or ()) + (c["k"].data_ptr(), c["v"].data_ptr())
-            if codes:
-                state += (self._fp8_attn_center_epoch, self._fp8_attn_center.data_ptr())
-            if current is None or "k8" not in c or c.get("fp8_filled") != state or tuple(c["k8"].shape) != (rows, self.num_heads, 128):
-                if "k8" not in c or tuple(c["k8"].shape) != (rows, self.num_heads, 128) or c["k8"].device != device:
-                    c["k8"], c["v8t"] = ops.attn_fp8_shadow(rows, self.num_heads, device)
-                ops.attn_quantize_kv(c["k"][0], c["v"][0], c["k8"], c["v8t"], 0, rows, k_scale, v_scale, amax=self._fp8_attn_amax[l],
-                                     center=self._fp8_attn_center[l] if codes else None)
-        for c in kv_cache:
-            for name in ("k", "v", "fp8_filled", "k8_hp", "v8t_hp"):
-                c.pop(name, None)
-            c["rows"] = rows
-            c["fp8_scales"] = (k_scale, v_scale)
-            c["fp8_center"] = self._fp8_center_stamp()
-        return kv_cache
-
-    def _check_kv_cache_kind(self, kv_cache, use_cp):
-        """The refusals of the e4m3-only cache that concern the dicts: made by the forward before anything else looks at them."""
-        compact = ["k" not in c and "v" not in c for c in kv_cache]
-        if not self._fp8_attention_only():
-            if any(compact):
-                raise RuntimeError("this KV cache is an e4m3-only one (new_fp8_kv_cache): it needs enable_fp8_attention(bf16_cache=False)")
-            return
-        if use_cp or self.context_parallel is not None:
-            raise RuntimeError("enable_fp8_attention(bf16_cache=False) does not support context parallelism")
-        if not all(compact):
-            raise RuntimeError("enable_fp8_attention(bf16_cache=False) needs the compact KV cache of new_fp8_kv_cache(): "
-                               "this one has \"k\" / \"v\" entries")
-        rows, scales = kv_cache_rows(kv_cache[0]), self._fp8_attn[:2]
-        for c in kv_cache:
-            if kv_cache_rows(c) != rows or tuple(c["k8"].shape) != (rows, self.num_heads, 128) \
-                    or tuple(c["v8t"].shape) != ((rows + 63) // 64, self.num_heads, 128, 64) \
-                    or not (c["k8"].is_cuda and c["k8"].is_contiguous() and c["v8t"].is_contiguous()) \
-                    or c["k8"].dtype != torch.uint8 or c["v8t"].dtype != torch.uint8 or c["v8t"].device != c["k8"].device:
-                raise ValueError("fp8 attention: every layer's compact KV cache must be the k8 / v8t pair of new_fp8_kv_cache(rows) "
-                                 "with the same number of rows")
-            if int(c["local_end_index"]) > 0 and c.get("fp8_scales", scales) != scales:
-                raise RuntimeError(f"fp8 attention: this e4m3-only KV cache holds rows quantised with k_scale, v_scale = {c['fp8_scales']}; "
-                                   "their codes cannot be derived again for other scales: reset the cache first")
-            if int(c["local_end_index"]) > 0 and c.get("fp8_center") != self._fp8_center_stamp():
-                raise RuntimeError("fp8 attention: this e4m3-only KV cache holds rows coded under other K centres than the model's has now "
-                                   "(fp8_attention_recenter / fp8_attention_set_centers move the rows of the caches they are given): "
-                                   "reset the cache first")
-
-    def _fp8_attention_only_shadow(self, kv_cache):
-        """_fp8_attention_shadow for the e4m3-only cache (checked by _check_kv_cache_kind): nothing to allocate but the maxima,
-        nothing to fill."""
-        k_scale, v_scale, _ = self._fp8_attn
-        L = self.num_layers
-        if self._fp8_attn_amax is None:
-            self._fp8_attn_amax = torch.zeros(L, 2, dtype=torch.float32, device=kv_cache[0]["k8"].device)
-        arrs = [(c_vp * L)(*[t_.data_ptr() for t_ in ts]) for ts in ([c["k8"] for c in kv_cache], [c["v8t"] for c in kv_cache],
-                                                                     [self._fp8_attn_amax[l] for l in range(L)])]
-        pp = ctypes.POINTER(c_vp)
-        sh = _Fp8Shadow(ctypes.cast(arrs[0], pp), ctypes.cast(arrs[1], pp), kv_cache_rows(kv_cache[0]), k_scale, v_scale,
-                        ctypes.cast(arrs[2], pp))
-        if self._fp8_attention_codes():      # the centre table behind the shadow, as _fp8_attention_shadow leaves it
-            self._fp8_alloc_centers(self.num_heads, kv_cache[0]["k8"].device, kv_cache_rows(kv_cache[0]))
-            arrs.append((c_vp * L)(*[self._fp8_attn_center[l].data_ptr() for l in range(L)]))
-        return sh, (sh, arrs)
-
-    def _fp8_attention_shadow(self, kv_cache, use_cp):
-        """The rtv_attn_fp8_shadow of this forward (None: bf16 attention) and what must stay alive with it.  Under the head exchange
-        of a context-parallel forward: a list, one shadow per local rank."""
-        if self._fp8_attn is None:
-            return None, None
-        if use_cp and not self._fp8_attn_cp:
-            raise RuntimeError("fp8 attention does not support context parallelism (sharded calls and the KV split have no fp8 kernels)")
-        k_scale, v_scale, epoch = self._fp8_attn
-        L = self.num_layers
-        if self._fp8_attn_amax is None:
-            self._fp8_attn_amax = torch.zeros(L, 2, dtype=torch.float32, device=kv_cache[0]["k"].device)
-        rows = kv_cache_rows(kv_cache[0])
-        if use_cp and self.context_parallel.head_exchange(self.num_heads):
-            return self._fp8_attention_shadow_heads(kv_cache, rows)
-        smooth = self._fp8_attn_smooth
-        if smooth:
-            k0 = kv_cache[0]["k"]
-            need = ops.attn_kv_center_workspace_bytes(rows, k0.shape[2])
-            if self._fp8_attn_center is None or tuple(self._fp8_attn_center.shape[1:]) != tuple(k0.shape[2:]) \
-                    or self._fp8_attn_center.device != k0.device:
-                self._fp8_attn_center = torch.zeros(L, k0.shape[2], 128, dtype=torch.float32, device=k0.device)
-                self._fp8_attn_center_ws = None
-            if self._fp8_attn_center_ws is None or self._fp8_attn_center_ws.numel() * 4 < need:      # (a larger cache than any before)
-                self._fp8_attn_center_ws = torch.empty(max(need, 16) // 4, dtype=torch.float32, device=k0.device)
-        for l, c in enumerate(kv_cache):
-            if c["k"].shape[0] != 1 or c["k"].shape[1] != rows:
-                raise ValueError("fp8 attention: batch size 1 and the same number of rows in every layer's KV cache")
-            H = c["k"].shape[2]
-            if smooth and H != self._fp8_attn_center.shape[1]:
-                raise ValueError("fp8 attention: smooth_k needs the same number of heads in every layer's KV cache")
-            if "k8" not in c or tuple(c["k8"].shape[:2]) != (rows, H) or c["k8"].device != c["k"].device:
-                c["k8"], c["v8t"] = ops.attn_fp8_shadow(rows, H, c["k"].device)
-                c["fp8_filled"] = None
-            state = (k_scale, v_scale, epoch, c["k"].data_ptr(), c["v"].data_ptr())
-            if smooth:
-                state += (self._fp8_attn_center_epoch, self._fp8_attn_center.data_ptr())
-            if c.get("fp8_filled") != state:
-                ops.attn_quantize_kv(c["k"][0], c["v"][0], c["k8"], c["v8t"], 0, rows, k_scale, v_scale, amax=self._fp8_attn_amax[l],
-                                     center=self._fp8_attn_center[l] if smooth else None)
-                c["fp8_filled"] = state
-        arrs = [(c_vp * L)(*[t_.data_ptr() for t_ in ts]) for ts in ([c["k8"] for c in kv_cache], [c["v8t"] for c in kv_cache],
-                                                                     [self._fp8_attn_amax[l] for l in range(L)])]
-        pp = ctypes.POINTER(c_vp)
-        sh = _Fp8Shadow(ctypes.cast(arrs[0], pp), ctypes.cast(arrs[1], pp), rows, k_scale, v_scale, ctypes.cast(arrs[2], pp))
-        if smooth:
-            arrs.append((c_vp * L)(*[self._fp8_attn_center[l].data_ptr() for l in range(L)]))
-        return sh, (sh, arrs)
-
-    def _fp8_attention_shadow_heads(self, kv_cache, rows):
-        """Head exchange: per layer and local rank one dense shadow of the num_heads / world heads the rank owns ("k8_hp" / "v8t_hp" of
-        the cache dict, allocated once), filled from the rank's head slice of the bf16 cache.  -> ([shadow per local rank], keep)."""
-        cp = self.context_parallel
-        k_scale, v_scale, epoch = self._fp8_attn
-        L, H, W = self.num_layers, self.num_heads, cp.world
-        hn = H // W
-        ranks = list(cp.local_ranks())
-        for l, c in enumerate(kv_cache):
-            Hc = c["k"].shape[2]
-            if c["k"].shape[0] != 1 or c["k"].shape[1] != rows or Hc not in (hn, H):
-                raise ValueError(f"fp8 attention: batch size 1, the same number of rows in every layer's KV cache, and {hn} (this rank's) or {H} heads")
-            hp = c.get("k8_hp")
-            if hp is None or len(hp) != len(ranks) or tuple(hp[0].shape[:2]) != (rows, hn) or hp[0].device != c["k"].device:
-                pairs = [ops.attn_fp8_shadow(rows, hn, c["k"].device) for _ in ranks]
-                c["k8_hp"], c["v8t_hp"] = [p[0] for p in pairs], [p[1] for p in pairs]
-                c["fp8_filled"] = None
-            state = (k_scale, v_scale, epoch, c["k"].data_ptr(), c["v"].data_ptr(), "heads", tuple(ranks), Hc)
-            if c.get("fp8_filled") != state:
-                for i, r in enumerate(ranks):
-                    h0 = 0 if Hc == hn else r * hn
-                    ops.attn_quantize_kv(c["k"][0][:, h0:h0 + hn], c["v"][0][:, h0:h0 + hn], c["k8_hp"][i], c["v8t_hp"][i], 0, rows, k_scale,
-                                         v_scale, amax=self._fp8_attn_amax[l])
-                c["fp8_filled"] = state
-        pp = ctypes.POINTER(c_vp)
-        amax = (c_vp * L)(*[self._fp8_attn_amax[l].data_ptr() for l in range(L)])
-        shs, arrs = [], [amax]
-        for i in range(len(ranks)):
-            a8 = (c_vp * L)(*[c["k8_hp"][i].data_ptr() for c in kv_cache])
-            av = (c_vp * L)(*[c["v8t_hp"][i].data_ptr() for c in kv_cache])
-            arrs += [a8, av]
-            shs.append(_Fp8Shadow(ctypes.cast(a8, pp), ctypes.cast(av, pp), rows, k_scale, v_scale, ctypes.cast(amax, pp)))
-        return shs, (shs, arrs)
+        return self._fp8_attention.convert_kv_cache(kv_cache)
 
     @staticmethod
     def _quantize_fp8(w):
@@ -1260,8 +935,9 @@ class CausalWanModel:
             for c in crossattn_cache:
                 if "vo" not in c:
                     c["vo"] = torch.zeros(self.dim * _cross_fold_max_cols(self.num_heads), dtype=torch.bfloat16, device=u.device)
-        self._check_kv_cache_kind(kv_cache, use_cp)
-        fp8_only = self._fp8_attention_only()      # the dicts hold k8 / v8t and nothing in bf16 (include/rtv_hip_attn_fp8_only.h)
+        fa = self._fp8_attention
+        fa.check_kv_cache_kind(kv_cache, use_cp)
+        fp8_only = fa.only()      # the dicts hold k8 / v8t and nothing in bf16 (include/rtv_hip_attn_fp8_only.h)
         row0, lo, hi, start_frame, causal_block, (ring_lo, ring_size, ring_shift), commit = \
             self._cache_window(kv_cache, M, current_start, fs, ring=not use_cp)
         L = self.num_layers
@@ -1272,34 +948,16 @@ class CausalWanModel:
                     raise ValueError("KV cache tensors must be [B, kv_size, H, 128] views with dense [H, 128] rows "
                                      "and one common row stride")
 
-        if fp8_only:
-            fp8_shadow, fp8_keep = self._fp8_attention_only_shadow(kv_cache)
-            commit_indices, scales, center_stamp = commit, self._fp8_attn[:2], self._fp8_center_stamp()
+        # the shadows, the unsharded forward with them as an argument (the context-parallel path has phases of its own, run_cp below)
+        # and the fp8 part of the graph key
+        plan = fa.plan(kv_cache, use_cp)
+        fp8_shadow, fp8_keep, forward, fp8_key = plan.shadow, plan.keep, plan.forward, plan.key
+        if plan.commit is not None:      # the compact cache records what its rows were coded with
+            commit_indices = commit
 
             def commit():
                 commit_indices()
-                for c in kv_cache:
-                    c["fp8_scales"] = scales      # what the codes in the cache were made with: they cannot be made again
-                    c["fp8_center"] = center_stamp
-        else:
-            fp8_shadow, fp8_keep = self._fp8_attention_shadow(kv_cache, use_cp)
-        # (the unsharded forward with the shadows as an argument; the context-parallel path has phases of its own, run_cp below)
-        forward = ("rtv_dit_forward",) if fp8_shadow is None or use_cp else ("rtv_dit_forward_attn_fp8", ctypes.byref(fp8_shadow))
-        if fp8_shadow is None:
-            fp8_key = None
-        elif isinstance(fp8_shadow, list):      # head exchange: one shadow per local rank
-            fp8_key = self._fp8_attn[:2] + ("heads", kv_cache[0]["k8_hp"][0].data_ptr(), kv_cache[-1]["v8t_hp"][-1].data_ptr())
-        else:
-            fp8_key = self._fp8_attn[:2] + (kv_cache[0]["k8"].data_ptr(), kv_cache[-1]["v8t"].data_ptr())
-        if fp8_only:      # the same struct, the entry point that never looks for a bf16 cache; part of the graph key like the scales
-            forward = ("rtv_dit_forward_attn_fp8_only", ctypes.byref(fp8_shadow))
-            fp8_key = ("only",) + fp8_key
-        if fp8_only and self._fp8_attention_codes():      # ... with the K rows centred as they are written
-            forward = ("rtv_dit_forward_attn_fp8_only_centered", ctypes.byref(fp8_shadow), fp8_keep[1][3])
-            fp8_key = ("only", "codes") + fp8_key[1:] + (self._fp8_attn_center.data_ptr(),)
-        if fp8_shadow is not None and self._fp8_attn_smooth and not fp8_only:      # the centred entry point: the centre table behind the shadow
-            forward = ("rtv_dit_forward_attn_fp8_centered", ctypes.byref(fp8_shadow), fp8_keep[1][3])
-            fp8_key += (self._fp8_attn_center.data_ptr(),)
+                plan.commit()
 
         def ptr_array(tensors):
             arr = (c_vp * L)(*[t_.data_ptr() for t_ in tensors])
@@ -1337,7 +995,7 @@ class CausalWanModel:
         if use_cp:
             commit()          # the exchanges below address the (shifted) cache rows
             if fp8_shadow is not None and any(c.get("fp8_filled") is None for c in kv_cache):
-                fp8_shadow, fp8_keep = self._fp8_attention_shadow(kv_cache, use_cp)      # a shift copy: refill, in place
+                fp8_shadow, fp8_keep = fa.shadow(kv_cache, use_cp)      # a shift copy: refill, in place
         if not use_cp:
             graph_key = None
             if self.use_hip_graphs and not need_cross:

@@ -529,8 +529,6 @@ __global__ __launch_bounds__(256) void attn_fp8_combine_kernel(const float* __re
   *(u32x4*)(o + (size_t)q * o_rs + (size_t)h * ATT_D + c8) = out;
 }
 
-static bool good_scale(float s) { return std::isfinite(s) && s > 0.f; }
-
 }  // namespace rtv
 
 using namespace rtv;

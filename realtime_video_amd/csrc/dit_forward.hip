@@ -918,6 +918,19 @@ static int check_fp8_only(const Ctx& c, const rtv_attn_fp8_shadow* sh) {
   return cut_written_rows(st, st->cache_row0, c.M, seg) < 0 ? -1 : 0;
 }
 
+// What the fp8 entry points ask of their shadow: need_shadow before anything else looks at the call (the four whole forwards),
+// check_shadow where the arrays are first needed (dit_forward behind its context, the sharded phases).
+static int need_shadow(const rtv_attn_fp8_shadow* shadow) {
+  if (!shadow) return set_error(-1, "dit: fp8 attention needs its shadow (rtv_attn_fp8_shadow)");
+  return 0;
+}
+static int check_shadow(const rtv_attn_fp8_shadow* shadow) {
+  RTV_TRY(need_shadow(shadow));
+  if (!shadow->k8 || !shadow->v8t || shadow->cache_rows <= 0)
+    return set_error(-1, "dit: fp8 attention needs the k8 / v8t shadow arrays and cache_rows");
+  return 0;
+}
+
 // The unsharded composition; fp8 != null: self-attention on the e4m3 shadows (rtv_dit_forward_attn_fp8), centers != null: whose K
 // codes are centred (rtv_dit_forward_attn_fp8_centered); fp8_only: whose shadows are the whole cache (rtv_dit_forward_attn_fp8_only;
 // with centers: rtv_dit_forward_attn_fp8_only_centered).
@@ -930,8 +943,7 @@ static int dit_forward(const rtv_dit_config* cfg, const rtv_dit_weights* w, cons
     // never a bf16 run in their place
     if (c.r0 != 0 || c.rc != c.M) return set_error(-1, "dit: fp8 attention does not support sharded calls (row_count < M)");
     if (st->attn_kv_splits > 1) return set_error(-1, "dit: fp8 attention does not support attn_kv_splits > 1");
-    if (!fp8->k8 || !fp8->v8t || fp8->cache_rows <= 0)
-      return set_error(-1, "dit: fp8 attention needs the k8 / v8t shadow arrays and cache_rows");
+    RTV_TRY(check_shadow(fp8));
     if (centers)
       for (int l = 0; l < c.L; ++l) {
         if (!centers[l]) return set_error(-1, "dit: fp8 attention: a layer has no K centre");
@@ -964,14 +976,14 @@ extern "C" int rtv_dit_forward(const rtv_dit_config* cfg, const rtv_dit_weights*
 extern "C" int rtv_dit_forward_attn_fp8(const rtv_dit_config* cfg, const rtv_dit_weights* w, const rtv_dit_step* st,
                                         const rtv_attn_fp8_shadow* shadow, void* workspace, size_t workspace_bytes,
                                         rtv_stream_t stream) {
-  if (!shadow) return set_error(-1, "dit: fp8 attention needs its shadow (rtv_attn_fp8_shadow)");
+  RTV_TRY(need_shadow(shadow));
   return dit_forward(cfg, w, st, shadow, nullptr, false, workspace, workspace_bytes, stream);
 }
 
 extern "C" int rtv_dit_forward_attn_fp8_centered(const rtv_dit_config* cfg, const rtv_dit_weights* w, const rtv_dit_step* st,
                                                  const rtv_attn_fp8_shadow* shadow, void* const* centers, void* workspace,
                                                  size_t workspace_bytes, rtv_stream_t stream) {
-  if (!shadow) return set_error(-1, "dit: fp8 attention needs its shadow (rtv_attn_fp8_shadow)");
+  RTV_TRY(need_shadow(shadow));
   if (!centers) return set_error(-1, "dit: centred fp8 attention needs its table of K centres");
   return dit_forward(cfg, w, st, shadow, centers, false, workspace, workspace_bytes, stream);
 }
@@ -979,26 +991,19 @@ extern "C" int rtv_dit_forward_attn_fp8_centered(const rtv_dit_config* cfg, cons
 extern "C" int rtv_dit_forward_attn_fp8_only(const rtv_dit_config* cfg, const rtv_dit_weights* w, const rtv_dit_step* st,
                                              const rtv_attn_fp8_shadow* shadow, void* workspace, size_t workspace_bytes,
                                              rtv_stream_t stream) {
-  if (!shadow) return set_error(-1, "dit: fp8 attention needs its shadow (rtv_attn_fp8_shadow)");
+  RTV_TRY(need_shadow(shadow));
   return dit_forward(cfg, w, st, shadow, nullptr, true, workspace, workspace_bytes, stream);
 }
 
 extern "C" int rtv_dit_forward_attn_fp8_only_centered(const rtv_dit_config* cfg, const rtv_dit_weights* w, const rtv_dit_step* st,
                                                       const rtv_attn_fp8_shadow* shadow, void* const* centers, void* workspace,
                                                       size_t workspace_bytes, rtv_stream_t stream) {
-  if (!shadow) return set_error(-1, "dit: fp8 attention needs its shadow (rtv_attn_fp8_shadow)");
+  RTV_TRY(need_shadow(shadow));
   if (!centers) return set_error(-1, "dit: centred fp8 attention needs its table of K centres");
   return dit_forward(cfg, w, st, shadow, centers, true, workspace, workspace_bytes, stream);
 }
 
 // ---- the sharded phases with the self-attention in fp8 (rtv_hip_attn_fp8_cp.h)
-static int check_shadow(const rtv_attn_fp8_shadow* shadow) {
-  if (!shadow) return set_error(-1, "dit: fp8 attention needs its shadow (rtv_attn_fp8_shadow)");
-  if (!shadow->k8 || !shadow->v8t || shadow->cache_rows <= 0)
-    return set_error(-1, "dit: fp8 attention needs the k8 / v8t shadow arrays and cache_rows");
-  return 0;
-}
-
 extern "C" int rtv_dit_quantize_block_attn_fp8(const rtv_dit_config* cfg, const rtv_dit_step* st, int layer, int heads,
                                                const rtv_attn_fp8_shadow* shadow, rtv_stream_t stream) {
   if (!cfg || !st) return set_error(-1, "dit: null argument");

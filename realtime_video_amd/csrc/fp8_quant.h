@@ -2,6 +2,8 @@
 //   s = max(max |x|, 1e-12) * fp32(1 / 448),   q = e4m3(clamp(x / s, -448, 448)),
 // the maximum taken over the tensor (gemm_fp8.hip) or over a row (fp8_rows.hip).
 #pragma once
+#include <cmath>
+
 #include "rtv_common.h"
 
 namespace rtv {
@@ -23,5 +25,22 @@ __device__ __forceinline__ u32x2 quantize8(const float* x, float scale) {
   w1 = __builtin_amdgcn_cvt_pk_fp8_f32(v[6], v[7], w1, true);
   return u32x2{(uint32_t)w0, (uint32_t)w1};
 }
+
+// The running maximum of a 256-thread workgroup's |x| into a device float kept as its bits, in two steps around a __syncthreads()
+// of the caller's: every wave leaves its maximum in s_max[4], then ONE thread folds the four and raises *amax.  Used by the e4m3 K
+// writer (kv_fp8.hip) and the recentre kernel (kv_fp8_center.hip); the quantisers of attn_fp8.hip / kv_fp8.hip write the same tail
+// out: on these helpers their launches measured slower (profiles/r26_kv_fp8_fold_ab.txt).
+__device__ __forceinline__ void block_max_stage(float v, float* s_max) {
+  v = wave_max(v);
+  if ((threadIdx.x & 63) == 0) s_max[threadIdx.x >> 6] = v;
+}
+__device__ __forceinline__ void block_max_commit(const float* s_max, unsigned* amax) {
+  // non-negative floats order like their bit patterns; most workgroups find the maximum already there and only read
+  const unsigned bits = __float_as_uint(fmaxf(fmaxf(s_max[0], s_max[1]), fmaxf(s_max[2], s_max[3])));
+  if (bits > __atomic_load_n(amax, __ATOMIC_RELAXED)) atomicMax(amax, bits);
+}
+
+// what every launcher asks of a quantisation scale
+inline bool good_scale(float s) { return std::isfinite(s) && s > 0.f; }
 
 }  // namespace rtv

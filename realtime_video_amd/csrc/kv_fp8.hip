@@ -1,10 +1,13 @@
-// The e4m3-only KV cache of fp8 self-attention (include/rtv_hip_attn_fp8_only.h): the two kernels that write a block's K and V rows
-// straight into k8 / v8t, with no bf16 cache row in between.
+// The e4m3-only KV cache of fp8 self-attention (include/rtv_hip_attn_fp8_only.h, rtv_hip_attn_fp8_only_center.h): the two kernels
+// that write a block's K and V rows straight into k8 / v8t, with no bf16 cache row in between.
 //
-//   qk_norm_rope_k8_kernel     qk_norm_rope_cache_kernel (elementwise.hip) with the k role storing e4m3 codes: the same canonical
-//                              sum of squares, the same roundings, the same RoPE, the same ring mapping; the rotated chunk is
-//                              packed to bf16 as the cache write packs it, unpacked, and quantised as attn_quantize_kv_kernel
+//   qk_norm_rope_k8_kernel<CPL, CENTER>  qk_norm_rope_cache_kernel (elementwise.hip) with the k role storing e4m3 codes: the same
+//                              canonical sum of squares, the same roundings, the same RoPE, the same ring mapping; the rotated chunk
+//                              is packed to bf16 as the cache write packs it, unpacked, and quantised as attn_quantize_kv_kernel
 //                              (attn_fp8.hip) quantises the cache row - so the codes are those of the shadow mode.  No V role.
+//                              CENTER codes k - c (K smoothing on the compact cache).  The row body restates that of the bf16 kernel
+//                              on purpose: carved into shared device functions it changed the instruction streams of the bf16
+//                              kernel, which the default path runs (profiles/r26_kv_fp8_fold_isa.txt).
 //   attn_quantize_v_rows_kernel  the V half of attn_quantize_kv_kernel reading a staging matrix (the V third of the projection
 //                              buffer) instead of the cache: one workgroup per (storage tile, head), whole tiles leave LDS as
 //                              16-byte pieces, partly covered tiles as words and bytes of their own rows only.
@@ -12,6 +15,7 @@
 #include <cmath>
 
 #include "../../include/rtv_hip_attn_fp8_only.h"
+#include "../../include/rtv_hip_attn_fp8_only_center.h"
 #include "attn_common.h"
 #include "fp8_quant.h"
 #include "ln_row.h"
@@ -26,6 +30,7 @@ struct RopeK8Args {
   bf16_t* q_out;     // null: no q role (the kv_only pass)
   uint8_t* k8;
   unsigned* amax;    // null: no running maximum
+  const float* center;   // CENTER only: [H][128] fp32 = [d] in the row's column order
   float k_scale;
   int cache_row0;
   int M, d, hd;
@@ -40,7 +45,9 @@ struct RopeK8Args {
 // Two waves per row as in qk_norm_rope_cache_kernel: one normalises and rotates q, the other k (one wave per row without q).
 // A wave behind the last row does nothing but reach the barrier of the workgroup's maximum.  The head dimension is 128, so a lane's
 // four (cos, sin) pairs are the same for all of its chunks (the LANE_CS form of qk_norm_rope_cache_kernel).
-template <int CPL>
+// CENTER: the centre is read at the point of use - two 16-byte loads per chunk, L2-resident, 20 KB at 14B width - and never held
+// across the row.
+template <int CPL, bool CENTER>
 __global__ __launch_bounds__(EW_THREADS) __attribute__((amdgpu_waves_per_eu(CPL <= 10 ? 5 : 3, 8))) void qk_norm_rope_k8_kernel(RopeK8Args a) {
   __shared__ float s_max[EW_THREADS / 64];
   const int lane = threadIdx.x & 63;
@@ -118,6 +125,11 @@ __global__ __launch_bounds__(EW_THREADS) __attribute__((amdgpu_waves_per_eu(CPL 
           *(u32x4*)(qo + c * 8) = packed;
         } else {
           unpack_bf16x8(packed, x);            // ... and what the quantiser would read back from the cache
+          if constexpr (CENTER) {
+            const f32x4 ce0 = *(const f32x4*)(a.center + c * 8), ce1 = *(const f32x4*)(a.center + c * 8 + 4);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) x[j] -= ce0[j], x[4 + j] -= ce1[j];   // fp32, rounded once, before the division
+          }
 #pragma unroll
           for (int j = 0; j < 8; ++j) kmax = fmaxf(kmax, fabsf(x[j]));
           *(u32x2*)(ko + c * 8) = quantize8(x, a.k_scale);
@@ -126,14 +138,9 @@ __global__ __launch_bounds__(EW_THREADS) __attribute__((amdgpu_waves_per_eu(CPL 
     }
   }
   if (a.amax == nullptr) return;   // kernel-uniform
-  kmax = wave_max(kmax);
-  if (lane == 0) s_max[threadIdx.x >> 6] = kmax;
+  block_max_stage(kmax, s_max);
   __syncthreads();
-  if (threadIdx.x == 0) {
-    // non-negative floats order like their bit patterns; most workgroups find the maximum already there and only read
-    const unsigned bits = __float_as_uint(fmaxf(fmaxf(s_max[0], s_max[1]), fmaxf(s_max[2], s_max[3])));
-    if (bits > __atomic_load_n(a.amax, __ATOMIC_RELAXED)) atomicMax(a.amax, bits);
-  }
+  if (threadIdx.x == 0) block_max_commit(s_max, a.amax);
 }
 
 struct QuantVArgs {
@@ -215,16 +222,15 @@ __global__ __launch_bounds__(256) void attn_quantize_v_rows_kernel(QuantVArgs p)
   }
 }
 
-static bool good_scale(float s) { return std::isfinite(s) && s > 0.f; }
-
 }  // namespace rtv
 
 using namespace rtv;
 
-extern "C" int rtv_qk_norm_rope_k8(const void* qkv, void* q_out, void* k8, int cache_rows, float k_scale, void* amax, int cache_row0,
-                                   int M, int d, int num_heads, float eps, const void* wq, const void* wk, const void* rope_cs, int F,
-                                   int gh, int gw, int start_frame, int row_offset, int ring_lo, int ring_size, int ring_shift,
-                                   rtv_stream_t stream) {
+// The checks and the launch of both e4m3 K writers; center != null selects the CENTER instantiation.
+static int qk_norm_rope_k8_launch(const char* who, const void* qkv, void* q_out, void* k8, int cache_rows, float k_scale, void* amax,
+                                  int cache_row0, int M, int d, int num_heads, float eps, const void* wq, const void* wk,
+                                  const void* rope_cs, int F, int gh, int gw, int start_frame, int row_offset, int ring_lo,
+                                  int ring_size, int ring_shift, const float* center, rtv_stream_t stream) {
   if (M <= 0) return 0;
   if (qk_norm_rope_check(d, cache_row0, M, d, num_heads, F, gh, gw, start_frame, row_offset, 0, 0, 0, ring_lo, ring_size, ring_shift,
                          q_out ? 3 : 2))
@@ -260,14 +266,35 @@ extern "C" int rtv_qk_norm_rope_k8(const void* qkv, void* q_out, void* k8, int c
   a.ring_lo = ring_lo;
   a.ring_size = ring_size;
   a.ring_shift = ring_shift;
-  // bytes: q read + written as bf16, k read as bf16 and written as codes
+  a.center = center;
+  // bytes: q read + written as bf16, k read as bf16 and written as codes (the centre stays in L2)
   ProfScope prof(PROF_ROPE, (hipStream_t)stream, ((q_out ? 4.0 : 0.0) + 3.0) * M * d);
   const int waves = M * (q_out ? 2 : 1);
   const dim3 grid((waves + ROWS_PER_WG - 1) / ROWS_PER_WG);
-#define RTV_ROPE_K8_CALL(CPL) hipLaunchKernelGGL(qk_norm_rope_k8_kernel<CPL>, grid, dim3(EW_THREADS), 0, (hipStream_t)stream, a)
+#define RTV_ROPE_K8_CALL(CPL)                                                                                        \
+  if (center) hipLaunchKernelGGL((qk_norm_rope_k8_kernel<CPL, true>), grid, dim3(EW_THREADS), 0, (hipStream_t)stream, a); \
+  else hipLaunchKernelGGL((qk_norm_rope_k8_kernel<CPL, false>), grid, dim3(EW_THREADS), 0, (hipStream_t)stream, a)
   RTV_ROW_DISPATCH(d, RTV_ROPE_K8_CALL);
 #undef RTV_ROPE_K8_CALL
-  return check_launch("qk_norm_rope_k8");
+  return check_launch(who);
+}
+
+extern "C" int rtv_qk_norm_rope_k8(const void* qkv, void* q_out, void* k8, int cache_rows, float k_scale, void* amax, int cache_row0,
+                                   int M, int d, int num_heads, float eps, const void* wq, const void* wk, const void* rope_cs, int F,
+                                   int gh, int gw, int start_frame, int row_offset, int ring_lo, int ring_size, int ring_shift,
+                                   rtv_stream_t stream) {
+  return qk_norm_rope_k8_launch("qk_norm_rope_k8", qkv, q_out, k8, cache_rows, k_scale, amax, cache_row0, M, d, num_heads, eps, wq, wk,
+                                rope_cs, F, gh, gw, start_frame, row_offset, ring_lo, ring_size, ring_shift, nullptr, stream);
+}
+
+extern "C" int rtv_qk_norm_rope_k8_centered(const void* qkv, void* q_out, void* k8, int cache_rows, float k_scale, void* amax,
+                                            int cache_row0, int M, int d, int num_heads, float eps, const void* wq, const void* wk,
+                                            const void* rope_cs, int F, int gh, int gw, int start_frame, int row_offset, int ring_lo,
+                                            int ring_size, int ring_shift, const float* center, rtv_stream_t stream) {
+  if (!center || ((uintptr_t)center & 15))
+    return set_error(-1, "qk_norm_rope_k8: center must be a 16-byte aligned device float[H][128]");
+  return qk_norm_rope_k8_launch("qk_norm_rope_k8_centered", qkv, q_out, k8, cache_rows, k_scale, amax, cache_row0, M, d, num_heads, eps,
+                                wq, wk, rope_cs, F, gh, gw, start_frame, row_offset, ring_lo, ring_size, ring_shift, center, stream);
 }
 
 extern "C" int rtv_attn_quantize_v_rows(const void* v_src, int64_t src_row_stride, int rows, int H, void* v8t, int cache_rows,

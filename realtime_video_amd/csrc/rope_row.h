@@ -1,4 +1,5 @@
-// What the wave-per-row RoPE kernels share: qk_norm_rope_cache_kernel (elementwise.hip) and its e4m3 form (kv_fp8.hip).
+// What the wave-per-row RoPE kernels share: qk_norm_rope_cache_kernel (elementwise.hip) and its e4m3 form
+// qk_norm_rope_k8_kernel<CPL, CENTER> (kv_fp8.hip).  The row body itself is written out in both: see the header of kv_fp8.hip.
 #pragma once
 #include "rtv_common.h"
 

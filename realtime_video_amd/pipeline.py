@@ -61,7 +61,7 @@ class CausalInferencePipeline:
         model = self.generator.model
         heads = model.kv_cache_heads() if hasattr(model, "kv_cache_heads") else cfg.num_heads
         shape = [batch_size, kv_cache_size, heads, cfg.dim // cfg.num_heads]
-        if getattr(model, "_fp8_attention_only", lambda: False)():
+        if getattr(model, "_fp8_attention", None) is not None and model._fp8_attention.only():
             # enable_fp8_attention(bf16_cache=False): the compact dicts of new_fp8_kv_cache - two e4m3 arrays per layer and no bf16
             # arena.  A reset is the index reset below (rows outside the window are masked by the attention kernel).
             if batch_size != 1:

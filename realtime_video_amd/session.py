@@ -369,7 +369,7 @@ class GenerationSession:
     def _smooth_k_model(models):
         """The native model behind models.transformer when it runs enable_fp8_attention(smooth_k=True), else None."""
         model = getattr(models.transformer, "model", models.transformer)
-        on = getattr(model, "_fp8_attn", None) is not None and getattr(model, "_fp8_attn_smooth", False)
+        on = getattr(model, "_fp8_attention", None) is not None and model._fp8_attention.smooth()
         return model if on else None
 
     def fp8_attention_recenter(self, models=None):

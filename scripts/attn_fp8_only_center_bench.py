@@ -139,13 +139,13 @@ class Rig:
             self.kv = [{"k": torch.zeros(1, window, HEADS, 128, dtype=BF, device=DEV), "v": torch.zeros(1, window, HEADS, 128, dtype=BF, device=DEV),
                         "global_end_index": 0, "local_end_index": 0} for _ in range(model.num_layers)]
         if mode == "codes":                                          # (before its first row: nothing to move, no second rounding)
-            model.fp8_attention_set_centers(model._fp8_attn_center.clone(), self.kv)
+            model.fp8_attention_set_centers(model._fp8_attention.center.clone(), self.kv)
         for c in self.kv:
             c["global_end_index"] = c["local_end_index"] = window - M
         self.forward()
         if mode == "smooth":
             model.fp8_attention_recenter(self.kv)
-            assert bool(model._fp8_attn_center.any())
+            assert bool(model._fp8_attention.center.any())
             self.forward()
         torch.cuda.synchronize()
 

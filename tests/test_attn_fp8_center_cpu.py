@@ -113,15 +113,15 @@ def test_smooth_k_refuses_context_parallelism():
     from realtime_video_amd.parallel import SimulatedContextParallel
     m = CausalWanModel(dim=256, ffn_dim=512, num_heads=2, num_layers=1, text_dim=64)
     m.context_parallel = SimulatedContextParallel(2, "heads")
-    assert m.enable_fp8_attention(smooth_k=True) is m and m._fp8_attn_smooth
+    assert m.enable_fp8_attention(smooth_k=True) is m and m._fp8_attention.mode.smooth
     kv = [{"k": torch.zeros(1, 64, 2, 128, dtype=torch.bfloat16), "v": torch.zeros(1, 64, 2, 128, dtype=torch.bfloat16),
            "global_end_index": 0, "local_end_index": 0}]
     with pytest.raises(RuntimeError, match="context parallelism"):
-        m._fp8_attention_shadow(kv, True)
-    assert "k8" not in kv[0] and m._fp8_attn_center is None
+        m._fp8_attention.shadow(kv, True)
+    assert "k8" not in kv[0] and m._fp8_attention.center is None
     with pytest.raises(RuntimeError, match="has not run yet"):
         m.fp8_attention_recenter(kv)
     m.enable_fp8_attention()
-    assert not m._fp8_attn_smooth
+    assert not m._fp8_attention.mode.smooth
     with pytest.raises(RuntimeError, match="smooth_k=True"):
         m.fp8_attention_recenter(kv)

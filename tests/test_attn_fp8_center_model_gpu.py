@@ -69,8 +69,8 @@ def tiny():
 
 def _spy_caches(model):
     seen = []
-    orig = model._fp8_attention_shadow
-    model._fp8_attention_shadow = lambda kv, use_cp: (seen.append(kv), orig(kv, use_cp))[1]
+    orig = model._fp8_attention.shadow
+    model._fp8_attention.shadow = lambda kv, use_cp: (seen.append(kv), orig(kv, use_cp))[1]
     return seen
 
 
@@ -87,8 +87,8 @@ def test_smooth_k_before_any_recentre_is_the_plain_mode(tiny):
     assert all(torch.equal(a, b) for a, b in zip(plain, smooth))
     for a, b in zip(kv_p, kv_s):
         assert torch.equal(a["k8"], b["k8"]) and torch.equal(a["v8t"], b["v8t"])
-    assert m._fp8_attn_center.shape == (cfg["num_layers"], cfg["num_heads"], 128) and not bool(m._fp8_attn_center.any())
-    assert runs[0][2]._fp8_attn_center is None, "the plain mode allocated a centre"
+    assert m._fp8_attention.center.shape == (cfg["num_layers"], cfg["num_heads"], 128) and not bool(m._fp8_attention.center.any())
+    assert runs[0][2]._fp8_attention.center is None, "the plain mode allocated a centre"
     assert torch.equal(runs[0][2].fp8_attention_amax(), m.fp8_attention_amax())
     _shadow_matches_cache(kv_s)
 
@@ -106,7 +106,7 @@ def test_recentred_forwards_against_the_centred_oracle(tiny, monkeypatch):
     cond = {"prompt_embeds": [ctx.to(DEV)]}
     a, _ = wr(lat[0].to(DEV), cond, T.to(DEV), kv, ca, current_start=0)
     assert model.fp8_attention_recenter(kv) is model
-    centers = model._fp8_attn_center.cpu().to(DEV)
+    centers = model._fp8_attention.center.cpu().to(DEV)
     for l, c in enumerate(kv):                        # the means of the rows written so far, within the mean kernel's bound
         want = c["k"][0, :4680].double().mean(0)
         assert bool(((centers[l].double() - want).abs() <= 4680 * 2.0 ** -24 * c["k"][0, :4680].double().abs().mean(0)).all()), l
@@ -119,7 +119,7 @@ def test_recentred_forwards_against_the_centred_oracle(tiny, monkeypatch):
     _shadow_matches_centred_cache(kv, centers)
     b, _ = wr(lat[3].to(DEV), cond, T.to(DEV), kv, ca, current_start=4680)
     _shadow_matches_centred_cache(kv, centers)
-    assert torch.equal(model._fp8_attn_center, centers), "a forward wrote the centres"
+    assert torch.equal(model._fp8_attention.center, centers), "a forward wrote the centres"
     amax = model.fp8_attention_amax()
     assert bool((amax > 0).all()) and bool((amax < 448).all())
 
@@ -162,10 +162,10 @@ def test_smooth_k_on_a_wrapped_ring(tiny):
         flow, _ = wr(lat[b].to(DEV), {"prompt_embeds": [ctx_d]}, T.to(DEV), kv, ca, current_start=b * 4680)
         errs.append(rel_l2(flow, ref))
         shifts.append(int(kv[0].get("ring_start", 0)))
-        _shadow_matches_centred_cache(kv, model._fp8_attn_center)
+        _shadow_matches_centred_cache(kv, model._fp8_attention.center)
         if b in (0, 2):
             model.fp8_attention_recenter(kv)
-            orc.centers = model._fp8_attn_center.cpu().to(DEV)
+            orc.centers = model._fp8_attention.center.cpu().to(DEV)
             n = min(int(kv[0]["local_end_index"]), rows)
             assert n == (4680, 0, rows)[b]
             want = kv[0]["k"][0, :n].double().mean(0)
@@ -189,7 +189,7 @@ def test_recentre_allocates_nothing_and_graph_replay_equals_eager(tiny):
         cond = {"prompt_embeds": [ctx.to(DEV)]}
         wr(lat[0].to(DEV), cond, T.to(DEV), kv, ca, current_start=0)            # fills the text caches, the shadows, the centres
         model.fp8_attention_recenter(kv)
-        ptr = model._fp8_attn_center.data_ptr()
+        ptr = model._fp8_attention.center.data_ptr()
         lats = [x.to(DEV) for x in lat]
         tt = T.to(DEV)
         seq = []
@@ -198,9 +198,9 @@ def test_recentre_allocates_nothing_and_graph_replay_equals_eager(tiny):
                 gc.collect()
                 torch.cuda.synchronize()
                 before = torch.cuda.memory_allocated()
-                first = model._fp8_attn_center.clone().cpu()
+                first = model._fp8_attention.center.clone().cpu()
                 model.fp8_attention_recenter(kv)                                # rows [0, 9360) now: another centre, same buffer
-                assert not torch.equal(model._fp8_attn_center.cpu(), first) and model._fp8_attn_center.data_ptr() == ptr
+                assert not torch.equal(model._fp8_attention.center.cpu(), first) and model._fp8_attention.center.data_ptr() == ptr
             for c in kv:
                 c["global_end_index"] = c["local_end_index"] = 4680
             out, _ = wr(lats[1 + rep], cond, tt, kv, ca, current_start=4680)
@@ -210,8 +210,8 @@ def test_recentre_allocates_nothing_and_graph_replay_equals_eager(tiny):
         assert torch.cuda.memory_allocated() == before, "recentre + forward allocated"
         if graphs:
             assert any(isinstance(e, dict) for e in model._graphs.values()), "no graph was captured"
-        _shadow_matches_centred_cache(kv, model._fp8_attn_center)
-        outs[graphs], cents[graphs] = seq, model._fp8_attn_center.cpu()
+        _shadow_matches_centred_cache(kv, model._fp8_attention.center)
+        outs[graphs], cents[graphs] = seq, model._fp8_attention.center.cpu()
     assert torch.equal(cents[False], cents[True])
     assert all(torch.equal(a, b) for a, b in zip(outs[False], outs[True]))
 
@@ -236,8 +236,8 @@ def test_disable_restores_the_bf16_launches_and_reenabling_refills(tiny):
         c["k8"].zero_()
         c["global_end_index"] = c["local_end_index"] = 4680
     wr(lat[3].to(DEV), {"prompt_embeds": [ctx.to(DEV)]}, T.to(DEV), kv, ca, current_start=4680)
-    assert bool(model._fp8_attn_center.any())
-    _shadow_matches_centred_cache(kv, model._fp8_attn_center)
+    assert bool(model._fp8_attention.center.any())
+    _shadow_matches_centred_cache(kv, model._fp8_attention.center)
 
 
 def test_session_recentres_once_behind_its_first_block(tiny):
@@ -254,16 +254,16 @@ def test_session_recentres_once_behind_its_first_block(tiny):
     padded[0, :ctx.shape[0]] = ctx
     models = Models(transformer=wr, pipeline=pipe, text_encoder=StaticTextEncoder(padded.to(DEV)))
     sess = GenerationSession(GenerateParams(seed=9, num_blocks=2, num_denoising_steps=2, keep_first_frame=True), models, device=DEV)
-    assert model._fp8_attn_center is None and not sess._fp8_recentered
+    assert model._fp8_attention.center is None and not sess._fp8_recentered
     out0 = sess.generate_block()
-    assert sess._fp8_recentered and model._fp8_attn_center_epoch == 1 and bool(model._fp8_attn_center.any())
-    first = model._fp8_attn_center.clone()
+    assert sess._fp8_recentered and model._fp8_attention.center_epoch == 1 and bool(model._fp8_attention.center.any())
+    first = model._fp8_attention.center.clone()
     out1 = sess.generate_block()
-    assert model._fp8_attn_center_epoch == 1 and torch.equal(model._fp8_attn_center, first), "the session recentred on its own again"
+    assert model._fp8_attention.center_epoch == 1 and torch.equal(model._fp8_attention.center, first), "the session recentred on its own again"
     assert bool(torch.isfinite(out0).all()) and bool(torch.isfinite(out1).all())
     _shadow_matches_centred_cache(pipe.kv_cache1, first)
     sess.fp8_attention_recenter()
-    assert model._fp8_attn_center_epoch == 2 and not torch.equal(model._fp8_attn_center, first)
+    assert model._fp8_attention.center_epoch == 2 and not torch.equal(model._fp8_attention.center, first)
     model.enable_fp8_attention()
     with pytest.raises(RuntimeError, match="smooth_k=True"):
         sess.fp8_attention_recenter()
@@ -305,7 +305,7 @@ def test_native_centred_forward_refusals(tiny, monkeypatch):
         real(name, *args[:3], None, *args[4:])
     with pytest.raises(RuntimeError, match="needs its table of K centres"):
         real(name, *args[:4], None, *args[5:])
-    holes = (ctypes.c_void_p * cfg["num_layers"])(*[model._fp8_attn_center[l].data_ptr() for l in range(cfg["num_layers"])])
+    holes = (ctypes.c_void_p * cfg["num_layers"])(*[model._fp8_attention.center[l].data_ptr() for l in range(cfg["num_layers"])])
     holes[cfg["num_layers"] - 1] = None
     with pytest.raises(RuntimeError, match="a layer has no K centre"):
         real(name, *args[:4], holes, *args[5:])

@@ -28,8 +28,8 @@ def _cp(world, exchange, splits=1):
 
 def _spy_caches(model):
     seen = []
-    orig = model._fp8_attention_shadow
-    model._fp8_attention_shadow = lambda kv, use_cp: (seen.append(kv), orig(kv, use_cp))[1]
+    orig = model._fp8_attention.shadow
+    model._fp8_attention.shadow = lambda kv, use_cp: (seen.append(kv), orig(kv, use_cp))[1]
     return seen
 
 

@@ -97,8 +97,8 @@ def test_fp8_attention_against_the_oracle_and_the_bf16_model(tiny, monkeypatch):
     with pytest.raises(RuntimeError):
         model.fp8_attention_amax()
     kv_seen = []
-    orig = model._fp8_attention_shadow
-    model._fp8_attention_shadow = lambda kv, use_cp: (kv_seen.append(kv), orig(kv, use_cp))[1]
+    orig = model._fp8_attention.shadow
+    model._fp8_attention.shadow = lambda kv, use_cp: (kv_seen.append(kv), orig(kv, use_cp))[1]
     ours = _three_forwards(model, wr, lat, ctx, T, T0)
     vs_oracle = [rel_l2(o, r) for o, r in zip(ours, ref_fp8)]
     vs_bf16 = [rel_l2(o, b) for o, b in zip(ours, tiny["bf16"])]

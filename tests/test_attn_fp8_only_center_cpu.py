@@ -150,8 +150,8 @@ def test_enable_takes_codes_only_on_the_compact_cache():
     from realtime_video_amd.parallel import SimulatedContextParallel
     m = _model()
     assert m.enable_fp8_attention(bf16_cache=False, smooth_k="codes") is m
-    assert m._fp8_attention_only() and m._fp8_attention_codes() and m._fp8_attn_center is None
-    state = (m._fp8_attn, m._fp8_attn_smooth, m._fp8_attn_only)
+    assert m._fp8_attention.only() and m._fp8_attention.codes() and m._fp8_attention.center is None
+    state = (m._fp8_attention.mode, m._fp8_attention.mode.smooth, m._fp8_attention.mode.only)
     with pytest.raises(ValueError, match='smooth_k="codes"'):          # True stays the error it was, and names the new value
         m.enable_fp8_attention(smooth_k=True, bf16_cache=False)
     with pytest.raises(ValueError, match="bf16_cache=False"):
@@ -163,13 +163,13 @@ def test_enable_takes_codes_only_on_the_compact_cache():
     m.context_parallel = SimulatedContextParallel(2, "heads")
     with pytest.raises(ValueError, match="context parallelism"):
         m.enable_fp8_attention(smooth_k="codes", bf16_cache=False)
-    assert state == (m._fp8_attn, m._fp8_attn_smooth, m._fp8_attn_only), "a refused call changed the mode"
+    assert state == (m._fp8_attention.mode, m._fp8_attention.mode.smooth, m._fp8_attention.mode.only), "a refused call changed the mode"
     m.context_parallel = None
     # the plain compact mode and the shadow mode know no codes mode
     m.enable_fp8_attention(bf16_cache=False)
-    assert not m._fp8_attention_codes() and m._fp8_center_stamp() is None
+    assert not m._fp8_attention.codes() and m._fp8_attention.center_stamp() is None
     m.enable_fp8_attention(smooth_k=True)
-    assert not m._fp8_attention_codes() and m._fp8_attn_smooth is True
+    assert not m._fp8_attention.codes() and m._fp8_attention.mode.smooth is True
 
 
 def test_python_refusals_need_no_gpu():
@@ -204,7 +204,7 @@ def test_python_refusals_need_no_gpu():
     with pytest.raises(RuntimeError, match="has not run yet"):
         m.fp8_attention_recenter(compact)
     # a compact dict whose rows stand under other centres
-    m._fp8_attn_center_new = m._fp8_attn_center_ws = torch.zeros(1)     # (as if a forward had allocated them: the check comes first)
+    m._fp8_attention.center_new = m._fp8_attention.center_ws = torch.zeros(1)     # (as if a forward had allocated them: the check comes first)
     stale = [dict(compact[0], local_end_index=10, fp8_center=None)]
     with pytest.raises(RuntimeError, match="other K centres"):
         m.fp8_attention_recenter(stale)

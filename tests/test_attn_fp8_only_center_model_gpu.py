@@ -81,11 +81,11 @@ def test_codes_before_any_recentre_is_the_plain_compact_mode(tiny):
         assert _same_codes(c_c[i], c_p[i]), f"codes behind forward {i}"
     assert torch.equal(a_c, a_p)
     shape = (cfg["num_layers"], cfg["num_heads"], 128)
-    assert m_c._fp8_attn_center.shape == shape and m_c._fp8_attn_center_new.shape == shape
-    assert not bool(m_c._fp8_attn_center.any()) and not bool(m_c._fp8_attn_center_new.any())
-    assert m_c._fp8_attn_center_ws.numel() * 4 >= 37 * cfg["num_heads"] * 512
-    assert m_p._fp8_attn_center is None, "the plain compact mode allocated a centre"
-    assert all(c["fp8_center"] == m_c._fp8_center_stamp() for c in kv_c)
+    assert m_c._fp8_attention.center.shape == shape and m_c._fp8_attention.center_new.shape == shape
+    assert not bool(m_c._fp8_attention.center.any()) and not bool(m_c._fp8_attention.center_new.any())
+    assert m_c._fp8_attention.center_ws.numel() * 4 >= 37 * cfg["num_heads"] * 512
+    assert m_p._fp8_attention.center is None, "the plain compact mode allocated a centre"
+    assert all(c["fp8_center"] == m_c._fp8_attention.center_stamp() for c in kv_c)
 
 
 def _sequence(tiny, model, wr, kv, ca, lat):
@@ -105,7 +105,7 @@ def test_given_centres_equal_the_shadow_mode_under_the_same_centres(tiny):
         model, wr = _model(tiny, mode)
         kv, ca = _kv(model, cfg, 9360, mode == "codes")
         assert model.fp8_attention_set_centers(centres, kv if mode == "codes" else None) is model
-        assert torch.equal(model._fp8_attn_center, centres) and model._fp8_attn_center.data_ptr() != centres.data_ptr()
+        assert torch.equal(model._fp8_attention.center, centres) and model._fp8_attention.center.data_ptr() != centres.data_ptr()
         got[mode] = _sequence(tiny, model, wr, kv, ca, lat) + (model.fp8_attention_amax().clone(),)
     (o_s, c_s, a_s), (o_c, c_c, a_c) = got["smooth"], got["codes"]
     for i in range(4):
@@ -155,12 +155,12 @@ def test_recentre_moves_the_cached_codes_and_the_next_forwards_hold_the_bound(ti
     a, _ = wr(lat[0].to(DEV), cond, T.to(DEV), kv, ca, current_start=0)
     before = _codes(kv)
     amax0 = model.fp8_attention_amax().clone()
-    ptrs = (model._fp8_attn_center.data_ptr(), model._fp8_attn_center_new.data_ptr())
+    ptrs = (model._fp8_attention.center.data_ptr(), model._fp8_attention.center_new.data_ptr())
     mem = _allocated()
     assert model.fp8_attention_recenter(kv) is model
     assert _allocated() == mem, "the recentre allocated"
-    assert ptrs == (model._fp8_attn_center.data_ptr(), model._fp8_attn_center_new.data_ptr())
-    centres = model._fp8_attn_center.clone()
+    assert ptrs == (model._fp8_attention.center.data_ptr(), model._fp8_attention.center_new.data_ptr())
+    centres = model._fp8_attention.center.clone()
     zero = torch.zeros_like(centres[0])
     for l, c in enumerate(kv):
         old = before[l][0]
@@ -172,7 +172,7 @@ def test_recentre_moves_the_cached_codes_and_the_next_forwards_hold_the_bound(ti
         assert torch.equal(c["k8"][:4680], moved), l
         assert torch.equal(c["k8"][4680:], old[4680:]) and torch.equal(c["v8t"], before[l][1]), l
         assert float(model.fp8_attention_amax()[l, 0]) == max(float(amax0[l, 0]), float(t.abs().max()))
-        assert c["fp8_center"] == model._fp8_center_stamp()
+        assert c["fp8_center"] == model._fp8_attention.center_stamp()
     assert bool(centres.any())
 
     for c in kv:
@@ -181,7 +181,7 @@ def test_recentre_moves_the_cached_codes_and_the_next_forwards_hold_the_bound(ti
     rc, _ = wr(lat[2].to(DEV), cond, T0.to(DEV), kv, ca, current_start=4680)
     _block_mask(model, False)
     b, _ = wr(lat[3].to(DEV), cond, T.to(DEV), kv, ca, current_start=4680)
-    assert torch.equal(model._fp8_attn_center, centres), "a forward wrote the centres"
+    assert torch.equal(model._fp8_attention.center, centres), "a forward wrote the centres"
 
     orc = CentredOracle(cfg["num_layers"])
     monkeypatch.setattr(wo, "attention_block_causal", orc.block_causal)
@@ -215,14 +215,14 @@ def test_recentre_allocates_nothing_and_graph_replay_equals_eager(tiny):
         cond = {"prompt_embeds": [ctx.to(DEV)]}
         wr(lat[0].to(DEV), cond, T.to(DEV), kv, ca, current_start=0)
         model.fp8_attention_recenter(kv)
-        ptr = model._fp8_attn_center.data_ptr()
+        ptr = model._fp8_attention.center.data_ptr()
         lats, tt, seq = [x.to(DEV) for x in lat], T.to(DEV), []
         for rep in range(3):
             if rep == 2:
                 before = _allocated()
-                first = model._fp8_attn_center.clone().cpu()
+                first = model._fp8_attention.center.clone().cpu()
                 model.fp8_attention_recenter(kv)                                # rows [0, 9360) now
-                assert not torch.equal(model._fp8_attn_center.cpu(), first) and model._fp8_attn_center.data_ptr() == ptr
+                assert not torch.equal(model._fp8_attention.center.cpu(), first) and model._fp8_attention.center.data_ptr() == ptr
                 del first
             for c in kv:
                 c["global_end_index"] = c["local_end_index"] = 4680
@@ -233,7 +233,7 @@ def test_recentre_allocates_nothing_and_graph_replay_equals_eager(tiny):
         if graphs:
             assert any(isinstance(e, dict) for e in model._graphs.values()), "no graph was captured"
             assert all(k[-1][:2] == ("only", "codes") for k in model._graphs), "the graph key does not carry the mode"
-        outs[graphs] = (seq, _codes(kv), model._fp8_attn_center.cpu())
+        outs[graphs] = (seq, _codes(kv), model._fp8_attention.center.cpu())
     assert torch.equal(outs[False][2], outs[True][2])
     assert all(torch.equal(a, b) for a, b in zip(outs[False][0], outs[True][0])) and _same_codes(outs[False][1], outs[True][1])
 
@@ -269,10 +269,10 @@ def test_session_equals_a_shadow_mode_session_under_the_same_centres(tiny):
             blocks.append(sess.generate_block().cpu())
             assert len(recentres) == 1, (mode, b)
         if mode == "codes":
-            centres = model._fp8_attn_center.clone()
-            assert bool(centres.any()) and model._fp8_attn_center_epoch >= 1
+            centres = model._fp8_attention.center.clone()
+            assert bool(centres.any()) and model._fp8_attention.center_epoch >= 1
         else:
-            assert torch.equal(model._fp8_attn_center, centres)
+            assert torch.equal(model._fp8_attention.center, centres)
         latents[mode] = (blocks, sess.all_latents.cpu())
     for b in range(3):
         assert torch.equal(latents["codes"][0][b], latents["smooth"][0][b]), b
@@ -327,11 +327,11 @@ def test_conversion_of_a_live_cache_takes_the_current_shadow_over(tiny, centred,
             before = _allocated()
             assert model.convert_kv_cache_to_fp8(kv) is kv
             # (the centred mode makes its second centre buffer here, L x H x 512 bytes: below 1 MiB, counted at its size)
-            assert before - _allocated() == held - (model._fp8_attn_center_new.numel() * 4 if centred else 0)
+            assert before - _allocated() == held - (model._fp8_attention.center_new.numel() * 4 if centred else 0)
             monkeypatch.undo()
             assert not calls and k8_ptrs == [(c["k8"].data_ptr(), c["v8t"].data_ptr()) for c in kv]
             assert all("k" not in c and "v" not in c and "fp8_filled" not in c and c["rows"] == 9360 for c in kv)
-            assert all(c["fp8_scales"] == (1.0, 1.0) and c["fp8_center"] == model._fp8_center_stamp() for c in kv)
+            assert all(c["fp8_scales"] == (1.0, 1.0) and c["fp8_center"] == model._fp8_attention.center_stamp() for c in kv)
         runs.append((_fourth(tiny, wr, kv, ca), _codes(kv), model.fp8_attention_amax().clone(), int(kv[0]["local_end_index"])))
     (o_s, c_s, a_s, n_s), (o_c, c_c, a_c, n_c) = runs
     assert torch.equal(o_c, o_s) and _same_codes(c_c, c_s) and torch.equal(a_c, a_s) and n_c == n_s == 9360
@@ -384,7 +384,7 @@ def test_pipeline_converts_its_cache_and_frees_the_arena(tiny):
     gc.collect()
     assert kv is pipe.kv_cache1 and pipe._kv_arena is None and all("k" not in c and "v" not in c and c["rows"] == rows for c in kv)
     assert arena() is None, "something still holds the bf16 arena"
-    assert all(c["k8"].shape == (rows, H, 128) and c["fp8_center"] == model._fp8_center_stamp() for c in kv)
+    assert all(c["k8"].shape == (rows, H, 128) and c["fp8_center"] == model._fp8_attention.center_stamp() for c in kv)
     ptrs = [c["k8"].data_ptr() for c in kv]
     pipe._initialize_kv_cache(1, BF, DEV)                                        # a reset keeps the converted dicts
     assert pipe.kv_cache1 is kv and ptrs == [c["k8"].data_ptr() for c in kv]
@@ -409,9 +409,9 @@ def test_python_refusals_leave_the_indices_alone(tiny):
 
     refused(RuntimeError, "other K centres", other)
     refused(RuntimeError, "other K centres", other, lambda: model.fp8_attention_recenter(other))
-    refused(RuntimeError, "other K centres", other, lambda: model.fp8_attention_set_centers(model._fp8_attn_center.clone(), other))
+    refused(RuntimeError, "other K centres", other, lambda: model.fp8_attention_set_centers(model._fp8_attention.center.clone(), other))
     refused(ValueError, "heads", kv, lambda: model.fp8_attention_set_centers(torch.zeros(cfg["num_layers"], 1, 128, device=DEV)))
-    refused(ValueError, r"\[num_layers, H, 128\]", kv, lambda: model.fp8_attention_set_centers(model._fp8_attn_center.double()))
+    refused(ValueError, r"\[num_layers, H, 128\]", kv, lambda: model.fp8_attention_set_centers(model._fp8_attention.center.double()))
     refused(ValueError, "compact one already", kv, lambda: model.convert_kv_cache_to_fp8(kv))
     refused(ValueError, 'smooth_k="codes"', kv, lambda: model.enable_fp8_attention(smooth_k=True, bf16_cache=False))
     refused(ValueError, "bf16_cache=False", kv, lambda: model.enable_fp8_attention(smooth_k="codes"))
@@ -427,7 +427,7 @@ def test_python_refusals_leave_the_indices_alone(tiny):
     for c in other:
         c["global_end_index"] = c["local_end_index"] = 0
     wr(lat[0].to(DEV), cond, T.to(DEV), other, ca, current_start=0)
-    assert int(other[0]["local_end_index"]) == 4680 and other[0]["fp8_center"] == model._fp8_center_stamp()
+    assert int(other[0]["local_end_index"]) == 4680 and other[0]["fp8_center"] == model._fp8_attention.center_stamp()
 
 
 def test_native_forward_refusals(tiny, monkeypatch):
@@ -465,12 +465,12 @@ def test_native_forward_refusals(tiny, monkeypatch):
     step.attn_kv_splits = 1
     refused("needs its shadow", *args[:3], None, *args[4:])
     refused("needs its table of K centres", *args[:4], None, *args[5:])
-    table = lambda: (ctypes.c_void_p * L)(*[model._fp8_attn_center[l].data_ptr() for l in range(L)])
+    table = lambda: (ctypes.c_void_p * L)(*[model._fp8_attention.center[l].data_ptr() for l in range(L)])
     holes = table()
     holes[L - 1] = None
     refused("a layer has no K centre", *args[:4], holes, *args[5:])
     odd = table()
-    odd[L - 1] = model._fp8_attn_center[L - 1].data_ptr() + 4
+    odd[L - 1] = model._fp8_attention.center[L - 1].data_ptr() + 4
     refused("16-byte aligned", *args[:4], odd, *args[5:])
     shadow.cache_rows = 0
     refused("needs the k8 / v8t shadow arrays and cache_rows")

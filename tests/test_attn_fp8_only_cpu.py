@@ -41,9 +41,9 @@ def _model():
 def test_enable_refuses_what_the_compact_cache_cannot_run():
     """smooth_k and context parallelism are ValueErrors at the call, and a refused call leaves the model's mode as it was."""
     m = _model()
-    assert m.enable_fp8_attention(bf16_cache=False) is m and m._fp8_attention_only()
-    assert m.enable_fp8_attention() is m and not m._fp8_attention_only()          # the default is the shadow mode
-    state = (m._fp8_attn, m._fp8_attn_only, m._fp8_attn_smooth, m._fp8_attn_cp)
+    assert m.enable_fp8_attention(bf16_cache=False) is m and m._fp8_attention.only()
+    assert m.enable_fp8_attention() is m and not m._fp8_attention.only()          # the default is the shadow mode
+    state = (m._fp8_attention.mode, m._fp8_attention.mode.only, m._fp8_attention.mode.smooth, m._fp8_attention.mode.context_parallel)
     with pytest.raises(ValueError, match="smooth_k"):
         m.enable_fp8_attention(smooth_k=True, bf16_cache=False)
     with pytest.raises(ValueError, match="context parallelism"):
@@ -53,11 +53,11 @@ def test_enable_refuses_what_the_compact_cache_cannot_run():
     m.context_parallel = object()                                                  # a model with context_parallel set
     with pytest.raises(ValueError, match="context parallelism"):
         m.enable_fp8_attention(bf16_cache=False)
-    assert state == (m._fp8_attn, m._fp8_attn_only, m._fp8_attn_smooth, m._fp8_attn_cp)
+    assert state == (m._fp8_attention.mode, m._fp8_attention.mode.only, m._fp8_attention.mode.smooth, m._fp8_attention.mode.context_parallel)
     m.context_parallel = None
     m.enable_fp8_attention(k_scale=2.0, v_scale=0.5, bf16_cache=False)
-    assert m._fp8_attn[:2] == (2.0, 0.5) and m._fp8_attention_only()
-    assert m.disable_fp8_attention() is m and not m._fp8_attention_only()
+    assert m._fp8_attention.mode[:2] == (2.0, 0.5) and m._fp8_attention.only()
+    assert m.disable_fp8_attention() is m and not m._fp8_attention.only()
 
 
 def test_cache_rows_helper_reads_both_kinds_of_dict():
