@@ -15,12 +15,13 @@
  * The dict contract of the Python side (realtime_video_amd.CausalWanModel.enable_fp8_attention(bf16_cache=False)): the KV cache of
  * a layer is {"k8", "v8t", "rows", "global_end_index", "local_end_index"} (model.new_fp8_kv_cache(rows, device)), with no "k" /
  * "v" entry.  Refused there, never run in another precision: smooth_k=True (recentring reads the bf16 K cache),
- * context_parallel=True or a model with context_parallel set, a dict with "k" / "v" handed to a model in the mode, a compact dict
- * handed to a model that is not, and a change of k_scale / v_scale on a cache that holds rows (the codes cannot be derived again:
- * reset the cache).
+ * context_parallel=True or a model with context_parallel set when the call does not ask for context_parallel="codes", a dict with
+ * "k" / "v" handed to a model in the mode, a compact dict handed to a model that is not, and a change of k_scale / v_scale on a
+ * cache that holds rows (the codes cannot be derived again: reset the cache).
  *
- * Out of scope: context parallelism on a compact cache, K smoothing, converting a live bf16 cache into a compact one, and any
- * change to the attention kernel, which is rtv_attn_fwd_fp8 as it is. */
+ * Out of scope here: K smoothing and converting a live bf16 cache into a compact one (rtv_hip_attn_fp8_only_center.h), context
+ * parallelism on a compact cache (rtv_hip_attn_fp8_only_cp.h: the row exchange, carrying the codes; the head exchange stays
+ * refused), and any change to the attention kernel, which is rtv_attn_fwd_fp8 as it is. */
 #ifndef RTV_HIP_ATTN_FP8_ONLY_H
 #define RTV_HIP_ATTN_FP8_ONLY_H
 #include <stdint.h>

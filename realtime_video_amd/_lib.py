@@ -10,7 +10,8 @@ include/rtv_hip_attn_fp8.h (ATTN_FP8_STRUCTS / ATTN_FP8_PROTOTYPES), with the K 
 include/rtv_hip_attn_fp8_center.h (ATTN_FP8_CENTER_PROTOTYPES), its KV split and sharded phases,
 include/rtv_hip_attn_fp8_cp.h (ATTN_FP8_CP_PROTOTYPES), and the e4m3-only KV cache of that mode,
 include/rtv_hip_attn_fp8_only.h (ATTN_FP8_ONLY_PROTOTYPES), with K smoothing on that cache,
-include/rtv_hip_attn_fp8_only_center.h (ATTN_FP8_ONLY_CENTER_PROTOTYPES), and the MXFP4 Linears, include/rtv_hip_mxfp4.h (MXFP4_PROTOTYPES), and the MXFP6
+include/rtv_hip_attn_fp8_only_center.h (ATTN_FP8_ONLY_CENTER_PROTOTYPES), and that cache under the row exchange of context
+parallelism with the exchange carrying codes, include/rtv_hip_attn_fp8_only_cp.h (ATTN_FP8_ONLY_CP_PROTOTYPES), and the MXFP4 Linears, include/rtv_hip_mxfp4.h (MXFP4_PROTOTYPES), and the MXFP6
 Linears, include/rtv_hip_mxfp6.h (MXFP6_PROTOTYPES), and the block Hadamard rotation in front of both quantisers,
 include/rtv_hip_mx_rotate.h (MX_ROTATE_PROTOTYPES), and the unit entry points of the text encoder's kernels,
 include/rtv_hip_t5_units.h (T5_UNITS_PROTOTYPES), and the text encoder on e4m3 weights with its skinny-M weight-only GEMM,
@@ -148,6 +149,8 @@ ATTN_FP8_ONLY_HEADER = "rtv_hip_attn_fp8_only.h"   # the e4m3-only KV cache (no 
 ATTN_FP8_ONLY_PROTOTYPES = parse_header(_read(ATTN_FP8_ONLY_HEADER), {**STRUCTS, **ATTN_FP8_STRUCTS})
 ATTN_FP8_ONLY_CENTER_HEADER = "rtv_hip_attn_fp8_only_center.h"   # K smoothing on the e4m3-only cache: four entry points, no struct of its own
 ATTN_FP8_ONLY_CENTER_PROTOTYPES = parse_header(_read(ATTN_FP8_ONLY_CENTER_HEADER), {**STRUCTS, **ATTN_FP8_STRUCTS})
+ATTN_FP8_ONLY_CP_HEADER = "rtv_hip_attn_fp8_only_cp.h"   # the e4m3-only cache under the row exchange, codes on the wire: five entry points, no struct of its own
+ATTN_FP8_ONLY_CP_PROTOTYPES = parse_header(_read(ATTN_FP8_ONLY_CP_HEADER), {**STRUCTS, **ATTN_FP8_STRUCTS})
 MXFP4_HEADER = "rtv_hip_mxfp4.h"   # MXFP4 Linears (e2m1 codes, e8m0 block scales): three entry points, no struct of its own
 MXFP4_PROTOTYPES = parse_header(_read(MXFP4_HEADER), dict(STRUCTS))
 MXFP6_HEADER = "rtv_hip_mxfp6.h"   # MXFP6 Linears (e2m3 codes, e8m0 block scales): three entry points, no struct of its own
@@ -202,7 +205,7 @@ def load():
             f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C realtime_video_amd/csrc`). There is no CPU fallback for the HIP path.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(IO_PROTOTYPES.items()) + list(JPEG_PROTOTYPES.items()) + list(JPEGDEC_PROTOTYPES.items()) + list(LORA_PROTOTYPES.items()) + list(LORA_EXT_PROTOTYPES.items()) + list(CROSS_FOLD_PROTOTYPES.items()) + list(FP8_ROWS_PROTOTYPES.items()) + list(ATTN_FP8_PROTOTYPES.items()) + list(ATTN_FP8_CENTER_PROTOTYPES.items()) + list(ATTN_FP8_CP_PROTOTYPES.items()) + list(ATTN_FP8_ONLY_PROTOTYPES.items()) + list(ATTN_FP8_ONLY_CENTER_PROTOTYPES.items()) + list(MXFP4_PROTOTYPES.items()) + list(MXFP6_PROTOTYPES.items()) + list(MX_ROTATE_PROTOTYPES.items()) + list(T5_UNITS_PROTOTYPES.items()) + list(T5_W8_PROTOTYPES.items()):
+    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(IO_PROTOTYPES.items()) + list(JPEG_PROTOTYPES.items()) + list(JPEGDEC_PROTOTYPES.items()) + list(LORA_PROTOTYPES.items()) + list(LORA_EXT_PROTOTYPES.items()) + list(CROSS_FOLD_PROTOTYPES.items()) + list(FP8_ROWS_PROTOTYPES.items()) + list(ATTN_FP8_PROTOTYPES.items()) + list(ATTN_FP8_CENTER_PROTOTYPES.items()) + list(ATTN_FP8_CP_PROTOTYPES.items()) + list(ATTN_FP8_ONLY_PROTOTYPES.items()) + list(ATTN_FP8_ONLY_CENTER_PROTOTYPES.items()) + list(ATTN_FP8_ONLY_CP_PROTOTYPES.items()) + list(MXFP4_PROTOTYPES.items()) + list(MXFP6_PROTOTYPES.items()) + list(MX_ROTATE_PROTOTYPES.items()) + list(T5_UNITS_PROTOTYPES.items()) + list(T5_W8_PROTOTYPES.items()):
         fn = getattr(lib, name, None)
         if fn is None:
             # RTV_LIB_PATH = an older build of the same C ABI (A/B measurements): entry points added since are simply absent

@@ -505,7 +505,21 @@ class CausalWanModel:
         for bit.  The compact dicts record the centres their rows were written under ("fp8_center", as "fp8_scales" records the
         scales): a forward that finds rows under other centres raises RuntimeError before its first launch.  "codes" with
         bf16_cache=True or under context parallelism is a ValueError; smooth_k=True stays what it was - centres from the bf16
-        cache - and stays a ValueError with bf16_cache=False."""
+        cache - and stays a ValueError with bf16_cache=False.
+
+        bf16_cache=False, context_parallel="codes" (opt-in; include/rtv_hip_attn_fp8_only_cp.h): the compact cache under the ROW
+        exchange of context parallelism (ContextParallel(exchange="rows"), or "auto" where the head count does not divide), with
+        the exchange carrying the e4m3 codes.  Per layer a rank quantises only the rows it projected into its segment of a staging
+        buffer [world, 2, M / world, dim] (one per block size and device, allocated by the first forward), ONE in-place all-gather
+        moves every rank's codes - half the bytes of the bf16 rows -, and every rank places the gathered rows into its k8 / v8t by
+        the ring mapping of the rolling cache (no shift copy).  No bf16 cache row exists on any rank; codes, maxima and outputs
+        equal the unsharded compact forward's bit for bit (attn_kv_splits = 1).  A rank's fp8_attention_amax() covers the rows that
+        rank wrote: the elementwise maximum over the ranks is the unsharded table.  Refused: "codes" with bf16_cache=True or with
+        any smooth_k (ValueError here); a head exchange - "auto" included when it resolves to heads - (RuntimeError from the
+        forward, before its first launch, the cache indices untouched); convert_kv_cache_to_fp8() under context parallelism.
+        context_parallel=True with bf16_cache=False, and a model with context_parallel set when the call does not ask for
+        "codes", stay ValueErrors.  Not run on more than one GPU: a lockstep simulation of the ranks and two processes sharing one
+        GPU are what the tests cover."""
         self._fp8_attention.enable(k_scale, v_scale, smooth_k, context_parallel, bf16_cache)
         return self
 
@@ -522,7 +536,9 @@ class CausalWanModel:
 
     def fp8_attention_amax(self):
         """float32 [num_layers, 2]: the largest |k| and |v| (raw bf16 values) quantised into a shadow since the mode first ran.
-        With smooth_k=True the K column follows |k - c| under the centre of the time - the value that saturates at 448 * k_scale."""
+        With smooth_k=True the K column follows |k - c| under the centre of the time - the value that saturates at 448 * k_scale.
+        With context_parallel="codes" a rank's table covers the rows that rank wrote (it quantises no others): the elementwise
+        maximum of the ranks' tables is the table of the unsharded forward."""
         return self._fp8_attention.amax_table()
 
     def fp8_attention_recenter(self, kv_cache):
@@ -938,8 +954,13 @@ class CausalWanModel:
         fa = self._fp8_attention
         fa.check_kv_cache_kind(kv_cache, use_cp)
         fp8_only = fa.only()      # the dicts hold k8 / v8t and nothing in bf16 (include/rtv_hip_attn_fp8_only.h)
+        # the compact cache under the row exchange (include/rtv_hip_attn_fp8_only_cp.h): the exchange moves a staging buffer of codes
+        # and every rank places the gathered rows itself, by the ring mapping - so the cache keeps its ring, without a shift copy
+        cp_codes = use_cp and fa.cp_codes()
+        if cp_codes and M % cp.world:      # (refused before the cache bookkeeping is looked at)
+            raise ValueError(f"token count {M} is not divisible by the context-parallel degree {cp.world}")
         row0, lo, hi, start_frame, causal_block, (ring_lo, ring_size, ring_shift), commit = \
-            self._cache_window(kv_cache, M, current_start, fs, ring=not use_cp)
+            self._cache_window(kv_cache, M, current_start, fs, ring=not use_cp or cp_codes)
         L = self.num_layers
         rs = self.dim if fp8_only else kv_cache[0]["k"].stride(1)      # (the e4m3-only forward does not read the step's stride)
         for c in ([] if fp8_only else kv_cache):
@@ -952,6 +973,9 @@ class CausalWanModel:
         # and the fp8 part of the graph key
         plan = fa.plan(kv_cache, use_cp)
         fp8_shadow, fp8_keep, forward, fp8_key = plan.shadow, plan.keep, plan.forward, plan.key
+        kv8 = fa.staging(M, cp.world, u.device) if cp_codes else None
+        if cp_codes:
+            fp8_key += ("kv8", kv8.data_ptr())
         if plan.commit is not None:      # the compact cache records what its rows were coded with
             commit_indices = commit
 
@@ -994,7 +1018,7 @@ class CausalWanModel:
             ops.ensure_gemm_workspace(u.device)
         if use_cp:
             commit()          # the exchanges below address the (shifted) cache rows
-            if fp8_shadow is not None and any(c.get("fp8_filled") is None for c in kv_cache):
+            if fp8_shadow is not None and not fp8_only and any(c.get("fp8_filled") is None for c in kv_cache):
                 fp8_shadow, fp8_keep = fa.shadow(kv_cache, use_cp)      # a shift copy: refill, in place
         if not use_cp:
             graph_key = None
@@ -1095,6 +1119,25 @@ class CausalWanModel:
                 null = c_vp(0)
                 for l in range(L):
                     last_kv_only = kv_only and l == L - 1      # only the K / V rows of the last layer are still needed
+                    if cp_codes:
+                        # rows exchange of the compact cache: [LN | K,V -> codes] -> all-gather of the codes (async) -> [Q] -> wait
+                        # -> commit of the gathered codes into k8 / v8t, attention ...
+                        kv8_p = c_vp(kv8.data_ptr())
+                        for i, (st, wsa) in enumerate(parts):
+                            _lib.call("rtv_dit_layer_proj_attn_fp8_only", cfg_p, w_p, ctypes.byref(st), l, PROJ_LN | PROJ_KV, W, kv8_p,
+                                      fp8[i], *wsa)
+                        pend = cp.gather_codes(kv8, async_op=True)
+                        if last_kv_only:
+                            pend.wait()
+                            for (st, _), sh in zip(parts, fp8):
+                                _lib.call("rtv_dit_commit_block_attn_fp8_only", cfg_p, ctypes.byref(st), l, W, kv8_p, sh, stream)
+                            break
+                        for i, (st, wsa) in enumerate(parts):
+                            _lib.call("rtv_dit_layer_proj_attn_fp8_only", cfg_p, w_p, ctypes.byref(st), l, PROJ_Q, W, kv8_p, fp8[i], *wsa)
+                        pend.wait()
+                        for i, (st, wsa) in enumerate(parts):
+                            _lib.call("rtv_dit_layer_rest_attn_fp8_only", cfg_p, w_p, ctypes.byref(st), l, W, kv8_p, fp8[i], *wsa)
+                        continue
                     if not heads:
                         for st, wsa in parts:
                             _lib.call("rtv_dit_layer_proj", cfg_p, w_p, ctypes.byref(st), l, PROJ_LN | PROJ_KV, 0, null, null, *wsa)

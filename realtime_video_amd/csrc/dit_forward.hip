@@ -21,6 +21,7 @@
 #include "../../include/rtv_hip_attn_fp8_only_center.h"
 #include "../../include/rtv_hip_attn_fp8_cp.h"
 #include "../../include/rtv_hip_attn_fp8_only.h"
+#include "../../include/rtv_hip_attn_fp8_only_cp.h"
 #include "../../include/rtv_hip_mxfp4.h"
 #include "../../include/rtv_hip_mxfp6.h"
 #include "../../include/rtv_hip_mx_rotate.h"
@@ -167,6 +168,8 @@ struct Ctx {
                                     // e4m3 shadows; null in every other entry point
   void* const* centers;             // rtv_dit_forward_attn_fp8_centered: per-layer K centres of the shadows; null in every other one
   bool fp8_only;                    // rtv_dit_forward_attn_fp8_only: the shadows ARE the cache - st->kv_k / kv_v / kv_row_stride are not read
+  void* kv8;                        // the phases of rtv_hip_attn_fp8_only_cp.h: the staging buffer the K | V phase writes its codes into
+  int kv8_world;                    // (with fp8_only; the cache itself is written by the commit behind the exchange); null otherwise
   const uint8_t* modes;  // use_fp8 == 7: the mode of each Linear (linear_modes, checked by make_ctx); null otherwise
   int fold_kh, fold_k;   // cross-attention V folded into the output projection: columns per head / in all; 0 = the unfolded path
                          // (then st->ca_v[L + l] is layer l's folded weight, rtv_dit_step.ca_vo_ld)
@@ -212,6 +215,8 @@ static int make_ctx(const rtv_dit_config* cfg, const rtv_dit_weights* w, const r
   c->fp8 = nullptr;
   c->centers = nullptr;
   c->fp8_only = false;
+  c->kv8 = nullptr;
+  c->kv8_world = 0;
   c->stream = stream;
   c->d = cfg->dim;
   c->H = cfg->num_heads;
@@ -460,6 +465,7 @@ static int dit_begin(Ctx& c) {
 static int hp_check(Ctx& c, int world);
 static int quantize_written_rows(Ctx& c, int l);
 static int write_fp8_only_rows(Ctx& c, int l, bool q);
+static int stage_fp8_only_rows(Ctx& c, int l, bool q, bool kv);
 
 // ---- layer, part 1: LN+modulate -> QKV -> RMSNorm(q,k)+RoPE -> local K/V rows into the cache (or the exchange buffers).
 // `parts` selects what this call does, so that the host can put a collective between the two projections and let it run
@@ -545,6 +551,7 @@ static int dit_layer_proj(Ctx& c, int l, int parts, int world, void* q_send, voi
                                c.cfg->eps, lw.norm_q_w, lw.norm_k_w, c.w->rope_cs, c.F, c.gh, c.gw, st->start_frame, c.r0, gc,
                                (int64_t)c.rc * gc, (int64_t)c.rc * 2 * gc, 0, 0, 0, rope_parts, c.stream);
   }
+  if (c.fp8_only && c.kv8) return stage_fp8_only_rows(c, l, q, kv);   // rtv_dit_layer_proj_attn_fp8_only: codes into the staging buffer
   if (c.fp8_only) return write_fp8_only_rows(c, l, q);   // (never with exchange buffers: the mode refuses sharded steps)
   RTV_TRY(qk_norm_rope_launch(b.qkv, b.q, st->kv_k[l], st->kv_v[l], st->kv_row_stride, st->cache_row0, c.rc, d, c.H, c.cfg->eps,
                               lw.norm_q_w, lw.norm_k_w, c.w->rope_cs, c.F, c.gh, c.gw, st->start_frame, c.r0, 0, 0, 0, st->ring_lo,
@@ -627,6 +634,23 @@ static int write_fp8_only_rows(Ctx& c, int l, bool q) {
     RTV_TRY(rtv_attn_quantize_v_rows(v_src, 3 * d, seg[i][1], c.H, sh->v8t[l], sh->cache_rows, seg[i][0], sh->v_scale, amax, c.stream));
     v_src += (size_t)seg[i][1] * 3 * d;
   }
+  return 0;
+}
+
+// The e4m3-only cache under the row exchange (rtv_hip_attn_fp8_only_cp.h): the q rows into b.q as the bf16 path writes them, the
+// codes of the local K and V rows into the rank's segment of the staging buffer.  The cache is written behind the exchange.
+static int stage_fp8_only_rows(Ctx& c, int l, bool q, bool kv) {
+  const rtv_dit_layer_weights& lw = c.w->layers[l];
+  const rtv_dit_step* st = c.st;
+  const rtv_attn_fp8_shadow* sh = c.fp8;
+  const int d = c.d;
+  if (q)
+    RTV_TRY(qk_norm_rope_launch(c.b.qkv, c.b.q, nullptr, nullptr, d, st->cache_row0, c.rc, d, c.H, c.cfg->eps, lw.norm_q_w, lw.norm_k_w,
+                                c.w->rope_cs, c.F, c.gh, c.gw, st->start_frame, c.r0, 0, 0, 0, st->ring_lo, st->ring_size,
+                                st->ring_shift, 1, c.stream));
+  if (kv)
+    RTV_TRY(rtv_attn_fp8_stage_kv8(c.b.qkv, c.kv8, c.kv8_world, c.r0, c.rc, sh->k_scale, sh->v_scale, sh->amax ? sh->amax[l] : nullptr, d,
+                                   c.H, c.cfg->eps, lw.norm_k_w, c.w->rope_cs, c.F, c.gh, c.gw, st->start_frame, c.stream));
   return 0;
 }
 
@@ -1043,6 +1067,80 @@ extern "C" int rtv_dit_layer_attn_hp_attn_fp8(const rtv_dit_config* cfg, const r
   RTV_TRY(hp_check(c, world));
   RTV_TRY(check_fp8_split(c, c.M, c.H / world));
   return dit_layer_attn_hp(c, layer, world, q_all, o_all);
+}
+
+// ---- the e4m3-only cache under the row exchange: the exchange carries codes (rtv_hip_attn_fp8_only_cp.h)
+// What the three phases ask of the staging buffer and of the step's rows before anything is launched.
+static int check_kv8(const void* kv8, int world, int M) {
+  if (!kv8) return set_error(-1, "dit: fp8 attention: the code exchange needs its staging buffer kv8");
+  if ((uintptr_t)kv8 & 15) return set_error(-1, "dit: fp8 attention: kv8 must be 16-byte aligned");
+  if (world <= 0 || M % world) return set_error(-1, "dit: fp8 attention: M = F * gh * gw must be a multiple of world");
+  return 0;
+}
+
+// One layer's arrays and the scales, as check_fp8_only asks them of every layer.
+static int check_fp8_only_layer(const rtv_attn_fp8_shadow* sh, int l) {
+  if (!sh->k8[l] || !sh->v8t[l]) return set_error(-1, "dit: fp8 attention: a layer has no shadow");
+  if (((uintptr_t)sh->k8[l] | (uintptr_t)sh->v8t[l]) & 15) return set_error(-1, "dit: fp8 attention: k8 and v8t must be 16-byte aligned");
+  if (sh->amax && ((uintptr_t)sh->amax[l] & 3)) return set_error(-1, "dit: fp8 attention: amax must be 4-byte aligned");
+  if (!(std::isfinite(sh->k_scale) && sh->k_scale > 0.f && std::isfinite(sh->v_scale) && sh->v_scale > 0.f))
+    return set_error(-1, "dit: fp8 attention: scales must be finite and positive");
+  return 0;
+}
+
+extern "C" int rtv_dit_layer_proj_attn_fp8_only(const rtv_dit_config* cfg, const rtv_dit_weights* w, const rtv_dit_step* st, int layer,
+                                                int parts, int world, void* kv8, const rtv_attn_fp8_shadow* shadow, void* ws,
+                                                size_t ws_bytes, rtv_stream_t stream) {
+  Ctx c;
+  RTV_TRY(make_ctx(cfg, w, st, ws, ws_bytes, stream, &c));
+  if (layer < 0 || layer >= c.L) return set_error(-1, "dit: layer out of range");
+  RTV_TRY(check_shadow(shadow));
+  RTV_TRY(check_fp8_only_layer(shadow, layer));
+  RTV_TRY(check_kv8(kv8, world, c.M));
+  const int S = c.M / world;
+  if (c.r0 / S != (c.r0 + c.rc - 1) / S) return set_error(-1, "dit: fp8 attention: the local rows must lie in one rank's segment of kv8");
+  c.fp8 = shadow;
+  c.fp8_only = true;
+  c.kv8 = kv8;
+  c.kv8_world = world;
+  return dit_layer_proj(c, layer, parts, 0, nullptr, nullptr);
+}
+
+static int commit_block_fp8_only(const rtv_dit_step* st, int M, int H, int layer, int world, const void* kv8,
+                                 const rtv_attn_fp8_shadow* sh, rtv_stream_t stream) {
+  return rtv_attn_fp8_commit_kv8(kv8, world, M, H, sh->k8[layer], sh->v8t[layer], sh->cache_rows, st->cache_row0, st->ring_lo,
+                                 st->ring_size, st->ring_shift, stream);
+}
+
+extern "C" int rtv_dit_commit_block_attn_fp8_only(const rtv_dit_config* cfg, const rtv_dit_step* st, int layer, int world,
+                                                  const void* kv8, const rtv_attn_fp8_shadow* shadow, rtv_stream_t stream) {
+  if (!cfg || !st) return set_error(-1, "dit: null argument");
+  RTV_TRY(check_shadow(shadow));
+  if (layer < 0 || layer >= cfg->num_layers) return set_error(-1, "dit: layer out of range");
+  RTV_TRY(check_fp8_only_layer(shadow, layer));
+  const int64_t M = (int64_t)st->F * st->gh * st->gw;
+  if (st->F <= 0 || st->gh <= 0 || st->gw <= 0 || M > INT32_MAX) return set_error(-1, "dit: empty token grid");
+  RTV_TRY(check_kv8(kv8, world, (int)M));
+  return commit_block_fp8_only(st, (int)M, cfg->num_heads, layer, world, kv8, shadow, stream);
+}
+
+extern "C" int rtv_dit_layer_rest_attn_fp8_only(const rtv_dit_config* cfg, const rtv_dit_weights* w, const rtv_dit_step* st, int layer,
+                                                int world, const void* kv8, const rtv_attn_fp8_shadow* shadow, void* ws,
+                                                size_t ws_bytes, rtv_stream_t stream) {
+  Ctx c;
+  RTV_TRY(make_ctx(cfg, w, st, ws, ws_bytes, stream, &c));
+  if (layer < 0 || layer >= c.L) return set_error(-1, "dit: layer out of range");
+  RTV_TRY(check_shadow(shadow));
+  RTV_TRY(check_fp8_only_layer(shadow, layer));
+  RTV_TRY(check_kv8(kv8, world, c.M));
+  // (make_ctx: the written rows lie inside the window, and the window inside the ring when there is one)
+  const int64_t end = st->ring_size > 0 ? (int64_t)st->ring_lo + st->ring_size : (int64_t)st->kv_hi;
+  if (end > shadow->cache_rows) return set_error(-1, "dit: fp8 attention: the attention window lies outside [0, cache_rows)");
+  c.fp8 = shadow;
+  c.fp8_only = true;
+  RTV_TRY(check_fp8_split(c, c.rc, c.H));
+  RTV_TRY(commit_block_fp8_only(st, c.M, c.H, layer, world, kv8, shadow, stream));   // the gathered codes, every rank for itself
+  return dit_layer_rest(c, layer);
 }
 
 extern "C" int rtv_dit_lab_capture_self_attn(void* q_copy, void* o_copy) {

@@ -18,8 +18,9 @@ c_vp = ctypes.c_void_p
 _Fp8Shadow = _lib.ATTN_FP8_STRUCTS["rtv_attn_fp8_shadow"]
 
 # What enable_fp8_attention() set: the scales, the epoch of the call (bumps at every enable / disable: a shadow filled before it is
-# refilled from the bf16 cache), smooth in (False, True, "codes"), context_parallel (sharded forwards run in fp8 instead of raising)
-# and only (bf16_cache=False: the e4m3 arrays are the whole KV cache).
+# refilled from the bf16 cache), smooth in (False, True, "codes"), context_parallel in (False, True, "codes") (True: sharded forwards
+# run in fp8 instead of raising; "codes": the compact cache under the row exchange, the exchange carrying the e4m3 codes) and only
+# (bf16_cache=False: the e4m3 arrays are the whole KV cache).
 Mode = collections.namedtuple("Mode", ["k_scale", "v_scale", "epoch", "smooth", "context_parallel", "only"])
 
 # What _forward_inference takes from plan(): the shadow (None: bf16 attention; a list under the head exchange: one per local rank),
@@ -51,30 +52,39 @@ class Fp8Attention:
         self.center = None          # float32 [num_layers, H, 128], zero-filled, allocated once; recenter() / set_centers() write it
         self.center_new = None      # smooth "codes": the second centre buffer a recentre computes into, allocated with the first
         self.center_ws = None       # workspace of the mean kernels, allocated with the centre
+        self.kv8 = {}               # context_parallel="codes": (M, world, device) -> the staging buffer of the code exchange
         self.center_epoch = 0       # bumps at every recentre: part of a shadow's "fp8_filled" state, like the scales
 
     # ------------------------------------------------------------------ the mode
     def enable(self, k_scale, v_scale, smooth_k, context_parallel, bf16_cache):
         if smooth_k not in (False, True, "codes"):
             raise ValueError("enable_fp8_attention: smooth_k is False, True or \"codes\"")
+        if not any(context_parallel is v for v in (False, True)) and context_parallel != "codes":
+            raise ValueError("enable_fp8_attention: context_parallel is False, True or \"codes\"")
         codes = isinstance(smooth_k, str)
+        cp_codes = isinstance(context_parallel, str)
         if smooth_k and context_parallel:
-            raise ValueError(f"enable_fp8_attention: smooth_k={smooth_k!r} is not supported together with context_parallel=True")
+            raise ValueError(f"enable_fp8_attention: smooth_k={smooth_k!r} is not supported together with context_parallel={context_parallel!r}")
+        if cp_codes and bf16_cache:
+            raise ValueError("enable_fp8_attention: context_parallel=\"codes\" exchanges the codes of the compact cache: it needs "
+                             "bf16_cache=False (with the bf16 cache kept, context_parallel=True)")
         if codes and bf16_cache:
             raise ValueError("enable_fp8_attention: smooth_k=\"codes\" takes the centres from the codes of the compact cache: it needs "
                              "bf16_cache=False (with the bf16 cache kept, smooth_k=True)")
         if not bf16_cache and smooth_k and not codes:
             raise ValueError("enable_fp8_attention: smooth_k=True needs the bf16 KV cache (bf16_cache=False keeps none to take the centres from; "
                              "smooth_k=\"codes\" takes them from the codes)")
-        if not bf16_cache and (context_parallel or self.model.context_parallel is not None):
-            raise ValueError("enable_fp8_attention: bf16_cache=False does not support context parallelism")
+        if not bf16_cache and not cp_codes and (context_parallel or self.model.context_parallel is not None):
+            raise ValueError("enable_fp8_attention: bf16_cache=False does not support context parallelism "
+                             "(but for context_parallel=\"codes\" under ContextParallel(exchange=\"rows\"))")
         k_scale, v_scale = float(k_scale), float(v_scale)
         for s in (k_scale, v_scale):
             if not (math.isfinite(s) and s > 0):
                 raise ValueError("enable_fp8_attention: scales must be finite and positive")
         self.prev = self.mode
         self.epoch += 1
-        self.mode = Mode(k_scale, v_scale, self.epoch, "codes" if codes else bool(smooth_k), bool(context_parallel), not bf16_cache)
+        self.mode = Mode(k_scale, v_scale, self.epoch, "codes" if codes else bool(smooth_k),
+                         "codes" if cp_codes else bool(context_parallel), not bf16_cache)
 
     def disable(self):
         self.epoch += 1
@@ -89,6 +99,18 @@ class Fp8Attention:
     def codes(self):
         """enable_fp8_attention(bf16_cache=False, smooth_k="codes") is on."""
         return self.only() and self.mode.smooth == "codes"
+
+    def cp_codes(self):
+        """enable_fp8_attention(bf16_cache=False, context_parallel="codes") is on."""
+        return self.only() and self.mode.context_parallel == "codes"
+
+    def staging(self, M, world, device):
+        """The staging buffer of the code exchange (include/rtv_hip_attn_fp8_only_cp.h), one per (M, world, device) for all layers,
+        never reallocated: captured hipGraphs embed its address."""
+        key = (int(M), int(world), torch.device(device))
+        if key not in self.kv8:
+            self.kv8[key] = ops.attn_fp8_staging(M, self.model.num_heads, world, device)
+        return self.kv8[key]
 
     def center_stamp(self):
         """What a compact dict records as "fp8_center" when rows are written into it: None in the plain compact mode, else the
@@ -256,7 +278,12 @@ class Fp8Attention:
                 raise RuntimeError("this KV cache is an e4m3-only one (new_fp8_kv_cache): it needs enable_fp8_attention(bf16_cache=False)")
             return
         if use_cp or model.context_parallel is not None:
-            raise RuntimeError("enable_fp8_attention(bf16_cache=False) does not support context parallelism")
+            if not self.cp_codes():
+                raise RuntimeError("enable_fp8_attention(bf16_cache=False) does not support context parallelism "
+                                   "(but for context_parallel=\"codes\" under ContextParallel(exchange=\"rows\"))")
+            if model.context_parallel is not None and model.context_parallel.head_exchange(model.num_heads):
+                raise RuntimeError("enable_fp8_attention(bf16_cache=False, context_parallel=\"codes\") runs under the row exchange only "
+                                   "(the head exchange keeps 1 / world of the cache per rank already): use ContextParallel(exchange=\"rows\")")
         if not all(compact):
             raise RuntimeError("enable_fp8_attention(bf16_cache=False) needs the compact KV cache of new_fp8_kv_cache(): "
                                "this one has \"k\" / \"v\" entries")

@@ -436,6 +436,37 @@ def attn_quantize_v_rows(v_src, v8t, cache_rows, dst_row0, v_scale=1.0, amax=Non
     return v8t
 
 
+def attn_fp8_staging(M, H, world, device, fill=0):
+    """The staging buffer of the code exchange (include/rtv_hip_attn_fp8_only_cp.h): uint8 [world, 2, M / world, H * 128], rank r's
+    K codes then its V codes, one contiguous message per rank."""
+    if world <= 0 or M % world:
+        raise ValueError(f"attn_fp8_staging: {M} rows are not divisible by the context-parallel degree {world}")
+    return torch.full((world, 2, M // world, H * 128), fill, dtype=torch.uint8, device=device)
+
+
+def attn_fp8_stage_kv8(qkv, kv8, row_begin, num_heads, wk, rope_cs, grid, start_frame, eps=1e-6, k_scale=1.0, v_scale=1.0, amax=None):
+    """The codes of the logical rows [row_begin, row_begin + rows) of a block of F * gh * gw rows (qkv [rows, 3 d] bf16, the
+    projection output of those rows) into the staging buffer kv8 [world, 2, M / world, d] (rtv_attn_fp8_stage_kv8).  amax: optional
+    float32 [2], raised over the rows written.  A thin wrapper: the entry point itself refuses what it documents."""
+    _gpu(qkv, kv8, wk, rope_cs, amax)
+    rows, d3 = qkv.shape
+    F, gh, gw = grid
+    _lib.call("rtv_attn_fp8_stage_kv8", _ptr(qkv), _ptr(kv8), kv8.shape[0], int(row_begin), rows, float(k_scale), float(v_scale), _ptr(amax),
+              d3 // 3, int(num_heads), float(eps), _ptr(wk), _ptr(rope_cs), int(F), int(gh), int(gw), int(start_frame), _stream())
+    return kv8
+
+
+def attn_fp8_commit_kv8(kv8, k8, v8t, cache_row0, ring=(0, 0, 0)):
+    """The M = world * kv8.shape[2] rows of a gathered staging buffer into the logical rows [cache_row0, cache_row0 + M) of k8 / v8t,
+    ring = (ring_lo, ring_size, ring_shift) of the cache (rtv_attn_fp8_commit_kv8).  A thin wrapper: the entry point itself refuses
+    what it documents."""
+    _gpu(kv8, k8, v8t)
+    world, _, S, d = kv8.shape
+    _lib.call("rtv_attn_fp8_commit_kv8", _ptr(kv8), world, world * S, d // 128, _ptr(k8), _ptr(v8t), k8.shape[0], int(cache_row0),
+              int(ring[0]), int(ring[1]), int(ring[2]), _stream())
+    return k8, v8t
+
+
 # --------------------------------------------------------------------------------------- GEMM
 _gemm_ws = {}
 

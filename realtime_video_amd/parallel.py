@@ -21,7 +21,13 @@ Two exchange patterns around self-attention (`ContextParallel(exchange=...)`):
 fp8 self-attention (CausalWanModel.enable_fp8_attention(context_parallel=True), include/rtv_hip_attn_fp8_cp.h) rides on the same
 exchanges, which keep moving bf16 rows: behind an exchange every rank quantises the block's rows into its e4m3 shadow itself - all
 heads under "rows", the num_heads / world heads it owns under "heads" (one dense shadow per local rank) - and `attn_kv_splits` then
-selects the KV split of the fp8 kernel.  The shadow bytes are never exchanged.
+selects the KV split of the fp8 kernel.  In that mode the shadow bytes are never exchanged.
+
+The compact KV cache (enable_fp8_attention(bf16_cache=False, context_parallel="codes"), include/rtv_hip_attn_fp8_only_cp.h; "rows"
+only) exchanges the e4m3 CODES instead: a rank quantises the rows it projected into its segment of a staging buffer
+[world, 2, M / world, d] (K codes, then V codes: one contiguous message), `gather_codes` is the one in-place all-gather of that
+buffer - M*d*(w-1)/w bytes received per rank and layer, half of the bf16 rows' 2*M*d*(w-1)/w elements - and every rank places the
+gathered codes into its k8 / v8t itself.  No bf16 cache row exists on any rank.
 """
 import torch
 import torch.distributed as dist
@@ -203,6 +209,12 @@ class ContextParallel(_ExchangeChoice):
                 return Pending(work if self.overlap else None, timer=(self, kind))
         return done
 
+    def gather_codes(self, kv8, async_op=False):
+        """In-place all-gather of the staging buffer of the code exchange (uint8 [world, 2, M / world, d]; this rank's segment
+        filled): ONE collective per layer."""
+        pend = self.all_gather_rows_(kv8, async_op, kind="gather_kv8")
+        return pend if async_op else None
+
     def gather_kv(self, k, v, row0, M, async_op=False):
         """All-gather cache rows [row0, row0+M) of one layer's K and V ([kv_size, H, hd] views).  If K and V rows
         are interleaved in one arena ([kv_size, 2, H, hd]) this is ONE collective, otherwise two."""
@@ -313,6 +325,9 @@ class SimulatedContextParallel(_ExchangeChoice):
         return Pending() if async_op else buf
 
     def gather_kv(self, k, v, row0, M, async_op=False):
+        return Pending() if async_op else None
+
+    def gather_codes(self, kv8, async_op=False):
         return Pending() if async_op else None
 
     def exchange_qkv(self, parts, k, v, row0, M):
